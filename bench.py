@@ -4,19 +4,24 @@
 `python bench.py --gpus N --steps K --warmup W`; for N > 1 the driver launches it under torch.distributed.run (one rank per GPU over
 RCCL); started WITHOUT a launcher (`WORLD_SIZE` unset) it spawns the N ranks itself (self_spawn).  A step is the full train step: forward -> BCE+Dice -> backward -> gradient all-reduce -> global clip + BertAdam, fp32 results,
 train mode with the reference's dropout 0.2, synthetic inputs / name-hashed synthetic weights (no network), inputs resident in HBM
-before the timed region.  Rank 0 prints ONE JSON line:
+before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run measures the MAIN configuration only: set-up, W warm-up steps, EXACTLY K timed steps, the line.  `--dump-outputs DIR` writes what the
+last timed step produced (the loss and the model state it leaves; float32 .npy files, < 64 MB, a fixed seeded sample of the larger tensors) so that
+two builds can be compared output for output.  Everything else below -- roofline, the BraTS / polyp blocks, the other operation order, the H2D-inclusive
+rate, the hipGraph replays, the CPU baseline and bench_shapes.json -- is measured only with `--full`:
 
   * the MAIN measurement (`metric`, `value`, ...): BASELINE.json configs[1] -- REFUGE fundus 2D, eff-b4, --translayers 3 --layercompress
     1,1,2,2, 512 x 512, batch 6 PER GPU (weak scaling) -- W warm-up steps, then EXACTLY K steps inside one barrier + synchronize bracket;
     `value` = images of all ranks / that time (max over ranks); per-step HIP-event times give `ms_per_step_median` beside it;
-  * `"brats"`: the 3-D half of the metric measured the same way in the same process (own `roofline`): cfg4 (BraTS 112 x 112 x 96, bs 4, one
+  * `"brats"` (--full): the 3-D half of the metric measured the same way in the same process (own `roofline`): cfg4 (BraTS 112 x 112 x 96, bs 4, one
     layer, BASELINE configs[3]) at N = 1, and cfg5 (128^3, 4 volumes per GPU, two layers, BASELINE configs[4]: the configuration the
     >= 6x scaling target is stated on) at every N;
-  * `"polyp"` (N > 1 only): BASELINE configs[2], polyp 352 x 352, at 6 images per GPU and with the reference's global batch 6 split over the ranks;
-  * `roofline`: the dominant kernel family = the tile engine (dense + implicit-GEMM kernels), with `attention_gemms`: up to six of the mode-batched
+  * `"polyp"` (--full): BASELINE configs[2], polyp 352 x 352, at 6 images per GPU and with the reference's global batch 6 split over the ranks;
+  * `roofline` (--full): the dominant kernel family = the tile engine (dense + implicit-GEMM kernels), with `attention_gemms`: up to six of the mode-batched
     squeezed-attention QK^T / P.V GEMMs as [M, N, K, batch, ms_per_step, TFLOP/s, frac]; `cpu_baseline`: the oracle on the host cores.
-The printed line is the COMPACT form (compact_line(): < 4 KB, the driver keeps an ~8 KB tail); the whole result -- `by_shape` (the twelve engine shapes
-with the most time, each with its FLOP per byte and applicable roof), notes, per-step extremes -- is written to bench_shapes.json beside this file.
+The printed line is the COMPACT form (compact_line(): < 4 KB, the driver keeps an ~8 KB tail); with --full the whole result -- `by_shape` (the twelve
+engine shapes with the most time, each with its FLOP per byte and applicable roof), notes, per-step extremes -- is written to bench_shapes.json beside this file.
 `--config cfgN` makes another BASELINE configuration the main measurement; `--engine f32` times the fp32-MFMA engine instead of bf16x6.
 """
 import argparse
@@ -212,8 +217,33 @@ def engine_roofline(prof, steps, cfg_name, engine_name, mode_batch=None):
     return roof, achieved
 
 
-def measure(cfg_name, args, steps, warmup, rank, world, dev, other_order=True, batch=None):
-    """W warm-up steps, EXACTLY `steps` timed steps inside a barrier + synchronize bracket (max over ranks), engine launches profiled."""
+DUMP_LIMIT = 60 << 20               # bytes of .npy data --dump-outputs may write (under 64 MB, decimal or binary)
+
+
+def dump_outputs(out_dir, loss, net, limit=DUMP_LIMIT):
+    """What a caller of the train step holds after the last timed step: the loss it returned (loss.npy) and the state it left in the model
+    (state.<key>.npy for every floating-point parameter and buffer), float32.  When the state is larger than `limit`, every tensor is cut to the same
+    fraction of its elements at indices drawn from a generator seeded by the tensor's name: the same elements in every run and every build."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'loss.npy'), loss.detach().float().reshape(1).cpu().numpy())
+    sd = [(k, v) for k, v in net.state_dict().items() if v.is_floating_point()]
+    total = sum(v.numel() for _, v in sd)
+    budget = (limit - 4 - 128 * (len(sd) + 1)) // 4                # elements, less the 128-byte .npy headers
+    frac = 1.0 if total <= budget else 0.99 * budget / total         # the 1 % covers the >= 1 element kept per tensor
+    for k, v in sd:
+        flat = v.detach().reshape(-1)
+        if frac < 1.0:
+            n = max(1, int(flat.numel() * frac))
+            idx = np.sort(np.random.default_rng(zlib.crc32(k.encode())).choice(flat.numel(), n, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(out_dir, 'state.%s.npy' % k), flat.float().cpu().numpy())
+
+
+def measure(cfg_name, args, steps, warmup, rank, world, dev, other_order=True, batch=None, dump_dir=None):
+    """W warm-up steps, EXACTLY `steps` timed steps inside a barrier + synchronize bracket (max over ranks); with --full the engine launches of every
+    PROF_EVERY-th timed step are profiled and the extra rates (other operation order, H2D-inclusive) are measured after the timed steps."""
     from segtran_amd import engine, segx, dist as sdist, functional as SF
     from segtran_amd.networks import segtran_shared as ss
     from segtran_amd.efficientnet.model import MBConvBlock
@@ -255,7 +285,7 @@ def measure(cfg_name, args, steps, warmup, rank, world, dev, other_order=True, b
     # r04_w measured the same step at 67.2 ms without them -- H2D copies included -- and 68.9 ms with them on every step); the roofline is computed
     # over those launches (5 of 50 steps by default; every step when fewer than 10 steps are timed: profiler runs)
     prof_every = 1 if (steps < 10 or graphed) else PROF_EVERY
-    prof_list = None if graphed else []
+    prof_list = None if (graphed or not args.full) else []
     prof_steps = 0
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
     # the per-launch profiling events are ~700 Python objects per step: a generation-2 collection in the middle of the timed region stalls the host for
@@ -279,6 +309,8 @@ def measure(cfg_name, args, steps, warmup, rank, world, dev, other_order=True, b
     finally:
         gc.enable()
     prof, L.gemm_prof = (prof_list or []), None
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, loss, net)                          # before any untimed step below moves the state on
     per_step = [ev[i].elapsed_time(ev[i + 1]) for i in range(steps)]
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -286,7 +318,7 @@ def measure(cfg_name, args, steps, warmup, rank, world, dev, other_order=True, b
         dt = t.item()
     other = None
     with_h2d = None
-    if world == 1 and not graphed and not args.single_order:
+    if args.full and world == 1 and not graphed and not args.single_order:
         # SURVEY.md 8(d) starts the step at the H2D copy of a pre-generated batch: the same step fed from a PINNED host batch, copy on the step's
         # stream inside the timed region (no loader thread hiding it).  Reported beside `value`, which keeps the inputs resident in HBM.
         xh, rh = x.cpu().pin_memory(), raw.cpu().pin_memory()
@@ -302,7 +334,7 @@ def measure(cfg_name, args, steps, warmup, rank, world, dev, other_order=True, b
                     'note': 'pinned host batch copied H2D on the step stream inside the timed region (PCIe-inclusive rate; not `value`)'}
     if graphed:
         step.close()
-    if world == 1 and other_order and not args.single_order and not graphed:   # the same step in the OTHER operation order, outside the timed region
+    if args.full and world == 1 and other_order and not args.single_order and not graphed:   # the same step in the OTHER operation order, outside the timed region
         set_op_order(net, args.reference_op_order)
         for _ in range(2):
             step(x, raw)
@@ -352,8 +384,8 @@ def measure(cfg_name, args, steps, warmup, rank, world, dev, other_order=True, b
                       'ranks': world, 'collective_backend': ((torch.distributed.get_backend() + (' (RCCL)' if torch.distributed.get_backend() == 'nccl' else '')) if world > 1 else None)},
            'roofline': roof}
     if rank == 0:
-        print('[bench] %s: %.1f ms/step (median %.1f), %.2f %s, engine %.1f TFLOP/s' % (cfg_name, res['ms_per_step'], med, res['value'], unit, achieved),
-              file=sys.stderr, flush=True)
+        print('[bench] %s: %.1f ms/step (median %.1f), %.2f %s%s' % (cfg_name, res['ms_per_step'], med, res['value'], unit,
+                                                                    ', engine %.1f TFLOP/s' % achieved if roof else ''), file=sys.stderr, flush=True)
     return res
 
 
@@ -365,7 +397,7 @@ def run_graph_replay(args, config=None, graph=True, batch=0):
     # first three blocks of ten cfg1 steps, then flat): HOST_WARMUP untimed steps there; graph replays and device-bound steps keep the short warm-up
     warm = max(3, args.warmup // 2) if graph else max(HOST_WARMUP, args.warmup)
     cmd = [sys.executable, os.path.abspath(__file__)] + (['--graph'] if graph else []) + ['--config', config or args.config, '--engine', args.engine, '--steps', str(max(10, args.steps // 2)),
-           '--warmup', str(warm), '--no-brats', '--no-cpu-baseline', '--single-order'] + (['--batch', str(batch)] if batch else [])
+           '--warmup', str(warm), '--full', '--no-brats', '--no-cpu-baseline', '--single-order'] + (['--batch', str(batch)] if batch else [])
     if args.reference_op_order:
         cmd.append('--reference-op-order')
     try:
@@ -402,7 +434,7 @@ def _short_roofline(roof, n_shapes=6):
     return out
 
 
-def compact_line(res):
+def compact_line(res, full_file='bench_shapes.json'):
     """The ONE JSON line rank 0 prints: headline fields, `config`, the scalars of `roofline`, `cpu_baseline` (value + medians), the BraTS / polyp blocks as
     value / ms_per_step / roofline.frac, and <= 6 attention GEMM rows.  Everything else (the per-shape tables, notes, per-step lists) goes to
     bench_shapes.json beside this file.  tests/test_bench_line.py holds the size bound."""
@@ -439,7 +471,8 @@ def compact_line(res):
                 if (r.get('config') or {}).get('overlap'):
                     b['overlap'] = r['config']['overlap']
                 line[blk][k] = b
-    line['full'] = 'bench_shapes.json'
+    if full_file:
+        line['full'] = full_file
     s = json.dumps(line, separators=(',', ':'))
     if len(s) > LINE_LIMIT:                 # never let a long note cost the record: drop the optional parts in order until the line fits
         for path in (('roofline', 'attention_gemms'), ('cpu_baseline', 'sample'), ('brats',), ('polyp',)):
@@ -486,6 +519,11 @@ def main():
     ap.add_argument('--single-order', action='store_true', help='skip the comparison run in the other operation order (profiling runs)')
     ap.add_argument('--reference-op-order', action='store_true',
                     help="time the reference's operation order (no linear-chain re-association, DESIGN.md section 5b) as the main number")
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beyond the headline: roofline, BraTS / polyp blocks, the other operation order, the H2D-inclusive rate, '
+                         'hipGraph replays, CPU baseline; writes bench_shapes.json')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the loss and model state of the last timed step of the main measurement to DIR/<name>.npy (float32, < 64 MB)')
     args = ap.parse_args()
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline(args.cpu_baseline_only, args.threads)))
@@ -508,8 +546,12 @@ def main():
     for kv in filter(None, os.environ.get('SEGX_TUNE', '').split(',')):       # e.g. SEGX_TUNE=2:1 (bisecting knobs, see segx_tune)
         k, v = kv.split(':'); L.c.segx_tune(int(k), int(v))
 
-    res = measure(args.config, args, args.steps, args.warmup, rank, world, dev, batch=args.batch or None)
+    res = measure(args.config, args, args.steps, args.warmup, rank, world, dev, batch=args.batch or None, dump_dir=args.dump_outputs)
     res = dict(res, higher_is_better=True, scaling='weak', vs_baseline=None, dtype='f32', data='synthetic')
+    if not args.full:                                  # a plain run: the headline alone
+        if rank == 0:
+            print(compact_line(res, full_file=None), flush=True)
+        return
     if not args.no_brats and args.config == 'cfg2':
         k2, w2 = max(10, args.steps // 2), max(3, args.warmup // 2)
         brats = {}

@@ -86,3 +86,39 @@ def test_every_committed_full_result_of_round_4_fits(name):
     if not os.path.exists(p):
         pytest.skip(name)
     assert len(bench.compact_line(json.load(open(p)))) < bench.LINE_LIMIT
+
+
+def test_plain_line_names_no_full_result_file():
+    res = {'metric': 'm', 'value': 1.0, 'unit': 'images/s', 'n_gpus': 1, 'steps': 3, 'warmup': 1, 'ms_per_step': 2.0, 'config': {'workload': 'w'}, 'roofline': None}
+    line = json.loads(bench.compact_line(res, full_file=None))
+    assert 'full' not in line and line['ms_per_step'] == 2.0 and line['steps'] == 3
+
+
+def test_dumped_outputs_stay_under_the_limit_and_sample_the_same_elements(tmp_path):
+    """--dump-outputs: loss + every floating-point state tensor as float32 .npy; a state larger than the limit is cut to a seeded sample that is the
+    same in every run (the files of two dumps are equal), and the files together stay under the limit."""
+    import numpy as np
+    import torch
+    torch.manual_seed(0)
+    net = torch.nn.Sequential(torch.nn.Linear(300, 200), torch.nn.BatchNorm1d(200), torch.nn.Linear(200, 7))
+    loss = torch.tensor(0.25, dtype=torch.float64)
+    whole = tmp_path / 'whole'
+    bench.dump_outputs(str(whole), loss, net)
+    sd = {k: v for k, v in net.state_dict().items() if v.is_floating_point()}
+    assert sorted(os.listdir(whole)) == sorted(['loss.npy'] + ['state.%s.npy' % k for k in sd])
+    assert np.load(whole / 'loss.npy').dtype == np.float32 and float(np.load(whole / 'loss.npy')[0]) == 0.25
+    for k, v in sd.items():
+        np.testing.assert_array_equal(np.load(whole / ('state.%s.npy' % k)), v.reshape(-1).numpy())
+    limit = 40000                                                # bytes: far below the 62 000 elements of this state
+    runs = [tmp_path / 'a', tmp_path / 'b']
+    for d in runs:
+        bench.dump_outputs(str(d), loss, net, limit=limit)
+    files = sorted(os.listdir(runs[0]))
+    assert files == sorted(os.listdir(runs[1])) == sorted(os.listdir(whole))
+    assert sum(os.path.getsize(runs[0] / f) for f in files) <= limit
+    for f in files:
+        a, b = np.load(runs[0] / f), np.load(runs[1] / f)
+        assert a.dtype == np.float32 and a.size >= 1 and np.array_equal(a, b)
+        full = np.load(whole / f)
+        assert a.size <= full.size and np.isin(a, full).all()   # a sample of the tensor's own elements
+    assert np.load(runs[0] / 'state.0.weight.npy').size < 300 * 200

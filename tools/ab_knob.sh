@@ -4,5 +4,5 @@ CFG=${1:-cfg4}; A=${2:-16:0}; B=${3:-16:1}; STEPS=${4:-15}
 cd ${GRAFT_REPO_ROOT:-$(pwd)}
 for R in 1 2; do for KV in $A $B; do
   echo -n "$CFG SEGX_TUNE=$KV: "
-  SEGX_TUNE=$KV python bench.py --config $CFG --steps $STEPS --warmup 5 --no-brats --no-cpu-baseline --single-order 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['ms_per_step_median'], d['roofline']['achieved'])"
+  SEGX_TUNE=$KV python bench.py --full --config $CFG --steps $STEPS --warmup 5 --no-brats --no-cpu-baseline --single-order 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['ms_per_step_median'], d['roofline']['achieved'])"
 done; done

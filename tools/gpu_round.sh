@@ -15,10 +15,10 @@ if [ "$MODE" = full ] || [ "$MODE" = quick ]; then
 fi
 if [ "$MODE" != micro ]; then
   # the driver's command (main cfg2 + brats cfg4/cfg5 blocks + cpu baseline), bf16x6 engine (default)
-  SEGX_BENCH_VERBOSE=2 timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default_shapes.txt; cut -c1-300 $OUT/bench_default.json
+  SEGX_BENCH_VERBOSE=2 timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default_shapes.txt; cut -c1-300 $OUT/bench_default.json
   # the fp32-MFMA engine on the same workloads (comparison; no cpu baseline)
   for CFG in cfg2 cfg4; do
-    SEGX_BENCH_VERBOSE=2 timeout 600 python bench.py --config $CFG --engine f32 --steps 12 --warmup 4 --no-brats --no-cpu-baseline --single-order > $OUT/bench_${CFG}_f32.json 2> $OUT/bench_${CFG}_f32_shapes.txt
+    SEGX_BENCH_VERBOSE=2 timeout 600 python bench.py --full --config $CFG --engine f32 --steps 12 --warmup 4 --no-brats --no-cpu-baseline --single-order > $OUT/bench_${CFG}_f32.json 2> $OUT/bench_${CFG}_f32_shapes.txt
     cut -c1-200 $OUT/bench_${CFG}_f32.json
   done
 fi

@@ -13,7 +13,7 @@ if [ "$MODE" = tests ]; then
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$?" >> $OUT/smoke.log; tail -2 $OUT/smoke.log
 fi
 if [ $# -gt 3 ]; then shift 3; for CMD in "$@"; do echo "== $CMD" >> $OUT/extra.log; timeout 600 bash -c "$CMD" >> $OUT/extra.log 2>&1; done; tail -5 $OUT/extra.log; fi
-SEGX_BENCH_VERBOSE=2 timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default_shapes.txt; wc -c $OUT/bench_default.json; cut -c1-400 $OUT/bench_default.json
+SEGX_BENCH_VERBOSE=2 timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default_shapes.txt; wc -c $OUT/bench_default.json; cut -c1-400 $OUT/bench_default.json
 cp bench_shapes.json $OUT/bench_shapes.json 2>/dev/null
 cd /tmp && export TMPDIR=/tmp
 for CFG in cfg2 cfg4 cfg5; do
