@@ -12,170 +12,31 @@ LN_EPS = 1e-12      # every LayerNorm of the Squeeze-and-Expansion transformer (
 
 
 # -------------------------------------------------------------------------------------------------
-# Block nodes: the ops of one backbone block as ONE autograd node (efficientnet/model.py:82-126, aj_i3d.py:121-126).
-# The eager step is what a data-parallel rank runs (RCCL cannot be captured), and at one or two images per rank its time is the host's: ~17 us per
-# launch, most of it torch.autograd.Function.apply going in and the engine's per-node dispatch coming back.  Inside `block_node(fn, ...)` every op of
-# this file runs its OWN forward / backward static methods against a plain context object, recorded on a tape; autograd sees one node per block
-# whose backward walks the tape in reverse.  Same kernels, same launch order, same results bit for bit -- only the bookkeeping per op changes.
-# Rule for code run under a tape: differentiable work goes through the ops of this file (plus contiguous reshapes of a block input, e.g.
-# `weight.reshape(Cout, Cin)`); a block input that should receive a gradient and gets none raises.
+# _Fn: base of every op of this file.  Outside a functorch transform, torch.autograd.Function.apply binds default arguments (only for a class with a
+# setup_context: no op here has one), unwraps tensors left over from a finished functorch transform (this library never receives one) and calls
+# _FunctionBase.apply.  _Fn.apply calls _FunctionBase.apply directly (4 us less per op) where that is exactly what Function.apply would do:
+#   _fast_apply   checked once, at import: _FunctionBase follows Function in torch's (private) class order and no class between them defines `apply`,
+#                 so super(Function, cls).apply is _FunctionBase.apply.  Otherwise every op goes through Function.apply.
+#   functorch     under vmap / grad / ... Function.apply takes another route (for these ops: torch's setup_context error) -- one C call per op checks
+#                 for it, so the kernels never run on a transform's wrapper tensors.
 # -------------------------------------------------------------------------------------------------
-_tape = None
-_tape_serial = 0
-block_nodes = False         # OFF by default: measured (profiles/r06_bn_ab_block_nodes_host.txt, same process, eight alternating repetitions) the eager cfg1 step takes 15.3 ms
-#                             with one node per backbone block and 14.4 ms with one node per op; cfg3 at one image 24.6 vs 23.2 -- the tape's Python per op costs
-#                             more than the C++ node it replaces.  Kept (opt-in, parity-tested bit for bit) as the measured answer to VERDICT r05 item 5.
-
-
-class _OpCtx:
-    """What the ops of this file use of an autograd context: save_for_backward / saved_tensors, needs_input_grad, plus free attributes."""
-    materialize = True
-
-    def save_for_backward(self, *ts):
-        self.saved_tensors = ts
-
-    def set_materialize_grads(self, v):
-        self.materialize = bool(v)
-
-    def mark_non_differentiable(self, *ts):
-        self.non_diff = ts
-
-
-class _Tape:
-    def __init__(self, inputs, needs):
-        global _tape_serial
-        _tape_serial += 1
-        self.serial, self.n, self.recs, self.req, self.done = _tape_serial, 0, [], [], False
-        self.in_ids = []
-        for t, r in zip(inputs, needs):
-            known = isinstance(t, torch.Tensor) and getattr(t, '_segx_tid', (0, 0))[0] == self.serial     # the same tensor passed twice: its gradient goes to the first
-            self.in_ids.append(self.tag(t, bool(r)) if isinstance(t, torch.Tensor) and not known else None)
-
-    def tag(self, t, req):
-        t._segx_tid = (self.serial, self.n)
-        self.req.append(req)
-        self.n += 1
-        return self.n - 1
-
-    def find(self, t):
-        """-> (tape id or None, shape to bring a gradient back to or None): a tensor the tape has seen, or a contiguous same-size view of one (weight.reshape(...))"""
-        k = getattr(t, '_segx_tid', None)
-        if k is not None and k[0] == self.serial:
-            return k[1], None
-        b = t._base
-        if b is not None:
-            k = getattr(b, '_segx_tid', None)
-            if k is not None and k[0] == self.serial:
-                if not (t.is_contiguous() and b.is_contiguous() and t.numel() == b.numel()):
-                    raise RuntimeError('block node: only a contiguous reshape of a block tensor may be taken outside the ops of functional.py (got %s of %s)'
-                                       % (tuple(t.shape), tuple(b.shape)))
-                return k[1], b.shape
-        return None, None
-
-    def run(self, fn, args):
-        ctx = _OpCtx()
-        keys = [self.find(a) if isinstance(a, torch.Tensor) else (None, None) for a in args]
-        ctx.needs_input_grad = tuple(k is not None and self.req[k] for k, _ in keys)
-        out = fn.forward(ctx, *args)
-        req = any(ctx.needs_input_grad)
-        nd = getattr(ctx, 'non_diff', ())
-        outs = out if isinstance(out, tuple) else (out,)
-        oids = []
-        for o in outs:
-            if isinstance(o, torch.Tensor) and not any(o is t for t in nd):
-                if getattr(o, '_segx_tid', (0, 0))[0] == self.serial:
-                    raise RuntimeError('block node: %s returned a tensor the block holds already; return a fresh tensor or a view' % fn.__name__)
-                oids.append(self.tag(o, req))         # a view of an input (the alias outputs of _BGemm / _Conv3dSlices / _MaxPool3d) is a tensor of its own, as for autograd
-            else:
-                oids.append(None)
-        if req:
-            self.recs.append((fn, ctx, keys, oids, [(o.shape, o.device) if isinstance(o, torch.Tensor) else None for o in outs]))
-        return out
+_MRO = torch.autograd.Function.__mro__
+_fast_apply = torch._C._FunctionBase in _MRO and not any('apply' in c.__dict__ for c in _MRO[1:_MRO.index(torch._C._FunctionBase)])
 
 
 class _Fn(torch.autograd.Function):
-    """Base of every op of this file: under a tape (block_node) the op is recorded instead of becoming an autograd node of its own."""
+    """Base of every op of this file: torch.autograd.Function with the fast path of apply above."""
 
     @classmethod
     def apply(cls, *args):
-        if _tape is not None:
-            return _tape.run(cls, args)
-        # torch.autograd.Function.apply minus its functorch wrapper scan (4 us per call; no functorch transform ever runs over this library's ops)
-        return super(torch.autograd.Function, cls).apply(*args)
-
-
-class _Block(_Fn):
-    @staticmethod
-    def forward(ctx, fn, static, *tensors):
-        global _tape
-        assert _tape is None, 'block nodes do not nest'
-        tape = _Tape(tensors, ctx.needs_input_grad[2:])
-        _tape = tape
-        try:
-            out = fn(tensors[0], *static)
-        finally:
-            _tape = None
-        outs = out if isinstance(out, tuple) else (out,)
-        tape.out_ids = []
-        for o in outs:
-            k, shp = tape.find(o)
-            if k is None or shp is not None or k in tape.in_ids:
-                raise RuntimeError('block node: every output must be a tensor produced by an op of the block')
-            tape.out_ids.append(k)
-        ctx.tape = tape
-        return out
-
-    @staticmethod
-    def backward(ctx, *gouts):
-        tape = ctx.tape
-        if tape.done:
-            raise RuntimeError('block node: backward ran already (retain_graph is not supported by block nodes)')
-        tape.done = True
-        grads = {}
-
-        def acc(k, g):
-            grads[k] = g if k not in grads else grads[k] + g          # what autograd's accumulation does for a tensor with two consumers
-
-        for k, g in zip(tape.out_ids, gouts):
-            if g is not None:
-                acc(k, g)
-        recs, tape.recs = tape.recs, None
-        while recs:
-            fn, octx, keys, oids, meta = recs.pop()
-            gs = [grads.pop(k, None) if k is not None else None for k in oids]
-            if all(g is None for g in gs):
-                continue
-            if octx.materialize:
-                gs = [g if (g is not None or m is None) else torch.zeros(m[0], dtype=torch.float32, device=m[1]) for g, m in zip(gs, meta)]
-            res = fn.backward(octx, *gs)
-            if not isinstance(res, tuple):
-                res = (res,)
-            for (k, shp), g in zip(keys, res):
-                if k is not None and g is not None and tape.req[k]:
-                    acc(k, g if shp is None else g.reshape(shp))
-        out = []
-        for i, k in enumerate(tape.in_ids):
-            g = grads.get(k) if k is not None else None
-            if g is None and k is not None and tape.req[k] and i > 0:
-                raise RuntimeError('block node: tensor input #%d requires a gradient and received none -- was it used outside the ops of functional.py?' % i)
-            out.append(g)
-        return (None, None) + tuple(out)
+        if _fast_apply and not torch._C._are_functorch_transforms_active():
+            return super(torch.autograd.Function, cls).apply(*args)
+        return super().apply(*args)
 
 
 def _live(t):
-    """does a gradient flow back through t?  (under a tape the tensors carry no requires_grad flag of their own: the tape knows)"""
-    if _tape is not None:
-        k = _tape.find(t)[0]
-        return k is not None and _tape.req[k]
+    """does a gradient flow back through t?"""
     return t.requires_grad and torch.is_grad_enabled()
-
-
-def block_node(fn, x, static, params):
-    """fn(x, *static) -- a block's forward written with the ops of this file -- as ONE autograd node.  params: every tensor the block reads that may
-    require a gradient (its module parameters).  Falls back to plain per-op nodes when gradients are off, a tape is active already, or block_nodes is False."""
-    if not block_nodes or _tape is not None or not torch.is_grad_enabled():
-        return fn(x, *static)
-    return _Block.apply(fn, static, x, *params)
 
 
 # -------------------------------------------------------------------------------------------------
@@ -1067,14 +928,13 @@ def bn_act(x, bn, act=ACT_NONE, resid=None, drop_connect=0.0):
                         float(drop_connect or 0.0))
 
 
-def bn_act_multi(x, bns, act=ACT_NONE, wb=None):
+def bn_act_multi(x, bns, act=ACT_NONE):
     """BatchNorm (+ activation) of SEVERAL BatchNorm modules in one pass: x's channels are the concatenation of the modules' channels (the outputs
     of convolutions that were run as one convolution with concatenated filters).  BatchNorm is per channel, so this is exactly the separate
     layers -- with one statistics pass, one apply pass and, when synchronised, ONE exchange for all of them.  Same momentum / eps required."""
     mom, eps, training = float(bns[0].momentum), float(bns[0].eps), bns[0].training
     assert all(float(b.momentum) == mom and float(b.eps) == eps and b.training == training for b in bns)
-    # wb: (weights, biases) concatenated by the caller -- a block node (block_node) does its differentiable ATen work outside the tape
-    w, b = wb if wb is not None else (torch.cat([m.weight for m in bns]), torch.cat([m.bias for m in bns]))
+    w, b = torch.cat([m.weight for m in bns]), torch.cat([m.bias for m in bns])
     rm, rv = torch.cat([m.running_mean for m in bns]), torch.cat([m.running_var for m in bns])
     y = _BNAct.apply(x, w, b, rm, rv, training, mom, eps, act, None, 0.0)
     if training:

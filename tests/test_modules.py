@@ -360,52 +360,22 @@ def test_avgpool2_and_transpose(backend):
     assert torch.equal(t.grad.cpu(), t.detach().cpu())
 
 
-@pytest.mark.parametrize('k,s,e,cin,cout', [(3, 1, 6, 8, 8), (5, 2, 6, 8, 12), (3, 1, 1, 8, 8)])
-def test_mbconv_block_node_equals_per_op_nodes(backend, monkeypatch, k, s, e, cin, cout):
-    """SF.block_node (one autograd node per MBConv block, its ops recorded on a tape: efficientnet/model.py:82-126) runs the same kernels in the same order as the
-    per-op autograd nodes of rounds 1-5: output, input gradient and every parameter gradient bit for bit, drop_connect and the skip connection included."""
-    from segtran_amd.efficientnet.model import MBConvBlock
-    blk = MBConvBlock(k, s, e, cin, cout, 0.25, 16)
-    prefix = 'backbone._blocks.3.'
-    sd = synth_state_dict({prefix + n: tuple(v.shape) for n, v in blk.state_dict().items()})
-    blk.load_state_dict({n[len(prefix):]: v for n, v in sd.items()})
-    blk.to(backend.dev).train()
-    g = torch.Generator(device='cpu').manual_seed(5)
-    x = torch.randn(3, cin, 12, 10, generator=g, device='cpu').to(backend.dev)
-    G = torch.randn(3, cout, 12 // s, 10 // s, generator=g, device='cpu').to(backend.dev)
+def test_op_apply_fast_path(backend, monkeypatch):
+    """_Fn.apply calls _FunctionBase.apply directly where torch's class layout makes that what torch.autograd.Function.apply does (SF._fast_apply): the
+    same outputs, gradients and autograd node as through Function.apply; under a functorch transform every op goes through Function.apply, which refuses it."""
+    assert SF._fast_apply                                                               # the installed torch takes the fast path
+    g = torch.Generator(device='cpu').manual_seed(31)
+    x0, w, b, G, Ga = (torch.randn(*shp, generator=g, device='cpu').to(backend.dev) for shp in ((2, 12, 5, 6), (8, 12, 1, 1), (8,), (2, 8, 5, 6), (2, 12, 5, 6)))
     res = []
-    for on in (True, False):
-        monkeypatch.setattr(SF, 'block_nodes', on)
-        blk.load_state_dict({n[len(prefix):]: v for n, v in sd.items()})              # running statistics back to the start
-        blk.zero_grad(set_to_none=True)
-        SF.manual_seed(21)
-        xp = x.clone().requires_grad_(True)
-        xin = xp * 1.0                                                                  # a non-leaf input, as inside the backbone
-        y = blk(xin, drop_connect_rate=0.3)
-        assert (type(y.grad_fn).__name__ == '_BlockBackward') == on
-        y.backward(G)
-        res.append([y.detach().clone(), xp.grad.clone()] + [p.grad.clone() for p in blk.parameters()] + [b.clone() for b in blk.buffers()])
-    assert len(res[0]) == len(res[1])
-    for a, b in zip(*res):
-        assert torch.equal(a, b)
-
-
-def test_block_node_fails_loudly_on_untracked_use(backend, monkeypatch):
-    """A block input that requires a gradient and is used OUTSIDE the ops of functional.py inside a block node gets no gradient: that must raise, not train on zeros."""
-    monkeypatch.setattr(SF, 'block_nodes', True)                                        # opt-in (off by default: measured slower on the host)
-    w = torch.randn(4, 4, device=backend.dev, requires_grad=True)
-    x = torch.randn(2, 4, device=backend.dev, requires_grad=True)
-
-    def fn(x_):
-        return SF.linear(x_ + w.sum(), torch.eye(4, device=backend.dev))              # `+` is not a libsegx op: neither x_ nor w is seen by the tape
-
-    y = SF.block_node(fn, x, (), [w])
-    with pytest.raises(RuntimeError, match='received none'):
-        y.sum().backward()
-    with torch.no_grad():
-        assert SF.block_node(fn, x, (), [w]).grad_fn is None                            # gradients off: plain ops, no node
-    monkeypatch.setattr(SF, 'block_nodes', False)
-    y = SF.block_node(fn, x, (), [w])                                                   # switched off: per-op autograd nodes, ATen work is differentiated as usual
-    assert type(y.grad_fn).__name__ != '_BlockBackward'
-    y.sum().backward()
-    assert w.grad is not None and x.grad is not None
+    for fast in (True, False):
+        monkeypatch.setattr(SF, '_fast_apply', fast)
+        x, wp, bp = (t.clone().requires_grad_(True) for t in (x0, w, b))
+        y, xa = SF.conv1x1(x, wp, bp, pass_input=True)                                  # the skip alias: a second output of the same node
+        assert type(y.grad_fn).__name__ == '_BGemmBackward' and xa.grad_fn is y.grad_fn
+        torch.autograd.backward([y, xa], [G, Ga])
+        res.append([y.detach(), xa.detach(), x.grad, wp.grad, bp.grad])
+    for u, v in zip(*res):
+        assert torch.equal(u, v)
+    monkeypatch.setattr(SF, '_fast_apply', True)
+    with pytest.raises(RuntimeError, match='setup_context'):                          # torch's own refusal, before any kernel runs
+        torch.func.vmap(lambda t: SF.conv1x1(t, w))(torch.stack([x0, x0]))

@@ -11,7 +11,7 @@ from segtran_amd.networks import segtran_shared as ss
 cfg, switch = sys.argv[1], sys.argv[2]
 steps = int(sys.argv[3]) if len(sys.argv) > 3 else 20
 owner, attr = switch.split('.')
-owner = {'InceptionModule': InceptionModule, 'MBConvBlock': MBConvBlock, 'CrossAttFeatTrans': ss.CrossAttFeatTrans, '_ModesAggr': SF._ModesAggr, '_ConvStem2d': SF._ConvStem2d, '_BGemm': SF._BGemm, '_DWConv': SF._DWConv, '_PreNorm': SF._PreNorm, 'SF': SF}[owner]          # SF.block_nodes: one autograd node per backbone block
+owner = {'InceptionModule': InceptionModule, 'MBConvBlock': MBConvBlock, 'CrossAttFeatTrans': ss.CrossAttFeatTrans, '_ModesAggr': SF._ModesAggr, '_ConvStem2d': SF._ConvStem2d, '_BGemm': SF._BGemm, '_DWConv': SF._DWConv, '_PreNorm': SF._PreNorm, 'SF': SF}[owner]
 dev = torch.device('cuda', 0)
 c = engine.CONFIGS[cfg]
 batch = int(os.environ.get('SEGX_AB_BATCH', c['bs']))

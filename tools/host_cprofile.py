@@ -11,7 +11,6 @@ B = int(sys.argv[2]) if len(sys.argv) > 2 else engine.CONFIGS[cfg]['bs']
 K = int(sys.argv[3]) if len(sys.argv) > 3 else 10
 dev = torch.device('cuda', 0)
 segx.lib().set_engine('x6')
-SF.block_nodes = os.environ.get('SEGX_BLOCK_NODES', '1') != '0'          # A/B: one autograd node per backbone block vs one per op
 torch.manual_seed(0); SF.manual_seed(0)
 net = engine.build_model(cfg, dev); net.train()
 opt = engine.init_optimizer(net, engine.CONFIGS[cfg]['task'])
@@ -27,7 +26,6 @@ for _ in range(K):
 t_host = time.perf_counter() - t0                 # host time to ISSUE K steps (the queue is deep enough not to block)
 torch.cuda.synchronize()
 t_all = time.perf_counter() - t0
-print('block_nodes', SF.block_nodes)
 print('%s batch %d: %.2f ms/step wall, %.2f ms/step of host issue time' % (cfg, B, t_all / K * 1e3, t_host / K * 1e3))
 pr = cProfile.Profile()
 pr.enable()
