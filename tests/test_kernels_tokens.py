@@ -316,10 +316,16 @@ def test_gemm_gelu_dropout_mask_equals_gelu_bwd_mask(backend, engine, Fd, offset
     assert 0.2 < (k == 0).float().mean().item() < 0.4
 
 
-@pytest.mark.parametrize('shape,R', [((5, 6), 2), ((3, 4, 2), 1), ((4, 4), 7)])
+@pytest.mark.parametrize('shape,R', [((5, 6), 2), ((3, 4, 2), 1), ((4, 4), 7),
+                                     ((4, 5), 6), ((2, 3, 2), 3),          # R >= every grid extent: every pair inside the radius, unused table entries
+                                     ((5, 6), 0), ((3, 4, 2), 0),          # R = 0: a one-entry table, only the diagonal
+                                     ((1, 9), 2),                          # a 1 x W grid (dh is always 0)
+                                     ((1, 4, 5), 2),                       # 3-D with D = 1 (dd is always 0, the middle slab of the table)
+                                     ((3, 5, 2), 2)])                      # non-square 3-D, every extent different
 @pytest.mark.parametrize('clamped', [False, True])
 def test_sliding_pos_bias_add(backend, shape, R, clamped):
-    """K14: scores + w * bias[N,N] computed on the fly from the (2R+1)^d table, vs the oracle's materialised lookup."""
+    """K14: scores + w * bias[N,N] computed on the fly from the (2R+1)^d table, vs the oracle's materialised lookup.  Six score matrices
+    (nmat = 6), so dtable sums over more than one matrix."""
     from oracle import segtran_oracle as O
     from segtran_amd import functional as SF
     N = 1
