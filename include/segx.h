@@ -369,30 +369,44 @@ int segx_dropout(const float* x, float* y, int64_t n, float p, uint64_t seed, ui
 int segx_set_rng_base(const uint64_t* base);
 int segx_rng_advance(uint64_t* base, uint64_t span, void* stream);
 
-/* tuning / bisecting knobs (results are identical for every setting): knob 1 = interp_linear_fwd kernel (0 auto, 1 scalar, 2 float4 rows);
- * knob 4 = tile engine of segx_gemm_f32 and the
- * implicit-GEMM convolutions (SEGX_ENGINE_*: same results to fp32 rounding, see above); returns the previous value of knob 4;
- * knob 7: weight gradients of the packed 3-D convolutions on the bf16x6 engine -- 0 (default): where the loader reads whole rows (OW % 8 == 0, or OW % 4 == 0
- * at unit W stride) and the tile is not the strided 64-row case; 1: every one (also the per-position gather); 2: every whole-row case (also the strided 64-row tile);
- * knob 8 = outputs per strip of the depthwise weight gradient (default 8192; >= 256);
- * knob 6 = schedule variant of the bf16x6 kernels with IDENTICAL results (0 = product; 1 = raised wave priority in the MFMA phase / of the consumer
- * waves; 6 = split-early schedule, 7 = product schedule at two waves per SIMD); the ablation variants 2..5, whose results are NOT the GEMM, exist only
- * in -DSEGX_BENCH builds (tools/build_variant.py) and are rejected by the product library; knob 9 = workgroups of a persistent launch of the wave-specialised bf16x6 kernels (default 256 = one per CU; a multiple of 8);
- * knob 5 = number of launches that ran on the bf16x6 engine since the last query (resets the count);
- * knob 3 = form of training BatchNorm when the library computes the statistics itself (segx_bn_act_fwd2 with nparts == 0, segx_bn_act_bwd2): 0 (default) =
- * channel-resident where a channel fits one workgroup, else a TEAM of workgroups per channel (one launch, the slabs stay in registers across a team barrier),
- * else two launches; 1 = never teams; 2 = teams for every shape with S % 4 == 0 (tests).  Same results to fp32 summation order;
- * knob 12 = poll bound of a team exchange (default 2^20 polls, ~1 s; 32 .. 2^24); knob 13 = FAULT INJECTION for the tests of the team form's failure
- * path: the last `value` workgroups of every team launch are not launched, so their team mates time out (0 = off, the default);
- * knob 14 = slab-in-LDS form of the stride-1 3 x 3 x 3 'same' max-pools: 0 (default) where the four-cells-per-thread form does not apply (row length not a
- * multiple of 4), 1 wherever a slab fits the LDS, 2 never; knob 15 = the same pools with rows of a multiple of 4 floats: 1 (default) a thread keeps its four
- * cells for up to eight slices and slides along the depth (a third of the row loads), 0 = one slice per thread;
- * knob 19 = order in which the tiles of a GEMM are walked inside an XCD's run: 1 (default) M fastest where the A operand of a member fits the XCD's L2 (<= 2 MiB) and B is
- * the big operand -- pointwise convolutions over 10^5 positions: B crosses the fabric once instead of once per row of tiles --, 0 = N fastest always (rounds 1-5).
- * Identical results for every setting. */
+/* Tuning / bisecting knobs: process-wide defaults; results are identical for every setting.  The ids are ABI (SEGX_TUNE=id:value of bench.py uses the numbers); ids 10 and
+ * 11 are retired and refused like any unknown id.  segx_tune returns 0, or -1 for an unknown knob or a setting outside the accepted ones (nothing is changed then). */
+enum {
+    SEGX_KNOB_INTERP_VARIANT = 1,       /* segx_interp_linear_fwd kernel: 0 (default) auto, 1 scalar, 2 float4 rows */
+    SEGX_KNOB_CONV_SMALL_POLICY = 2,    /* which output-channel counts the implicit-GEMM convolutions treat as small: 0 (default) Cout % 128 in 1..64, 1 Cout <= 64 */
+    SEGX_KNOB_BN_PATH = 3,              /* form of training BatchNorm when the library computes the statistics itself (segx_bn_act_fwd2 with nparts == 0, segx_bn_act_bwd2):
+                                         * 0 (default) = channel-resident where a channel fits one workgroup, else a TEAM of workgroups per channel (one launch, the slabs stay in
+                                         * registers across a team barrier), else two launches; 1 = never teams; 2 = teams for every shape with S % 4 == 0 (tests).  Same results
+                                         * to fp32 summation order */
+    SEGX_KNOB_ENGINE = 4,               /* tile engine of segx_gemm_f32 and the implicit-GEMM convolutions (SEGX_ENGINE_*, default SEGX_ENGINE_F32: same results to fp32 rounding,
+                                         * see above); segx_tune returns the PREVIOUS engine */
+    SEGX_KNOB_X6_LAUNCHES = 5,          /* no setting but a counter: segx_tune returns the number of launches that ran on the bf16x6 engine since the last query and resets it
+                                         * (the value is ignored); not readable through segx_tune_get */
+    SEGX_KNOB_X6_VARIANT = 6,           /* schedule variant of the bf16x6 kernels with IDENTICAL results: 0 (default) = product; 1 = raised wave priority in the MFMA phase / of
+                                         * the consumer waves; 6 = split-early schedule; 7 = product schedule at two waves per SIMD.  The ablation variants 2..5, whose results are
+                                         * NOT the GEMM, exist only in -DSEGX_BENCH builds (tools/build_variant.py) and are rejected by the product library */
+    SEGX_KNOB_CONV_X6_WGRAD_ALL = 7,    /* weight gradients of the packed 3-D convolutions on the bf16x6 engine -- 0 (default): where the loader reads whole rows (OW % 8 == 0, or
+                                         * OW % 4 == 0 at unit W stride) and the tile is not the strided 64-row case; 1: every one (also the per-position gather); 2: every whole-row
+                                         * case (also the strided 64-row tile) */
+    SEGX_KNOB_DW_STRIP_OUTPUTS = 8,     /* outputs per strip of the depthwise weight gradient (default 8192; >= 256) */
+    SEGX_KNOB_WS_GRID = 9,              /* workgroups of a persistent launch of the wave-specialised bf16x6 kernels (default 256 = one per CU; 8 .. 4096, a multiple of 8) */
+    SEGX_KNOB_TEAM_SPIN = 12,           /* poll bound of a team exchange (default 2^20 polls, ~1 s; 32 .. 2^24) */
+    SEGX_KNOB_TEAM_DROP = 13,           /* FAULT INJECTION for the tests of the team form's failure path: the last `value` workgroups of every team launch are not launched, so
+                                         * their team mates time out (0 = off, the default; <= 4096) */
+    SEGX_KNOB_POOL_SLAB = 14,           /* slab-in-LDS form of the stride-1 3 x 3 x 3 'same' max-pools: 0 (default) where the four-cells-per-thread form does not apply (row length
+                                         * not a multiple of 4), 1 wherever a slab fits the LDS, 2 never */
+    SEGX_KNOB_POOL_DSLIDE = 15,         /* the same pools with rows of a multiple of 4 floats: 1 (default) a thread keeps its four cells for up to eight slices and slides along the
+                                         * depth (a third of the row loads), 0 = one slice per thread */
+    SEGX_KNOB_CONV_HALO = 16,           /* 3 x 3 x 3 stride-1 'same' convolutions on the LDS-resident-halo kernels where they apply (1, default); 0 = im2col kernels only */
+    SEGX_KNOB_CONV_HALO_MIN_TILES = 17, /* fewest 128-output spatial tiles (x batch) for which the halo kernels are used (default 256; 1 .. 2^24; below: split-K im2col) */
+    SEGX_KNOB_SKINNY_NT = 18,           /* batch-reduced skinny weight gradients on the streaming kernel (SEGX_TILE_SKINNY_NT; 1, default); 0 = the tile kernels' split-K slabs */
+    SEGX_KNOB_TILE_WALK = 19            /* order in which the tiles of a GEMM are walked inside an XCD's run: 1 (default) M fastest where the A operand of a member fits the XCD's
+                                         * L2 (<= 2 MiB) and B is the big operand -- pointwise convolutions over 10^5 positions: B crosses the fabric once instead of once per row of
+                                         * tiles --, 0 = N fastest always (rounds 1-5) */
+};
 int segx_tune(int knob, int value);
-/* r06: the value a knob holds now (knobs 1-4, 6-9, 12-19; -1 for an unknown knob and for the counter knob 5): a caller that changes a process-wide default for its own
- * lifetime (dist.GradReducer: knob 3) reads it first and puts it back instead of assuming the default */
+/* r06: the value a knob holds now (-1 for an unknown knob and for the counter SEGX_KNOB_X6_LAUNCHES): a caller that changes a process-wide default for its own
+ * lifetime (dist.GradReducer: SEGX_KNOB_BN_PATH) reads it first and puts it back instead of assuming the default */
 int segx_tune_get(int knob);
 /* r04: TWO adjacent outer axes of a linear resampling in one streaming pass over [outer, n1, n2, inner] (inner % 4 == 0: the contiguous extent, read
  * and written as float4; align_corners = False): the y and z axes of the 3-D feature pyramid's trilinear up-sampling (segtran3d.py:304,319,351,364,384)

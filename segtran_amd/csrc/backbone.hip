@@ -546,7 +546,7 @@ static int team_occupancy_ok(const void* kernel, const char* what) {
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, 256, 0) != hipSuccess) { (void)hipGetLastError(); n = 0; }
         seen[kernel] = n;
     }
-    return n >= 2 ? 0 : fail(-1, "%s: the team kernel fits %d workgroup(s) per compute unit, the team exchange needs 2 (segx_tune(3, 1) selects the two-launch form)", what, n);
+    return n >= 2 ? 0 : fail(-1, "%s: the team kernel fits %d workgroup(s) per compute unit, the team exchange needs 2 (segx_tune(SEGX_KNOB_BN_PATH = 3, 1) selects the two-launch form)", what, n);
 }
 static inline void team_fill(BnTeam& t) {
     const TeamHost& h = team_host();

@@ -104,7 +104,7 @@ __device__ __forceinline__ float wave_max(float v);
 __device__ __forceinline__ void team_store(float* p, float v) { SEGX_TEAM_STORE(p, v); }
 __device__ __forceinline__ float team_load(const float* p) { return SEGX_TEAM_LOAD(p); }
 constexpr int TEAM_SLOT = 8, TEAM_MBOX = 16;               // floats per slot (payload 0..2, tag 4..5) and per mailbox (one 64-byte line: payload 0..2, tag 4..5)
-constexpr unsigned TEAM_SPIN_LIMIT = 1u << 20;             // default of knob 12 (~1 s of polling: three orders of magnitude above the longest exchange measured)
+constexpr unsigned TEAM_SPIN_LIMIT = 1u << 20;             // default of knob 12, team_spin (~1 s of polling: three orders of magnitude above the longest exchange measured)
 // of ONE team: slots [members][TEAM_SLOT], mbox [members][TEAM_MBOX]; err = the process's error word (device address of pinned host memory), spin = poll bound
 struct TeamBufs { float* slots; float* mbox; unsigned tag_lo, tag_hi; unsigned* err; unsigned spin; };
 __device__ __forceinline__ void team_put_tag(float* line, unsigned lo, unsigned hi) {
@@ -273,24 +273,36 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
 // caller sets once (which tile engine eligible GEMMs / convolutions use, tuning knobs whose every setting gives the same results) and one
 // statistics counter.  All of it is std::atomic: entry points are called from the main thread AND autograd's backward thread, on any number
 // of streams.  A call never writes a knob; per-call choices (segx_gemm_desc.engine / .tile / .splitk) override the defaults.
+// THE knob table: every settable knob once, in id order -- X(id, field, default, lowest, highest accepted value).  The Knobs struct below and segx_tune /
+// segx_tune_get (tune.hip) are generated from it; include/segx.h names the ids (SEGX_KNOB_*) and describes them for callers.  Every knob accepts only the
+// settings the product suite exercises (tests/): an unknown value is an error, never a silent new code path.  What the table cannot say:
+//   knob 4  segx_tune returns the PREVIOUS engine instead of 0;
+//   knob 5  is no setting but the counter x6_launches: segx_tune(SEGX_KNOB_X6_LAUNCHES, any) reads and resets it, segx_tune_get answers -1;
+//   knob 6  the product build accepts {0, 1, 6, 7} of its range only: the ablations 2..5 need -DSEGX_BENCH (tools/build_variant.py);
+//   knob 9  must be a multiple of 8;
+//   ids 10 and 11 are retired: both calls answer -1 for them, like for any unknown id.
+#define SEGX_KNOB_TABLE(X)                                                                                                                                        \
+    X(1, interp_variant, 0, 0, 2)                    /* interp_linear_fwd kernel: 0 auto, 1 scalar, 2 float4 rows */                                              \
+    X(2, conv_small_policy, 0, 0, 1)                 /* output-channel counts the implicit-GEMM convolutions treat as small: 0 = Cout % 128 in 1..64, 1 = Cout <= 64 */         \
+    X(3, bn_path, 0, 0, 2)                           /* training BatchNorm: 0 = resident -> workgroup teams -> two launches; 1 = no teams; 2 = teams even where the resident form serves (tests) */ \
+    X(4, engine, SEGX_ENGINE_F32, SEGX_ENGINE_F32, SEGX_ENGINE_BF16X6) /* default tile engine */                                                                  \
+    X(6, x6_variant, 0, 0, 7)                        /* schedule variants of the bf16x6 kernels (0 product; ablations only in SEGX_BENCH builds) */              \
+    X(7, conv_x6_wgrad_all, 0, 0, 2)                 /* packed 3-D weight gradients on the bf16x6 engine: 0 whole-row loaders off the strided 64-row tile, 1 every one, 2 every whole-row case */ \
+    X(8, dw_strip_outputs, 8192, 256, 2147483647)    /* outputs per strip of the depthwise weight gradient */                                                     \
+    X(9, ws_grid, 256, 8, 4096)                      /* workgroups of a persistent (wave-specialised) launch */                                                   \
+    X(12, team_spin, (int)TEAM_SPIN_LIMIT, 32, 1 << 24) /* poll bound of a team exchange (tests shorten it) */                                                    \
+    X(13, team_drop, 0, 0, 4096)                     /* FAULT INJECTION (tests): the last n workgroups of a team launch are not launched -> their mates time out */ \
+    X(14, pool_slab, 0, 0, 2)                        /* slab-in-LDS form of the stride-1 3x3x3 pools: 0 where the 4-outputs-per-thread form does not apply, 1 wherever it fits, 2 never */ \
+    X(15, pool_dslide, 1, 0, 1)                      /* stride-1 3x3x3 pools with W % 4 == 0 slide along depth (1, default) or take the per-slice four-cell form (0) */ \
+    X(16, conv_halo, 1, 0, 1)                        /* 3 x 3 x 3 stride-1 'same' convolutions on the LDS-resident-halo kernels (conv3d_halo.hip) where they apply; 0 = im2col kernels only */ \
+    X(17, conv_halo_min_tiles, 256, 1, 1 << 24)      /* fewest 128-output spatial tiles (x batch) for which the halo kernels are used (below: split-K im2col) */   \
+    X(18, skinny_nt, 1, 0, 1)                        /* batch-reduced skinny weight gradients on the streaming kernel (gemm_skinny.hip); 0 = the tile kernels' split-K slabs */ \
+    X(19, tile_walk, 1, 0, 1)                        /* 1 = the GEMM kernels walk M fastest where the A operand fits an XCD's L2 and B is the big one (gemm_core.h tile_walk), 0 = N fastest always (rounds 1-5) */
 struct Knobs {
-    std::atomic<int> engine{SEGX_ENGINE_F32};       // knob 4: default tile engine
-    std::atomic<int> x6_variant{0};                 // knob 6: schedule variants of the bf16x6 kernels (0 product; ablations only in SEGX_BENCH builds)
+#define SEGX_KNOB_FIELD(id, field, def, lo, hi) std::atomic<int> field{def};
+    SEGX_KNOB_TABLE(SEGX_KNOB_FIELD)
+#undef SEGX_KNOB_FIELD
     std::atomic<int> x6_launches{0};                // knob 5: launches that ran on the bf16x6 engine since the last query
-    std::atomic<int> ws_grid{256};                  // knob 9: workgroups of a persistent (wave-specialised) launch
-    std::atomic<int> conv_x6_wgrad_all{0};          // knob 7
-    std::atomic<int> dw_strip_outputs{8192};        // knob 8
-    std::atomic<int> interp_variant{0};             // knob 1
-    std::atomic<int> conv_small_policy{0};          // knob 2
-    std::atomic<int> bn_path{0};                    // knob 3: 0 = resident -> workgroup teams -> two launches; 1 = no teams; 2 = teams even where the resident form serves (tests)
-    std::atomic<int> team_spin{(int)TEAM_SPIN_LIMIT}; // knob 12: poll bound of a team exchange (tests shorten it)
-    std::atomic<int> pool_slab{0};                  // knob 14: slab-in-LDS form of the stride-1 3x3x3 pools: 0 where the 4-outputs-per-thread form does not apply, 1 wherever it fits, 2 never
-    std::atomic<int> pool_dslide{1};                // knob 15: stride-1 3x3x3 pools with W % 4 == 0 slide along depth (1, default) or take the per-slice four-cell form (0)
-    std::atomic<int> conv_halo{1};                  // knob 16: 3 x 3 x 3 stride-1 'same' convolutions on the LDS-resident-halo kernels (conv3d_halo.hip) where they apply; 0 = im2col kernels only
-    std::atomic<int> conv_halo_min_tiles{256};      // knob 17: fewest 128-output spatial tiles (x batch) for which the halo kernels are used (below: split-K im2col)
-    std::atomic<int> skinny_nt{1};                  // knob 18: batch-reduced skinny weight gradients on the streaming kernel (gemm_skinny.hip); 0 = the tile kernels' split-K slabs
-    std::atomic<int> tile_walk{1};                  // knob 19: 1 = the GEMM kernels walk M fastest where the A operand fits an XCD's L2 and B is the big one (gemm_core.h tile_walk), 0 = N fastest always (rounds 1-5)
-    std::atomic<int> team_drop{0};                  // knob 13: FAULT INJECTION (tests): the last n workgroups of a team launch are not launched -> their mates time out
 };
 inline Knobs& knobs() { static Knobs k; return k; }
 inline int kget(const std::atomic<int>& a) { return a.load(std::memory_order_relaxed); }

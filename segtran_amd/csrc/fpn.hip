@@ -844,54 +844,6 @@ extern "C" int segx_rng_advance(uint64_t* base, uint64_t span, void* stream_) {
     hipLaunchKernelGGL(rng_advance_kernel, dim3(1), dim3(64), 0, stream, base, span);
     return check_launch("segx_rng_advance");
 }
-extern "C" int segx_tune(int knob, int value) {
-    segx::Knobs& k = segx::knobs();
-    // every knob accepts only the settings the product suite exercises (tests/): an unknown value is an error, never a silent new code path
-    if (knob == 1) { if (value < 0 || value > 2) return -1; k.interp_variant = value; return 0; }
-    if (knob == 2) { if (value != 0 && value != 1) return -1; k.conv_small_policy = value; return 0; }
-    if (knob == 3) { if (value < 0 || value > 2) return -1; k.bn_path = value; return 0; }     // training BatchNorm: 0 resident -> teams -> two launches, 1 no teams, 2 teams everywhere
-    if (knob == 4) { if (value != SEGX_ENGINE_F32 && value != SEGX_ENGINE_BF16X6) return -1; return k.engine.exchange(value); }
-    if (knob == 8) { if (value < 256) return -1; k.dw_strip_outputs = value; return 0; }
-    if (knob == 7) { if (value < 0 || value > 2) return -1; k.conv_x6_wgrad_all = value; return 0; }
-#ifdef SEGX_BENCH
-    if (knob == 6) { if (value < 0 || value > 7) return -1; k.x6_variant = value; return 0; }      // 2..5: ablations whose results are NOT the GEMM
-#else
-    if (knob == 6) { if (value != 0 && value != 1 && value != 6 && value != 7) return -1; k.x6_variant = value; return 0; }
-#endif
-    if (knob == 9) { if (value < 8 || value > 4096 || value % 8) return -1; k.ws_grid = value; return 0; }
-    if (knob == 5) { return k.x6_launches.exchange(0); }
-    if (knob == 14) { if (value < 0 || value > 2) return -1; k.pool_slab = value; return 0; }
-    if (knob == 15) { if (value != 0 && value != 1) return -1; k.pool_dslide = value; return 0; }
-    if (knob == 16) { if (value != 0 && value != 1) return -1; k.conv_halo = value; return 0; }
-    if (knob == 17) { if (value < 1 || value > (1 << 24)) return -1; k.conv_halo_min_tiles = value; return 0; }
-    if (knob == 18) { if (value != 0 && value != 1) return -1; k.skinny_nt = value; return 0; }
-    if (knob == 19) { if (value != 0 && value != 1) return -1; k.tile_walk = value; return 0; }
-    if (knob == 12) { if (value < 32 || value > (1 << 24)) return -1; k.team_spin = value; return 0; }     // poll bound of a team exchange
-    if (knob == 13) { if (value < 0 || value > 4096) return -1; k.team_drop = value; return 0; }          // fault injection (tests): unlaunched tail of a team grid
-    return -1;
-}
-extern "C" int segx_tune_get(int knob) {
-    const segx::Knobs& k = segx::knobs();
-    switch (knob) {
-        case 1: return segx::kget(k.interp_variant);
-        case 2: return segx::kget(k.conv_small_policy);
-        case 3: return segx::kget(k.bn_path);
-        case 4: return segx::kget(k.engine);
-        case 6: return segx::kget(k.x6_variant);
-        case 7: return segx::kget(k.conv_x6_wgrad_all);
-        case 8: return segx::kget(k.dw_strip_outputs);
-        case 9: return segx::kget(k.ws_grid);
-        case 12: return segx::kget(k.team_spin);
-        case 13: return segx::kget(k.team_drop);
-        case 14: return segx::kget(k.pool_slab);
-        case 15: return segx::kget(k.pool_dslide);
-        case 16: return segx::kget(k.conv_halo);
-        case 17: return segx::kget(k.conv_halo_min_tiles);
-        case 18: return segx::kget(k.skinny_nt);
-        case 19: return segx::kget(k.tile_walk);
-        default: return -1;
-    }
-}
 // RandomResizedCrop (datasets3d.py:611-665) as ONE gather pass: the volume is (virtually) resampled to (D, H, W) with the trilinear
 // align_corners=False rule, zero-padded, and a window of (od, oh, ow) voxels is cut out at offset (oz, oy, ox) measured in the resampled,
 // UNPADDED grid (i.e. crop start - front pad; negative / beyond-the-end coordinates fall into the padding and read 0).  Only the voxels

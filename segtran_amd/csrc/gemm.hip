@@ -142,6 +142,17 @@ static int call_engine(const segx_gemm_desc* d) {
     return d->engine == SEGX_ENGINE_SEL_F32 ? SEGX_ENGINE_F32 : d->engine == SEGX_ENGINE_SEL_BF16X6 ? SEGX_ENGINE_BF16X6 : kget(knobs().engine);
 }
 static bool x6_eligible(int engine, int M, int N, bool vec) { return engine == SEGX_ENGINE_BF16X6 && vec && M > 48 && N > 48; }
+// The pricing step of both planners: one candidate tile at the split factor the caller fixed (1 where the call may not split), or at the best one.
+// ws_grid > 0: the candidate is a wave-specialised tile, priced as a persistent launch of that many workgroups.  Returns the split factor, *t its time.
+static int price(const TileInfo& c, int M, int N, int K, int nbatch, bool may_split, int splitk_fixed, int ws_grid, double* t) {
+    const TileInfo6 c6{c.id, c.bm, c.bn, c.wg_per_cu, c.ktile_us, c.fixed_us};
+    if (splitk_fixed > 0 || !may_split) {
+        const int sk = splitk_fixed > 0 ? splitk_fixed : 1;
+        *t = ws_grid > 0 ? model_us_ws(c6, M, N, K, nbatch, sk, ws_grid) : model_us(c, M, N, K, nbatch, sk);
+        return sk;
+    }
+    return ws_grid > 0 ? best_splitk_ws(c6, M, N, K, nbatch, ws_grid, t) : best_splitk(c, M, N, K, nbatch, t);
+}
 // ws_ok: the wave-specialised persistent kernels may run this GEMM (whole 32-k stages, 32-bit operand offsets; no fused GELU: its epilogue
 // runs on four of the eight waves there and measured 63 against 91 TFLOP/s)
 // nrc = number of row-contiguous operands (0..2): their loaders cost the 4-wave kernels 9 % / 34 % per k-tile (r03_f: 201 / 185 / 150 TFLOP/s for
@@ -151,31 +162,26 @@ static void plan6(int M, int N, int K, int nbatch, bool gelu, bool may_split, in
     const float f4 = nrc == 0 ? 1.0f : nrc == 1 ? 1.09f : 1.34f, fws = nrc == 0 ? 1.0f : nrc == 1 ? 1.01f : 1.05f;
     for (const TileInfo6& c6 : kTiles6) {
         if (gelu && c6.id != SEGX_TILE_128x128) continue;                  // the fused GELU epilogue is built for the default tile
-        const TileInfo c{c6.id, c6.bm, c6.bn, c6.wg_per_cu, c6.ktile_us * f4, c6.fixed_us};
-        double t; int sk;
-        if (splitk_fixed > 0 || !may_split) { sk = splitk_fixed > 0 ? splitk_fixed : 1; t = model_us(c, M, N, K, nbatch, sk); }
-        else sk = best_splitk(c, M, N, K, nbatch, &t);
-        if (best_t < 0.0 || t < best_t * 0.97) { best_t = t; *tile = c.id; *splitk = sk; }
+        double t;
+        const int sk = price(TileInfo{c6.id, c6.bm, c6.bn, c6.wg_per_cu, c6.ktile_us * f4, c6.fixed_us}, M, N, K, nbatch, may_split, splitk_fixed, 0, &t);
+        if (best_t < 0.0 || t < best_t * 0.97) { best_t = t; *tile = c6.id; *splitk = sk; }
     }
     if (!ws_ok || gelu) return;
     for (const TileInfo6& w6 : kTilesWs) {
-        const TileInfo6 c6{w6.id, w6.bm, w6.bn, w6.wg_per_cu, w6.ktile_us * fws, w6.fixed_us};
-        double t; int sk;
-        if (splitk_fixed > 0 || !may_split) { sk = splitk_fixed > 0 ? splitk_fixed : 1; t = model_us_ws(c6, M, N, K, nbatch, sk, kget(knobs().ws_grid)); }
-        else sk = best_splitk_ws(c6, M, N, K, nbatch, kget(knobs().ws_grid), &t);
-        if (t < best_t * 0.97) { best_t = t; *tile = c6.id; *splitk = sk; }
+        double t;
+        const int sk = price(TileInfo{w6.id, w6.bm, w6.bn, w6.wg_per_cu, w6.ktile_us * fws, w6.fixed_us}, M, N, K, nbatch, may_split, splitk_fixed, kget(knobs().ws_grid), &t);
+        if (t < best_t * 0.97) { best_t = t; *tile = w6.id; *splitk = sk; }
     }
 }
-static bool gemm_lean_ok(const segx_gemm_desc* d);
-// a residual operand keeps the call on the 4-wave kernels: their epilogue reads it as 16-byte quads next to the 16-byte stores, the wave-specialised
-// kernels' 4-byte epilogue would read it scalar (r04_c: the 160 x 4096 x 960 x 6 dX GEMM 0.47 -> 0.76 ms/step with the residual on the 256 x 128 tile)
-static bool gemm_ws_ok(const segx_gemm_desc* d) { return !d->resid && gemm_lean_ok(d); }
 // whole 32-k stages and 32-bit operand offsets: what the lean loaders (4-wave lean kernels, wave-specialised kernels) need
 static bool gemm_lean_ok(const segx_gemm_desc* d) {
     const bool akc = (d->a_k == 1), bkc = (d->b_k == 1);
     const int64_t a_span = akc ? (int64_t)d->M * d->a_m : (int64_t)d->K * d->a_k, b_span = bkc ? (int64_t)d->N * d->b_n : (int64_t)d->K * d->b_k;
     return d->K % BKT == 0 && a_span < (1LL << 29) && b_span < (1LL << 29);
 }
+// a residual operand keeps the call on the 4-wave kernels: their epilogue reads it as 16-byte quads next to the 16-byte stores, the wave-specialised
+// kernels' 4-byte epilogue would read it scalar (r04_c: the 160 x 4096 x 960 x 6 dX GEMM 0.47 -> 0.76 ms/step with the residual on the 256 x 128 tile)
+static bool gemm_ws_ok(const segx_gemm_desc* d) { return !d->resid && gemm_lean_ok(d); }
 static void plan(int M, int N, int K, int nbatch, bool vec, bool may_split, int splitk_fixed, int* tile, int* splitk) {
     const TileInfo* cand[3]; int nc = 0;
     if (!vec) cand[nc++] = &kTiles[0];
@@ -184,9 +190,8 @@ static void plan(int M, int N, int K, int nbatch, bool vec, bool may_split, int 
     else { cand[nc++] = &kTiles[0]; cand[nc++] = &kTiles[1]; cand[nc++] = &kTiles[2]; }
     double best_t = -1.0;
     for (int i = 0; i < nc; ++i) {
-        double t; int sk;
-        if (splitk_fixed > 0 || !may_split) { sk = splitk_fixed > 0 ? splitk_fixed : 1; t = model_us(*cand[i], M, N, K, nbatch, sk); }
-        else sk = best_splitk(*cand[i], M, N, K, nbatch, &t);
+        double t;
+        const int sk = price(*cand[i], M, N, K, nbatch, may_split, splitk_fixed, 0, &t);
         if (best_t < 0.0 || t < best_t * 0.97) { best_t = t; *tile = cand[i]->id; *splitk = sk; }   // larger tiles win ties
     }
 }
@@ -210,9 +215,7 @@ static int skinny_nt_splitk(const float* A, const float* B, const segx_gemm_desc
     if ((int64_t)d->M * d->a_m >= (1LL << 31) || (int64_t)d->N * d->b_n >= (1LL << 31)) return 0;          // 32-bit row offsets inside a member
     return sk;
 }
-}  // namespace segx
 
-namespace segx {
 static int gemm_plan_impl(const float* A, const float* B, const segx_gemm_desc* d, int* tile, int* splitk, bool use_table) {
     SEGX_REQUIRE(A && B && d && tile && splitk && d->M > 0 && d->N > 0 && d->K > 0 && d->nb0 > 0 && d->nb1 > 0, "segx_gemm_plan: bad args");
     const bool plain = d->epilogue == SEGX_EPI_NONE;
@@ -233,6 +236,220 @@ static int gemm_plan_impl(const float* A, const float* B, const segx_gemm_desc* 
     else plan(d->M, d->N, d->K, d->nb0 * d->nb1, vec && plain, plain && !d->gmax, 0, &t, &sk);
     *tile = t; *splitk = sk;
     return 0;
+}
+
+// ---- routing: which kernel runs a validated descriptor ----------------------------------------------------------------------------------
+enum GemmFamily {
+    GEMM_F32,        // gemm_f32_kernel: v_mfma_f32_32x32x2_f32, every layout, float4-legal or not
+    GEMM_X6,         // gemm_x6_kernel: bf16x6, four waves
+    GEMM_X6_LEAN,    // gemm_x6_lean_kernel: the same with the lean operand loaders
+    GEMM_WS,         // gemm_x6ws_kernel: wave-specialised, persistent
+    GEMM_WS_PRE,     // gemm_x6ws_pre_kernel: ... with the B operand split ahead of time
+    GEMM_SKINNY      // gemm_skinny.hip: streaming batch-reduced weight gradient
+};
+struct GemmRoute {
+    int family;      // GemmFamily
+    int tile;        // SEGX_TILE_* the kernel is built for, after every fallback (never AUTO)
+    bool akc, bkc;   // A / B k-contiguous
+    bool vec;        // float4-legal operands (false: gemm_f32_kernel's scalar loaders, default tile)
+    int epi;         // SEGX_EPI_*
+    int sched;       // knob 6 as it applies to THIS kernel: 0 = the product schedule (gemm_x6_kernel at the waves per SIMD of its tile); GEMM_X6 on the plain NT
+                     // default tile: 1 / 6 / 7 (and the ablations 2..5 in SEGX_BENCH builds); GEMM_WS: 1 (2..5 on the plain NT form in SEGX_BENCH builds)
+    int splitk;      // k slabs (GEMM_SKINNY: x the batch size = its slabs = its grid)
+    int ws_grid;     // knob 9: most workgroups of a persistent launch (GEMM_WS, GEMM_WS_PRE)
+    bool walk;       // knob 19: the tiles may be walked M fastest (set_tiles)
+};
+static bool ws_tile_id(int tile) { return tile >= SEGX_TILE_256x128 && tile <= SEGX_TILE_WS256x96; }
+
+// Pure: reads the descriptor, the operand addresses (alignment only) and the knobs -- every knob a launch depends on is read here -- and launches nothing.
+static int gemm_route(const float* A, const float* B, const segx_gemm_desc* d, GemmRoute* out) {
+    GemmRoute r;
+    r.akc = d->a_k == 1; r.bkc = d->b_k == 1; r.vec = gemm_vec_ok(A, B, d);
+    r.epi = d->epilogue; r.sched = 0; r.splitk = d->splitk > 1 ? d->splitk : 1;
+    r.ws_grid = kget(knobs().ws_grid); r.walk = kget(knobs().tile_walk) != 0;
+    const int nbatch = d->nb0 * d->nb1;
+    const bool gelu = d->epilogue == SEGX_EPI_GELU, ws_forced = ws_tile_id(d->tile);
+    const int engine = call_engine(d);
+    SEGX_REQUIRE(!ws_forced || engine == SEGX_ENGINE_BF16X6, "segx_gemm_f32: tile %d exists on the bf16x6 engine only", d->tile);
+    int tile = d->tile;
+    if (tile == SEGX_TILE_SKINNY_NT) {
+        // the plan's slab count travels as splitk; anything the streaming kernel does not serve quietly takes the planner's tile (like the 96-row tiles)
+        const int ssk = skinny_nt_splitk(A, B, d);
+        if (ssk > 0 && r.splitk <= ssk) { r.family = GEMM_SKINNY; r.tile = tile; *out = r; return 0; }
+        tile = SEGX_TILE_AUTO;
+    }
+    // the wave-specialised kernels address an operand through 32-bit byte offsets from a per-item base and take whole 32-k stages only
+    const bool ws_ok = gemm_ws_ok(d);
+    // the bf16x6 engine has the default tile, the two 64-row tiles and the wave-specialised ones; its fused GELU is built for a k-contiguous A
+    const bool x6 = x6_eligible(engine, d->M, d->N, r.vec) && (!gelu || r.akc) &&
+                    (tile == SEGX_TILE_AUTO || tile == SEGX_TILE_128x128 || tile == SEGX_TILE_64x128 || tile == SEGX_TILE_64x64 || ws_forced);
+    if (tile == SEGX_TILE_AUTO) {                            // the caller chose the split factor (or 1): the tile is priced for that one
+        int sk_unused = 1;
+        if (x6) plan6(d->M, d->N, d->K, nbatch, gelu, false, r.splitk, ws_ok, (!r.akc) + (!r.bkc), &tile, &sk_unused);
+        else plan(d->M, d->N, d->K, nbatch, r.vec && !gelu, false, r.splitk, &tile, &sk_unused);
+    }
+    if (ws_forced && !ws_ok) tile = SEGX_TILE_128x128;
+    // the 96-row tiles (channel counts 272 / 160 / 192 / 672 / 960 of the backbone: 3 x 96 = 288 rows cover 272 where 3 x 128 compute 384) stage their 96-row
+    // side with the k-contiguous loader only (the row-contiguous one deals 64 / 128 / 256 rows over a workgroup); no fused GELU
+    if ((tile == SEGX_TILE_WS96x256 && (!r.akc || gelu)) || (tile == SEGX_TILE_WS256x96 && (!r.bkc || gelu))) tile = SEGX_TILE_128x128;
+    // no fused GELU on the other two few-channel tiles either (pointwise convolutions have none): the default tile's four-wave form runs it
+    if (gelu && (tile == SEGX_TILE_WS128x256 || tile == SEGX_TILE_WS64x256)) tile = SEGX_TILE_128x128;
+    const bool ws = x6 && ws_ok && ws_tile_id(tile);
+    if (!r.vec || (gelu && !ws) || (ws_forced && !x6)) tile = SEGX_TILE_128x128;       // odd shapes / fused GELU: only the default tile (and the wave-specialised ones) are built
+    r.tile = tile;
+    if (!x6) {
+        SEGX_REQUIRE(!gelu || r.akc, "segx_gemm_f32: the GELU epilogue is built for a k-contiguous A operand (nn.Linear, attention fusion)");
+        r.family = GEMM_F32;
+    } else if (ws) {
+        // persistent launch.  Variant 1 = consumers at raised wave priority (same results); the ablation variants 2..5 (results are NOT the GEMM) exist in
+        // -DSEGX_BENCH builds only (tools/build_variant.py), for the plain NT form
+        const int v = kget(knobs().x6_variant);
+        r.sched = v == 1 ? 1 : 0;
+#ifdef SEGX_BENCH
+        if (v >= 2 && v <= 5 && !gelu && r.akc && r.bkc) r.sched = v;
+#endif
+        // pre-split B operand (segx_x6_presplit): the wave-specialised 256 x 128 / 128 x 256 kernels with a copy-only B loader; anything else ignores the planes
+        const bool pre = d->b_planes && !gelu && (tile == SEGX_TILE_256x128 || tile == SEGX_TILE_WS128x256);
+        r.family = pre ? GEMM_WS_PRE : GEMM_WS;
+        if (pre) r.sched = 0;
+    } else {
+        const int v = kget(knobs().x6_variant);
+        if (v > 0 && !gelu && r.akc && r.bkc && tile == SEGX_TILE_128x128) {
+            r.family = GEMM_X6; r.sched = v;                 // the schedule variants are built on the plain NT default tile with the dense loaders
+        } else {
+#ifdef SEGX_NO_LEAN                                          // bench-only A/B build (tools/build_variant.py)
+            r.family = GEMM_X6;
+#else
+            r.family = gemm_lean_ok(d) ? GEMM_X6_LEAN : GEMM_X6;
+#endif
+        }
+    }
+    *out = r;
+    return 0;
+}
+
+// ---- launch: the route's run-time choices -> template arguments.  Only the forms a route can name are instantiated: the 96-row tiles for one layout pair each,
+// the fused GELU with a k-contiguous A only, the schedule variants on the plain NT default tile only. ---------------------------------------------------------
+using GemmKernel = void (*)(GemmArgs);
+struct GemmLaunch { GemmKernel fn; int bm, bn; };            // bm x bn: the tile the kernel was instantiated for
+template <class Cfg> static GemmLaunch built_for(GemmKernel fn) { return GemmLaunch{fn, Cfg::BM, Cfg::BN}; }
+// a run-time flag as a template argument: f(std::true_type) or f(std::false_type)
+template <class F> static GemmKernel by_flag(bool flag, F f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }
+// THE place where the layout flags become template arguments: f(A k-contiguous, B k-contiguous)
+template <class F> static GemmKernel by_layout(const GemmRoute& r, F f) {
+    return by_flag(r.akc, [&](auto ak) { return by_flag(r.bkc, [&](auto bk) { return f(ak, bk); }); });
+}
+
+using Cfg64 = TileCfg<2, 2, 1, 1>; using Cfg128x32 = TileCfg<4, 1, 1, 1>; using Cfg32x128 = TileCfg<1, 4, 1, 1>; using Cfg64x128 = TileCfg<2, 2, 1, 2>;
+using Cfg256x128 = TileCfg<2, 2, 4, 2>;
+using Cfg128x256 = TileCfg<2, 2, 2, 4>; using Cfg64x256 = TileCfg<2, 2, 1, 4>; using Cfg96x256 = TileCfg<1, 4, 3, 2>; using Cfg256x96 = TileCfg<4, 1, 2, 3>;      // few output channels x many positions (backbone pointwise convolutions)
+
+template <class Cfg> static GemmLaunch f32_tile(const GemmRoute& r) {
+    return built_for<Cfg>(by_layout(r, [](auto ak, auto bk) -> GemmKernel { return gemm_f32_kernel<Cfg, decltype(ak)::value, decltype(bk)::value, true, SEGX_EPI_NONE>; }));
+}
+static GemmLaunch f32_kernel(const GemmRoute& r) {
+    if (r.epi == SEGX_EPI_GELU)
+        return built_for<Cfg128>(by_flag(r.bkc, [&](auto bk) { return by_flag(r.vec, [](auto v) -> GemmKernel {
+            return gemm_f32_kernel<Cfg128, true, decltype(bk)::value, decltype(v)::value, SEGX_EPI_GELU>; }); }));
+    if (!r.vec) return built_for<Cfg128>(by_layout(r, [](auto ak, auto bk) -> GemmKernel { return gemm_f32_kernel<Cfg128, decltype(ak)::value, decltype(bk)::value, false, SEGX_EPI_NONE>; }));
+    switch (r.tile) {
+        case SEGX_TILE_64x64: return f32_tile<Cfg64>(r);
+        case SEGX_TILE_128x32: return f32_tile<Cfg128x32>(r);
+        case SEGX_TILE_32x128: return f32_tile<Cfg32x128>(r);
+        case SEGX_TILE_64x128: return f32_tile<Cfg64x128>(r);
+        default: return f32_tile<Cfg128>(r);
+    }
+}
+
+// the four-wave bf16x6 kernels; W = waves per SIMD the tile's registers and LDS allow
+template <bool LEAN, class Cfg, bool AK, bool BK, int E, int W> static GemmKernel x6_form() {
+    if constexpr (LEAN) return gemm_x6_lean_kernel<Cfg, AK, BK, E, W>; else return gemm_x6_kernel<Cfg, AK, BK, E, W>;
+}
+template <bool LEAN, class Cfg, int W> static GemmLaunch x6_tile(const GemmRoute& r) {
+    return built_for<Cfg>(by_layout(r, [](auto ak, auto bk) { return x6_form<LEAN, Cfg, decltype(ak)::value, decltype(bk)::value, SEGX_EPI_NONE, W>(); }));
+}
+template <bool LEAN> static GemmLaunch x6_kernel(const GemmRoute& r) {
+    if (r.epi == SEGX_EPI_GELU) return built_for<Cfg128>(by_flag(r.bkc, [](auto bk) { return x6_form<LEAN, Cfg128, true, decltype(bk)::value, SEGX_EPI_GELU, 3>(); }));
+    switch (r.tile) {
+        case SEGX_TILE_64x64: return x6_tile<LEAN, Cfg64, 5>(r);
+        case SEGX_TILE_64x128: return x6_tile<LEAN, Cfg64x128, 4>(r);
+        default: return x6_tile<LEAN, Cfg128, 3>(r);
+    }
+}
+// the schedule variants of gemm_x6_kernel (plain NT, default tile): <waves per SIMD, VAR>
+template <int W, int VAR> static GemmLaunch x6_sched() { return built_for<Cfg128>(gemm_x6_kernel<Cfg128, true, true, SEGX_EPI_NONE, W, VAR>); }
+static GemmLaunch x6_sched_kernel(int sched) {
+    switch (sched) {
+        case 1: return x6_sched<3, 1>();
+        case 6: return x6_sched<2, 6>();
+#ifdef SEGX_BENCH
+        case 2: return x6_sched<3, 2>(); case 3: return x6_sched<3, 3>(); case 4: return x6_sched<3, 4>(); case 5: return x6_sched<3, 5>();
+#endif
+        default: return x6_sched<2, 0>();      // 7: the product schedule at two waves per SIMD (what the split-early schedule is compared with)
+    }
+}
+template <class Cfg, bool AK, bool BK, int E> static GemmKernel ws_form(int sched) {
+    constexpr bool NT = E == SEGX_EPI_NONE && AK && BK;      // the ablations are built for the plain NT form
+    switch (sched) {
+        case 1: return gemm_x6ws_kernel<Cfg, AK, BK, E, 1>;
+#ifdef SEGX_BENCH
+        case 2: return gemm_x6ws_kernel<Cfg, AK, BK, E, NT ? 2 : 0>; case 3: return gemm_x6ws_kernel<Cfg, AK, BK, E, NT ? 3 : 0>;
+        case 4: return gemm_x6ws_kernel<Cfg, AK, BK, E, NT ? 4 : 0>; case 5: return gemm_x6ws_kernel<Cfg, AK, BK, E, NT ? 5 : 0>;
+#endif
+        default: return gemm_x6ws_kernel<Cfg, AK, BK, E, 0>;
+    }
+}
+// every layout, and the fused GELU with a k-contiguous A (gemm_route names the GELU form for the 256 x 128 and 128 x 128 tiles only)
+template <class Cfg> static GemmLaunch ws_tile(const GemmRoute& r) {
+    if (r.epi == SEGX_EPI_GELU) return built_for<Cfg>(by_flag(r.bkc, [&](auto bk) { return ws_form<Cfg, true, decltype(bk)::value, SEGX_EPI_GELU>(r.sched); }));
+    return built_for<Cfg>(by_layout(r, [&](auto ak, auto bk) { return ws_form<Cfg, decltype(ak)::value, decltype(bk)::value, SEGX_EPI_NONE>(r.sched); }));
+}
+static GemmLaunch ws_kernel(const GemmRoute& r) {
+    switch (r.tile) {
+        case SEGX_TILE_256x128: return ws_tile<Cfg256x128>(r);
+        case SEGX_TILE_WS128x128: return ws_tile<Cfg128>(r);
+        case SEGX_TILE_WS128x256: return ws_tile<Cfg128x256>(r);
+        case SEGX_TILE_WS64x256: return ws_tile<Cfg64x256>(r);
+        case SEGX_TILE_WS96x256: return built_for<Cfg96x256>(by_flag(r.bkc, [&](auto bk) { return ws_form<Cfg96x256, true, decltype(bk)::value, SEGX_EPI_NONE>(r.sched); }));
+        default: return built_for<Cfg256x96>(by_flag(r.akc, [&](auto ak) { return ws_form<Cfg256x96, decltype(ak)::value, true, SEGX_EPI_NONE>(r.sched); }));
+    }
+}
+template <class Cfg> static GemmLaunch ws_pre_tile(const GemmRoute& r) {
+    return built_for<Cfg>(by_flag(r.akc, [](auto ak) -> GemmKernel { return gemm_x6ws_pre_kernel<Cfg, decltype(ak)::value>; }));
+}
+static GemmLaunch route_kernel(const GemmRoute& r) {
+    switch (r.family) {
+        case GEMM_X6: return r.sched ? x6_sched_kernel(r.sched) : x6_kernel<false>(r);
+#ifndef SEGX_NO_LEAN
+        case GEMM_X6_LEAN: return x6_kernel<true>(r);
+#endif
+        case GEMM_WS: return ws_kernel(r);
+        case GEMM_WS_PRE: return r.tile == SEGX_TILE_256x128 ? ws_pre_tile<Cfg256x128>(r) : ws_pre_tile<Cfg128x256>(r);
+        default: return f32_kernel(r);
+    }
+}
+static void set_tiles(GemmArgs& g, const GemmLaunch& k, const GemmRoute& r) {
+    g.tiles_m = ceil_div(g.M, k.bm); g.tiles_n = ceil_div(g.N, k.bn); g.mfast = r.walk ? tile_walk(g.M, g.N, g.K, g.tiles_m) : 0;
+}
+// persistent launch: one workgroup per CU, a multiple of eight (one run of items per XCD and round)
+static int persistent_grid(const GemmArgs& g, const GemmRoute& r, int* grid) {
+    const int64_t items = (int64_t)g.tiles_m * g.tiles_n * g.nbatch * g.splitk;
+    SEGX_REQUIRE(items < 2147483647LL - 512, "segx_gemm_f32: too many tiles");
+    *grid = (int)i64min(r.ws_grid, (items + 7) / 8 * 8);
+    return 0;
+}
+// The workspace holds nslabs slabs of M x N (slab (zk, zb) at (zk * nbatch + zb) * M * N): one deterministic sum over all of them.  The streaming skinny kernel's
+// slabs are always few outputs (one side <= 32 rows): it takes one of the two per-output-parts forms whatever the sizes.
+static void slab_reduce(const segx_gemm_desc* d, float* C, const float* bias, int nslabs, bool skinny, hipStream_t stream) {
+    const int64_t total = (int64_t)d->M * d->N;
+    const float* ws = static_cast<const float*>(d->workspace);
+    if (total * 16 <= 512 * 1024 && nslabs >= 16)          // few outputs, many slabs: 16 threads per output
+        hipLaunchKernelGGL((slab_sum_parts_kernel<16>), dim3((unsigned)((total + 15) / 16)), dim3(256), 0, stream, ws, C, bias, d->M, d->N, nslabs, total, d->c_m, d->alpha, d->bias_mode);
+    else if (skinny || (total * 4 <= 1024 * 1024 && nslabs >= 4))
+        hipLaunchKernelGGL((slab_sum_parts_kernel<4>), dim3((unsigned)((total + 63) / 64)), dim3(256), 0, stream, ws, C, bias, d->M, d->N, nslabs, total, d->c_m, d->alpha, d->bias_mode);
+    else
+        SEGX_SPLITK_REDUCE((unsigned)i64min(2048, (total + 255) / 256), stream, ws, C, bias, d->M, d->N, 1, nslabs, total, (int64_t)0, (int64_t)0, d->c_m, d->alpha,
+                           d->bias_mode, (int64_t)0, (int64_t)0, total, (const float*)nullptr);
 }
 }  // namespace segx
 
@@ -256,219 +473,57 @@ extern "C" int segx_gemm_f32(const float* A, const float* B, float* C, const seg
     SEGX_REQUIRE(splitk == 1 || (d->workspace && d->epilogue == SEGX_EPI_NONE && !d->gmax), "segx_gemm_f32: split-K needs workspace and a plain epilogue");
     const bool breduce = d->batch_reduce != 0;
     SEGX_REQUIRE(!breduce || (d->workspace && d->epilogue == SEGX_EPI_NONE && !d->gmax), "segx_gemm_f32: batch_reduce needs workspace and a plain epilogue");
+    SEGX_REQUIRE(!d->resid || (d->epilogue == SEGX_EPI_NONE && !breduce && !d->gmax), "segx_gemm_f32: resid needs a plain epilogue (no GELU, no batch_reduce, no gmax)");
+    SEGX_REQUIRE(d->tile >= SEGX_TILE_AUTO && d->tile <= SEGX_TILE_SKINNY_NT, "segx_gemm_f32: bad tile %d", d->tile);
+    SEGX_REQUIRE(d->engine >= SEGX_ENGINE_SEL_DEFAULT && d->engine <= SEGX_ENGINE_SEL_BF16X6, "segx_gemm_f32: bad engine selector %d", d->engine);
+    GemmRoute r;
+    int rc = gemm_route(A, B, d, &r);
+    if (rc) return rc;
 
+    const int nbatch = d->nb0 * d->nb1;
+    const float* bias = d->bias_mode ? d->bias : nullptr;
+    if (r.family == GEMM_SKINNY) {
+        const int nslabs = splitk * nbatch;
+        rc = launch_skinny_nt(A, B, static_cast<float*>(d->workspace), d->M, d->N, d->K, d->nb0, d->nb1, d->a_b0, d->a_b1, d->a_m, d->b_b0, d->b_b1, d->b_n, nslabs, stream);
+        if (rc) return rc;
+        slab_reduce(d, C, bias, nslabs, true, stream);
+        return check_launch("segx_gemm_f32/skinny_nt_reduce");
+    }
     GemmArgs g;
-    g.A = A; g.B = B; g.C = C; g.bias = d->bias_mode ? d->bias : nullptr; g.aux = d->epilogue == SEGX_EPI_GELU ? d->aux : nullptr;
+    g.A = A; g.B = B; g.C = C; g.bias = bias; g.aux = d->epilogue == SEGX_EPI_GELU ? d->aux : nullptr;
     g.gmax = d->gmax;
-    g.M = d->M; g.N = d->N; g.K = d->K; g.nb1 = d->nb1; g.nbatch = d->nb0 * d->nb1;
+    g.M = d->M; g.N = d->N; g.K = d->K; g.nb1 = d->nb1; g.nbatch = nbatch;
     g.a_b0 = d->a_b0; g.a_b1 = d->a_b1; g.a_m = d->a_m; g.a_k = d->a_k;
     g.b_b0 = d->b_b0; g.b_b1 = d->b_b1; g.b_n = d->b_n; g.b_k = d->b_k;
     g.c_b0 = d->c_b0; g.c_b1 = d->c_b1; g.c_m = d->c_m; g.bias_b1 = d->bias_b1; g.bias_b0 = d->bias_b0;
     g.alpha = d->alpha; g.epilogue = d->epilogue; g.bias_mode = d->bias_mode;
-    const bool akc = (d->a_k == 1), bkc = (d->b_k == 1);
-    const bool vec = gemm_vec_ok(A, B, d);
-    g.vecA = vec; g.vecB = vec;
+    g.vecA = r.vec; g.vecB = r.vec;
     g.dropout_p = d->dropout_p; g.seed = d->seed; g.offset = d->offset; g.rbase = rng_base();
     g.splitk = splitk;
     // k_chunk: multiple of the k-tile so slabs start on tile boundaries (and stay float4-aligned)
     g.k_chunk = splitk == 1 ? d->K : ceil_div(ceil_div(d->K, splitk), BKT) * BKT;
-    const int nbatch = d->nb0 * d->nb1;
     g.c_split = (int64_t)nbatch * d->M * d->N;
     g.slab = breduce ? 1 : 0;
     g.Bp = nullptr; g.bp_plane = g.bp_b0 = g.bp_b1 = 0;
+    if (r.family == GEMM_WS_PRE) { g.Bp = static_cast<const unsigned short*>(d->b_planes); g.bp_plane = (int64_t)d->N * d->K; g.bp_b0 = d->bp_b0; g.bp_b1 = d->bp_b1; }
     g.resid = d->resid;
-    SEGX_REQUIRE(!d->resid || (d->epilogue == SEGX_EPI_NONE && !breduce && !d->gmax), "segx_gemm_f32: resid needs a plain epilogue (no GELU, no batch_reduce, no gmax)");
     if (splitk > 1 || breduce) g.C = d->workspace;
-    SEGX_REQUIRE(d->tile >= SEGX_TILE_AUTO && d->tile <= SEGX_TILE_SKINNY_NT, "segx_gemm_f32: bad tile %d", d->tile);
-    const bool ws_tile = d->tile >= SEGX_TILE_256x128 && d->tile <= SEGX_TILE_WS256x96;
-    SEGX_REQUIRE(d->engine >= SEGX_ENGINE_SEL_DEFAULT && d->engine <= SEGX_ENGINE_SEL_BF16X6, "segx_gemm_f32: bad engine selector %d", d->engine);
-    const int engine = call_engine(d);
-    SEGX_REQUIRE(!ws_tile || engine == SEGX_ENGINE_BF16X6, "segx_gemm_f32: tile %d exists on the bf16x6 engine only", d->tile);
-    const int x6_variant = kget(knobs().x6_variant);
-    int tile = d->tile;
-    if (tile == SEGX_TILE_SKINNY_NT) {
-        // the plan's slab count travels as splitk; anything the streaming kernel does not serve quietly takes the planner's tile (like the 96-row tiles)
-        const int ssk = skinny_nt_splitk(A, B, d);
-        if (ssk > 0 && splitk <= ssk) {
-            const int nslabs = splitk * d->nb0 * d->nb1;
-            int rc = launch_skinny_nt(A, B, static_cast<float*>(d->workspace), d->M, d->N, d->K, d->nb0, d->nb1, d->a_b0, d->a_b1, d->a_m, d->b_b0, d->b_b1, d->b_n,
-                                      nslabs, stream);
-            if (rc) return rc;
-            const int64_t total = (int64_t)d->M * d->N;
-            if (total * 16 <= 512 * 1024 && nslabs >= 16)
-                hipLaunchKernelGGL((slab_sum_parts_kernel<16>), dim3((unsigned)((total + 15) / 16)), dim3(256), 0, stream, (const float*)d->workspace, C, g.bias,
-                                   d->M, d->N, nslabs, total, d->c_m, d->alpha, d->bias_mode);
-            else
-                hipLaunchKernelGGL((slab_sum_parts_kernel<4>), dim3((unsigned)((total + 63) / 64)), dim3(256), 0, stream, (const float*)d->workspace, C, g.bias,
-                                   d->M, d->N, nslabs, total, d->c_m, d->alpha, d->bias_mode);
-            return check_launch("segx_gemm_f32/skinny_nt_reduce");
-        }
-        tile = SEGX_TILE_AUTO;
-    }
-    const bool gelu = d->epilogue == SEGX_EPI_GELU;
-    // the wave-specialised kernels address an operand through 32-bit byte offsets from a per-item base and take whole 32-k stages only
-    const bool ws_ok = gemm_ws_ok(d), lean_ok = gemm_lean_ok(d);
-    bool x6 = x6_eligible(engine, d->M, d->N, vec) && (!gelu || akc) &&
-              (tile == SEGX_TILE_AUTO || tile == SEGX_TILE_128x128 || tile == SEGX_TILE_64x128 || tile == SEGX_TILE_64x64 || ws_tile);
-    if (tile == SEGX_TILE_AUTO) {
-        int sk_unused = 1;
-        if (x6) plan6(d->M, d->N, d->K, nbatch, gelu, false, splitk, ws_ok, (!akc) + (!bkc), &tile, &sk_unused);
-        else plan(d->M, d->N, d->K, nbatch, vec && !gelu, false, splitk, &tile, &sk_unused);
-    }
-    if (ws_tile && !ws_ok) tile = SEGX_TILE_128x128;
-    // the 96-row tiles (channel counts 272 / 160 / 192 / 672 / 960 of the backbone: 3 x 96 = 288 rows cover 272 where 3 x 128 compute 384) stage their 96-row
-    // side with the k-contiguous loader only (the row-contiguous one deals 64 / 128 / 256 rows over a workgroup); no fused GELU
-    if ((tile == SEGX_TILE_WS96x256 && (!akc || gelu)) || (tile == SEGX_TILE_WS256x96 && (!bkc || gelu))) tile = SEGX_TILE_128x128;
-    const bool ws = x6 && ws_ok && tile >= SEGX_TILE_256x128 && tile <= SEGX_TILE_WS256x96;
-    if (!vec || (gelu && !ws) || (ws_tile && !x6)) tile = SEGX_TILE_128x128;       // odd shapes / fused GELU: only the default tile (and the wave-specialised ones) are built
 
-    dim3 block(256);
-    using Cfg64 = TileCfg<2, 2, 1, 1>; using Cfg128x32 = TileCfg<4, 1, 1, 1>; using Cfg32x128 = TileCfg<1, 4, 1, 1>;
-    using Cfg64x128 = TileCfg<2, 2, 1, 2>;
-    if (x6) {
-        knobs().x6_launches.fetch_add(1, std::memory_order_relaxed);
-#ifdef SEGX_NO_LEAN                                     // bench-only A/B build (tools/build_variant.py)
-#define SEGX_LEAN4 false
-#else
-#define SEGX_LEAN4 true
-#endif
-#define SEGX_LAUNCH6(CFG, AK, BK, E, W)                                                                    \
-    do {                                                                                                   \
-        g.tiles_m = ceil_div(d->M, CFG::BM); g.tiles_n = ceil_div(d->N, CFG::BN); g.mfast = kget(knobs().tile_walk) ? tile_walk(d->M, d->N, d->K, g.tiles_m) : 0;                          \
-        if (SEGX_LEAN4 && lean_ok) hipLaunchKernelGGL((gemm_x6_lean_kernel<CFG, AK, BK, E, W>), dim3(g.tiles_m * g.tiles_n, nbatch, splitk), block, 0, stream, g); \
-        else hipLaunchKernelGGL((gemm_x6_kernel<CFG, AK, BK, E, W>), dim3(g.tiles_m * g.tiles_n, nbatch, splitk), block, 0, stream, g); \
-    } while (0)
-#define SEGX_LAUNCH6_LAYOUT(CFG, W)                                          \
-    do {                                                                     \
-        if (akc && bkc) SEGX_LAUNCH6(CFG, true, true, SEGX_EPI_NONE, W);      \
-        else if (akc && !bkc) SEGX_LAUNCH6(CFG, true, false, SEGX_EPI_NONE, W); \
-        else if (!akc && bkc) SEGX_LAUNCH6(CFG, false, true, SEGX_EPI_NONE, W); \
-        else SEGX_LAUNCH6(CFG, false, false, SEGX_EPI_NONE, W);               \
-    } while (0)
-        using Cfg256x128 = TileCfg<2, 2, 4, 2>;
-        // persistent launch: one workgroup per CU, a multiple of eight (one run of items per XCD and round).  Variant 1 = consumers at raised wave
-        // priority (same results); the ablation variants 2..5 (results are NOT the GEMM) exist in -DSEGX_BENCH builds only (tools/build_variant.py)
-#ifdef SEGX_BENCH
-#define SEGX_WS_VARIANTS(CFG, AK, BK, E)                                                                   \
-        switch (E == SEGX_EPI_NONE && AK && BK ? x6_variant : (x6_variant == 1 ? 1 : 0)) {                 \
-        case 1: hipLaunchKernelGGL((gemm_x6ws_kernel<CFG, AK, BK, E, 1>), dim3(G), dim3(512), 0, stream, g); break; \
-        case 2: hipLaunchKernelGGL((gemm_x6ws_kernel<CFG, AK, BK, E, (E == SEGX_EPI_NONE && AK && BK) ? 2 : 0>), dim3(G), dim3(512), 0, stream, g); break; \
-        case 3: hipLaunchKernelGGL((gemm_x6ws_kernel<CFG, AK, BK, E, (E == SEGX_EPI_NONE && AK && BK) ? 3 : 0>), dim3(G), dim3(512), 0, stream, g); break; \
-        case 4: hipLaunchKernelGGL((gemm_x6ws_kernel<CFG, AK, BK, E, (E == SEGX_EPI_NONE && AK && BK) ? 4 : 0>), dim3(G), dim3(512), 0, stream, g); break; \
-        case 5: hipLaunchKernelGGL((gemm_x6ws_kernel<CFG, AK, BK, E, (E == SEGX_EPI_NONE && AK && BK) ? 5 : 0>), dim3(G), dim3(512), 0, stream, g); break; \
-        default: hipLaunchKernelGGL((gemm_x6ws_kernel<CFG, AK, BK, E, 0>), dim3(G), dim3(512), 0, stream, g); }
-#else
-#define SEGX_WS_VARIANTS(CFG, AK, BK, E)                                                                   \
-        if (x6_variant == 1) hipLaunchKernelGGL((gemm_x6ws_kernel<CFG, AK, BK, E, 1>), dim3(G), dim3(512), 0, stream, g); \
-        else hipLaunchKernelGGL((gemm_x6ws_kernel<CFG, AK, BK, E, 0>), dim3(G), dim3(512), 0, stream, g);
-#endif
-#define SEGX_LAUNCHWS(CFG, AK, BK, E)                                                                      \
-    do {                                                                                                   \
-        g.tiles_m = ceil_div(d->M, CFG::BM); g.tiles_n = ceil_div(d->N, CFG::BN); g.mfast = kget(knobs().tile_walk) ? tile_walk(d->M, d->N, d->K, g.tiles_m) : 0;                          \
-        const int64_t items = (int64_t)g.tiles_m * g.tiles_n * nbatch * splitk;                            \
-        SEGX_REQUIRE(items < 2147483647LL - 512, "segx_gemm_f32: too many tiles");                         \
-        const int G = (int)i64min(kget(knobs().ws_grid), (items + 7) / 8 * 8);                                              \
-        SEGX_WS_VARIANTS(CFG, AK, BK, E)                                                                    \
-    } while (0)
-#define SEGX_LAUNCHWS_LAYOUT(CFG)                                                          \
-    do {                                                                                   \
-        if (gelu) { if (bkc) SEGX_LAUNCHWS(CFG, true, true, SEGX_EPI_GELU); else SEGX_LAUNCHWS(CFG, true, false, SEGX_EPI_GELU); } \
-        else if (akc && bkc) SEGX_LAUNCHWS(CFG, true, true, SEGX_EPI_NONE);                \
-        else if (akc && !bkc) SEGX_LAUNCHWS(CFG, true, false, SEGX_EPI_NONE);              \
-        else if (!akc && bkc) SEGX_LAUNCHWS(CFG, false, true, SEGX_EPI_NONE);              \
-        else SEGX_LAUNCHWS(CFG, false, false, SEGX_EPI_NONE);                              \
-    } while (0)
-#define SEGX_LAUNCH6V(V, W)                                                                                \
-    do {                                                                                                   \
-        g.tiles_m = ceil_div(d->M, Cfg128::BM); g.tiles_n = ceil_div(d->N, Cfg128::BN); g.mfast = kget(knobs().tile_walk) ? tile_walk(d->M, d->N, d->K, g.tiles_m) : 0;                    \
-        hipLaunchKernelGGL((gemm_x6_kernel<Cfg128, true, true, SEGX_EPI_NONE, W, V>), dim3(g.tiles_m * g.tiles_n, nbatch, splitk), block, 0, stream, g); \
-    } while (0)
-        using Cfg128x256 = TileCfg<2, 2, 2, 4>; using Cfg64x256 = TileCfg<2, 2, 1, 4>; using Cfg96x256 = TileCfg<1, 4, 3, 2>; using Cfg256x96 = TileCfg<4, 1, 2, 3>;      // few output channels x many positions (backbone pointwise convolutions)
-        // pre-split B operand (segx_x6_presplit): the wave-specialised 256 x 128 / 128 x 256 kernels with a copy-only B loader; anything else ignores the planes
-        const bool pre = d->b_planes && ws && !gelu && (tile == SEGX_TILE_256x128 || tile == SEGX_TILE_WS128x256);
-        if (pre) {
-            g.Bp = static_cast<const unsigned short*>(d->b_planes); g.bp_plane = (int64_t)d->N * d->K; g.bp_b0 = d->bp_b0; g.bp_b1 = d->bp_b1;
-#define SEGX_LAUNCHWS_PRE(CFG)                                                                             \
-    do {                                                                                                   \
-        g.tiles_m = ceil_div(d->M, CFG::BM); g.tiles_n = ceil_div(d->N, CFG::BN); g.mfast = kget(knobs().tile_walk) ? tile_walk(d->M, d->N, d->K, g.tiles_m) : 0;                          \
-        const int64_t items = (int64_t)g.tiles_m * g.tiles_n * nbatch * splitk;                            \
-        SEGX_REQUIRE(items < 2147483647LL - 512, "segx_gemm_f32: too many tiles");                         \
-        const int G = (int)i64min(kget(knobs().ws_grid), (items + 7) / 8 * 8);                             \
-        if (akc) hipLaunchKernelGGL((gemm_x6ws_pre_kernel<CFG, true>), dim3(G), dim3(512), 0, stream, g);  \
-        else hipLaunchKernelGGL((gemm_x6ws_pre_kernel<CFG, false>), dim3(G), dim3(512), 0, stream, g);     \
-    } while (0)
-            if (tile == SEGX_TILE_256x128) SEGX_LAUNCHWS_PRE(Cfg256x128); else SEGX_LAUNCHWS_PRE(Cfg128x256);
-#undef SEGX_LAUNCHWS_PRE
-        }
-        else if (tile == SEGX_TILE_256x128) SEGX_LAUNCHWS_LAYOUT(Cfg256x128);
-        else if (tile == SEGX_TILE_WS128x128) SEGX_LAUNCHWS_LAYOUT(Cfg128);
-        else if (tile == SEGX_TILE_WS128x256 && !gelu) SEGX_LAUNCHWS_LAYOUT(Cfg128x256);
-        else if (tile == SEGX_TILE_WS64x256 && !gelu) SEGX_LAUNCHWS_LAYOUT(Cfg64x256);
-        else if (tile == SEGX_TILE_WS96x256) { if (bkc) SEGX_LAUNCHWS(Cfg96x256, true, true, SEGX_EPI_NONE); else SEGX_LAUNCHWS(Cfg96x256, true, false, SEGX_EPI_NONE); }
-        else if (tile == SEGX_TILE_WS256x96) { if (akc) SEGX_LAUNCHWS(Cfg256x96, true, true, SEGX_EPI_NONE); else SEGX_LAUNCHWS(Cfg256x96, false, true, SEGX_EPI_NONE); }
-        else if (gelu) { if (bkc) SEGX_LAUNCH6(Cfg128, true, true, SEGX_EPI_GELU, 3); else SEGX_LAUNCH6(Cfg128, true, false, SEGX_EPI_GELU, 3); }
-        else if (x6_variant > 0 && akc && bkc && (tile == SEGX_TILE_128x128 || tile == SEGX_TILE_AUTO)) {
-            switch (x6_variant) { case 1: SEGX_LAUNCH6V(1, 3); break; case 6: SEGX_LAUNCH6V(6, 2); break;
-#ifdef SEGX_BENCH
-                                  case 2: SEGX_LAUNCH6V(2, 3); break; case 3: SEGX_LAUNCH6V(3, 3); break; case 4: SEGX_LAUNCH6V(4, 3); break; case 5: SEGX_LAUNCH6V(5, 3); break;
-#endif
-                                  default: SEGX_LAUNCH6V(0, 2); break; }      // 7: the product schedule at two waves per SIMD (what the split-early schedule is compared with)
-        }
-        else if (tile == SEGX_TILE_64x64) SEGX_LAUNCH6_LAYOUT(Cfg64, 5);
-        else if (tile == SEGX_TILE_64x128) SEGX_LAUNCH6_LAYOUT(Cfg64x128, 4);
-        else SEGX_LAUNCH6_LAYOUT(Cfg128, 3);
-#undef SEGX_LAUNCH6
-#undef SEGX_LAUNCH6V
-#undef SEGX_LAUNCH6_LAYOUT
-#undef SEGX_LAUNCHWS
-#undef SEGX_WS_VARIANTS
-#undef SEGX_LAUNCHWS_LAYOUT
+    if (r.family != GEMM_F32) knobs().x6_launches.fetch_add(1, std::memory_order_relaxed);
+    const GemmLaunch k = route_kernel(r);
+    set_tiles(g, k, r);
+    if (r.family == GEMM_WS || r.family == GEMM_WS_PRE) {
+        int grid;
+        rc = persistent_grid(g, r, &grid);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k.fn, dim3(grid), dim3(512), 0, stream, g);
     } else
-#define SEGX_LAUNCH(CFG, AK, BK, V, E)                                                                     \
-    do {                                                                                                   \
-        g.tiles_m = ceil_div(d->M, CFG::BM); g.tiles_n = ceil_div(d->N, CFG::BN); g.mfast = kget(knobs().tile_walk) ? tile_walk(d->M, d->N, d->K, g.tiles_m) : 0;                          \
-        hipLaunchKernelGGL((gemm_f32_kernel<CFG, AK, BK, V, E>), dim3(g.tiles_m * g.tiles_n, nbatch, splitk), block, 0, stream, g); \
-    } while (0)
-#define SEGX_LAUNCH_LAYOUT(CFG, V, E)                                   \
-    do {                                                                \
-        if (akc && bkc) SEGX_LAUNCH(CFG, true, true, V, E);             \
-        else if (akc && !bkc) SEGX_LAUNCH(CFG, true, false, V, E);      \
-        else if (!akc && bkc) SEGX_LAUNCH(CFG, false, true, V, E);      \
-        else SEGX_LAUNCH(CFG, false, false, V, E);                      \
-    } while (0)
-    if (d->epilogue == SEGX_EPI_GELU) {
-        SEGX_REQUIRE(akc, "segx_gemm_f32: the GELU epilogue is built for a k-contiguous A operand (nn.Linear, attention fusion)");
-        if (bkc) { if (vec) SEGX_LAUNCH(Cfg128, true, true, true, SEGX_EPI_GELU); else SEGX_LAUNCH(Cfg128, true, true, false, SEGX_EPI_GELU); }
-        else { if (vec) SEGX_LAUNCH(Cfg128, true, false, true, SEGX_EPI_GELU); else SEGX_LAUNCH(Cfg128, true, false, false, SEGX_EPI_GELU); }
-    } else if (!vec) {
-        SEGX_LAUNCH_LAYOUT(Cfg128, false, SEGX_EPI_NONE);
-    } else if (tile == SEGX_TILE_64x64) {
-        SEGX_LAUNCH_LAYOUT(Cfg64, true, SEGX_EPI_NONE);
-    } else if (tile == SEGX_TILE_128x32) {
-        SEGX_LAUNCH_LAYOUT(Cfg128x32, true, SEGX_EPI_NONE);
-    } else if (tile == SEGX_TILE_32x128) {
-        SEGX_LAUNCH_LAYOUT(Cfg32x128, true, SEGX_EPI_NONE);
-    } else if (tile == SEGX_TILE_64x128) {
-        SEGX_LAUNCH_LAYOUT(Cfg64x128, true, SEGX_EPI_NONE);
-    } else {
-        SEGX_LAUNCH_LAYOUT(Cfg128, true, SEGX_EPI_NONE);
-    }
-    int rc = check_launch("segx_gemm_f32");
+        hipLaunchKernelGGL(k.fn, dim3(g.tiles_m * g.tiles_n, nbatch, splitk), dim3(256), 0, stream, g);
+    rc = check_launch("segx_gemm_f32");
     if (rc) return rc;
     if (breduce) {
-        // the workspace holds splitk * nbatch slabs of M x N (slab (zk, zb) at (zk * nbatch + zb) * M * N): one deterministic sum over all of them
-        const int64_t total = (int64_t)d->M * d->N;
         SEGX_REQUIRE((int64_t)splitk * nbatch < 2147483647LL, "segx_gemm_f32: too many slabs");
-        const int nslabs = splitk * nbatch;
-        if (total * 16 <= 512 * 1024 && nslabs >= 16)          // few outputs, many slabs: 16 threads per output
-            hipLaunchKernelGGL((slab_sum_parts_kernel<16>), dim3((unsigned)((total + 15) / 16)), dim3(256), 0, stream, (const float*)d->workspace, C, g.bias,
-                               d->M, d->N, nslabs, total, d->c_m, d->alpha, d->bias_mode);
-        else if (total * 4 <= 1024 * 1024 && nslabs >= 4)
-            hipLaunchKernelGGL((slab_sum_parts_kernel<4>), dim3((unsigned)((total + 63) / 64)), dim3(256), 0, stream, (const float*)d->workspace, C, g.bias,
-                               d->M, d->N, nslabs, total, d->c_m, d->alpha, d->bias_mode);
-        else
-            SEGX_SPLITK_REDUCE((unsigned)i64min(2048, (total + 255) / 256), stream, (const float*)d->workspace, C, g.bias, d->M, d->N, 1, nslabs, total, (int64_t)0, (int64_t)0, d->c_m, d->alpha,
-                               d->bias_mode, (int64_t)0, (int64_t)0, total, (const float*)nullptr);
+        slab_reduce(d, C, bias, splitk * nbatch, false, stream);
         return check_launch("segx_gemm_f32/batch_reduce");
     }
     if (splitk > 1) {

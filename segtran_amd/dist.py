@@ -66,14 +66,14 @@ class GradReducer:
         # concurrent kernel can delay but not prevent: a team is at most half the CUs' worth of workgroups at two resident workgroups per CU (team_cap), RCCL's
         # channels hold a few dozen, and the polls are bounded and fail loudly (segx_team_status -> RuntimeError at the optimizer step).  r06:
         # the teams therefore STAY on by default -- the per-rank step keeps the 1 + 1 / 2 + 1 pass structure of the one-GPU step; r05 switched them off whenever
-        # overlap was on (3 ms per cfg2 step).  `overlap_bn_teams=False` restores that (two-launch form, knob 3 = 1) for a stack where the check does fail.
+        # overlap was on (3 ms per cfg2 step).  `overlap_bn_teams=False` restores that (two-launch form, Knob.BN_PATH = 1) for a stack where the check does fail.
         self.bn_teams_off, self._bn_path_prev = False, 0
         if overlap and (self.world > 1 or self.force) and self.flat.is_cuda and not overlap_bn_teams:
             from . import segx
             c = segx.lib().c
-            self._bn_path_prev = c.segx_tune_get(3)                 # whatever SEGX_TUNE / a bench loop / a test put there: restored by close(), left alone unless it is the default
+            self._bn_path_prev = c.segx_tune_get(segx.Knob.BN_PATH)                 # whatever SEGX_TUNE / a bench loop / a test put there: restored by close(), left alone unless it is the default
             if self._bn_path_prev == 0:
-                self.bn_teams_off = c.segx_tune(3, 1) == 0
+                self.bn_teams_off = c.segx_tune(segx.Knob.BN_PATH, 1) == 0
         self._armed, self._hooks = False, []
         self._pending, self._need, self._works, self._launched = [], [], [], []
         self._src, self._slot = None, 0
@@ -183,7 +183,7 @@ class GradReducer:
         self._hooks, self._armed = [], False
         if self.bn_teams_off:
             from . import segx
-            segx.lib().c.segx_tune(3, self._bn_path_prev)
+            segx.lib().c.segx_tune(segx.Knob.BN_PATH, self._bn_path_prev)
             self.bn_teams_off = False
 
 

@@ -5,7 +5,9 @@ product path has NO fallback (no oracle, no eager-PyTorch replacement).  The cla
 path-parameterised only so that tests can point it at the fiber-emulated build of the SAME sources
 (tests/hipemu) and exercise kernel index math on CPU tensors.
 """
+import contextlib
 import ctypes
+import enum
 import os
 import torch
 
@@ -35,6 +37,27 @@ EPI_NONE, EPI_GELU = 0, 1
 (TILE_AUTO, TILE_128x128, TILE_64x64, TILE_128x32, TILE_32x128, TILE_64x128, TILE_256x128, TILE_WS128x128, TILE_WS128x256, TILE_WS64x256,
  TILE_WS96x256, TILE_WS256x96, TILE_SKINNY_NT) = range(13)
 BIAS_NONE, BIAS_N, BIAS_M = 0, 1, 2
+
+
+class Knob(enum.IntEnum):
+    """The ids of segx_tune / segx_tune_get: SEGX_KNOB_* of include/segx.h (tests/test_abi.py holds the two lists equal)."""
+    INTERP_VARIANT = 1
+    CONV_SMALL_POLICY = 2
+    BN_PATH = 3
+    ENGINE = 4
+    X6_LAUNCHES = 5
+    X6_VARIANT = 6
+    CONV_X6_WGRAD_ALL = 7
+    DW_STRIP_OUTPUTS = 8
+    WS_GRID = 9
+    TEAM_SPIN = 12
+    TEAM_DROP = 13
+    POOL_SLAB = 14
+    POOL_DSLIDE = 15
+    CONV_HALO = 16
+    CONV_HALO_MIN_TILES = 17
+    SKINNY_NT = 18
+    TILE_WALK = 19
 
 
 def _ptr(t):
@@ -74,10 +97,32 @@ class SegxLib:
         """'f32': every GEMM / implicit-GEMM convolution on v_mfma_f32_32x32x2_f32 (a k-ordered fp32 fmaf chain); 'x6': eligible ones
         (float4-legal operands, > 48 rows on both sides) on the bf16 matrix core with the 3-way operand split (fp32-equivalent).
         Returns the previous engine name."""
-        prev = self.c.segx_tune(4, self.ENGINES[name])
-        if prev < 0:
-            raise RuntimeError('segx_tune(4): engine %r rejected' % name)
-        return 'x6' if prev == 1 else 'f32'
+        return 'x6' if self.tune(Knob.ENGINE, self.ENGINES[name]) == 1 else 'f32'
+
+    # ---- process-wide knobs (segx_tune) ---------------------------------------------------------
+    def tune(self, knob, value):
+        """Set one knob; raises on a setting the library refuses.  Returns what segx_tune returns (the previous engine for Knob.ENGINE, else 0)."""
+        rc = self.c.segx_tune(knob, value)
+        if rc < 0:
+            raise ValueError('segx_tune(%r, %r) refused' % (knob, value))
+        return rc
+
+    @contextlib.contextmanager
+    def tuned(self, **settings):
+        """with L.tuned(ws_grid=8, skinny_nt=0): ... -- knobs by their lower-case Knob names, set for the block; the values they HELD (segx_tune_get, not
+        the defaults) come back at its end."""
+        knobs = [Knob[name.upper()] for name in settings]
+        held = [(k, self.c.segx_tune_get(k)) for k in knobs]
+        for k, v in held:
+            if v < 0:                                        # Knob.X6_LAUNCHES is a counter, not a setting: nothing to put back
+                raise ValueError('tuned(): %r is not a readable setting' % k)
+        try:
+            for k, v in zip(knobs, settings.values()):
+                self.tune(k, v)
+            yield self
+        finally:
+            for k, v in reversed(held):
+                self.tune(k, v)
 
     def set_rng_base(self, t):
         """t: int64 [1] device tensor (kept alive by the caller) holding the device-side base of every dropout stream, or None."""
@@ -88,7 +133,7 @@ class SegxLib:
 
     def x6_launches(self):
         """launches that ran on the bf16x6 engine since the last call"""
-        return int(self.c.segx_tune(5, 0))
+        return int(self.c.segx_tune(Knob.X6_LAUNCHES, 0))
 
     # ---- team exchange: loud failure (include/segx.h: segx_team_status) ---------------------------------
     def team_check(self):
@@ -98,7 +143,7 @@ class SegxLib:
         if n:
             raise RuntimeError('libsegx: %d team exchange(s) of the team BatchNorm kernels timed out -- their workgroups were not co-resident (another kernel '
                                'holding the compute units, a CU mask, a partitioned device?).  The affected launches produced NaN statistics.  '
-                               'segx_tune(3, 1) selects the two-launch BatchNorm, which needs no exchange.' % n)
+                               'segx_tune(SEGX_KNOB_BN_PATH = 3, 1) selects the two-launch BatchNorm, which needs no exchange.' % n)
 
     def team_cap(self):
         return int(self.c.segx_team_cap())
@@ -637,8 +682,8 @@ _SIGS = {
     'segx_layernorm_fwd': 'pppppplifp', 'segx_layernorm_bwd': 'pppppplip',
     'segx_colreduce_ws_floats': 'lli', 'segx_colsum': 'pppllp', 'segx_ln_param_grad': 'ppppppplip',
     'segx_sum': 'plppfp', 'segx_rowsum': 'ppllp',
-    'segx_prenorm_fwd': 'pppplfppplliiffuup'.replace('lliif', 'liif'),
-    'segx_prenorm_bwd': 'ppppplfpppplii' + 'fuup',
+    'segx_prenorm_fwd': 'pppplfpppliiffuup',
+    'segx_prenorm_bwd': 'ppppplfppppliifuup',
     'segx_prenorm_bwd_all_ws_floats': 'ii', 'segx_prenorm_bwd_all': 'ppppplfpppppppiiifuup',
     'segx_posembed_fwd': 'pppppliifp', 'segx_posembed_bwd': 'ppppppliip',
     'segx_modes_aggr_fwd': 'pppppppiliffuup', 'segx_modes_aggr_bwd': 'ppppppppilifuup',

@@ -71,6 +71,13 @@ def test_gemm_desc_layout_matches_header():
     assert names == [f[0] for f in segx.GemmDesc._fields_], (names, [f[0] for f in segx.GemmDesc._fields_])
 
 
+def test_knob_names_match_header():
+    """segx.Knob (Python) and the SEGX_KNOB_* enum of include/segx.h: the same names with the same ids."""
+    hdr = open(os.path.join(ROOT, 'include', 'segx.h')).read()
+    declared = {name: int(v) for name, v in re.findall(r'\bSEGX_KNOB_(\w+)\s*=\s*(\d+)', re.sub(r'/\*.*?\*/', '', hdr, flags=re.S))}
+    assert len(declared) == 17 and declared == {k.name: k.value for k in segx.Knob}
+
+
 def test_product_library_rejects_the_ablation_variants():
     """include/segx.h: knob 6 values 2..5 (kernels whose results are NOT the GEMM) exist in -DSEGX_BENCH builds only."""
     from segtran_amd.build import build

@@ -4,6 +4,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 from segtran_amd import functional as SF
+from segtran_amd.segx import Knob
 
 
 def rnd(*shape, seed=0, scale=1.0):
@@ -187,17 +188,14 @@ def test_bn_forms_team_and_two_launch(backend, path, shape):
     130 x 132; 1 = never teams (130 x 132 then takes the two-launch form the default no longer reaches).  Plain / relu / swish, the skip + drop_connect
     tail and the squeeze-excite pooling variant must all match PyTorch in forward, backward and running statistics."""
     L = backend.L
-    assert L.c.segx_tune(3, 7) < 0                      # unknown settings are refused
-    assert L.c.segx_tune(3, path) == 0
-    try:
+    assert L.c.segx_tune(Knob.BN_PATH, 7) < 0           # unknown settings are refused
+    with L.tuned(bn_path=path):
         for act in (0, 1, 2):
             test_bn_act.__wrapped__(backend, shape, act, True) if hasattr(test_bn_act, '__wrapped__') else test_bn_act(backend, shape, act, True)
         if len(shape) == 4:
             test_bn_with_skip_add_and_drop_connect(backend, shape, 0.5, True)
             B, C, H, W = shape
             test_bn_act_squeeze_excite_fused(backend, B, C, 2, H, W, True)
-    finally:
-        assert L.c.segx_tune(3, 0) == 0
 
 
 @pytest.mark.parametrize('fill', ['ones_bits', 'small_ints', 'previous_call'])
@@ -264,34 +262,33 @@ def test_team_exchange_that_times_out_fails_loudly(backend):
     L.c.segx_team_status(1)
     ref = _team_run(L, x, dy, w, b)
     assert L.c.segx_team_status(0) == 0
-    assert L.c.segx_tune(12, 16) < 0 and L.c.segx_tune(13, -1) < 0 and L.c.segx_tune(13, 5000) < 0          # out-of-range settings are refused
-    assert L.c.segx_tune(12, 64) == 0 and L.c.segx_tune(13, 1) == 0
+    assert L.c.segx_tune(Knob.TEAM_SPIN, 16) < 0 and L.c.segx_tune(Knob.TEAM_DROP, -1) < 0 and L.c.segx_tune(Knob.TEAM_DROP, 5000) < 0          # out-of-range settings are refused
     try:
-        y, mean, var, dx, dw, db = _team_run(L, x, dy, w, b)
-        n = L.c.segx_team_status(0)
-        assert n >= 2                                          # forward AND backward launch of the last channel's team
-        assert torch.equal(mean[:C - 1], ref[1][:C - 1]) and torch.equal(y[:, :C - 1], ref[0][:, :C - 1]) and torch.equal(dx[:, :C - 1], ref[3][:, :C - 1])
-        assert torch.isnan(mean[C - 1]) and torch.isnan(var[C - 1]) and torch.isnan(dw[C - 1]) and torch.isnan(db[C - 1])
-        chunk = 1024 * 16                                      # floats per member (16 float4 per lane); the unlaunched member owns the last chunk of the last plane
-        assert torch.isnan(y[:, C - 1].reshape(-1)[:B * S - (S - chunk)]).all() and torch.isnan(dx[0, C - 1]).all()
-        with pytest.raises(RuntimeError, match='team exchange'):
-            L.team_check()
-        assert L.c.segx_team_status(0) == 0                    # team_check cleared the word
-        # the failed exchange must not reach the RUNNING statistics (a checkpoint written after the RuntimeError would keep them)
-        rm, rv = torch.zeros(C, device=x.device), torch.ones(C, device=x.device)
-        _team_run(L, x, dy, w, b, run=(rm, rv))
-        assert L.c.segx_team_status(1) >= 2
-        assert torch.isfinite(rm).all() and torch.isfinite(rv).all() and rm[C - 1] == 0 and rv[C - 1] == 1 and (rm[:C - 1] != 0).all()
-        # the training loop's hook: BertAdam.step() checks the word before it touches the weights
-        _team_run(L, x, dy, w, b)
-        from segtran_amd.optimization import BertAdam
-        p = torch.nn.Parameter(torch.ones(8, device=x.device)); p.grad = torch.ones(8, device=x.device)
-        opt = BertAdam([p], lr=1e-3, warmup=-1, t_total=-1)
-        with pytest.raises(RuntimeError, match='team exchange'):
-            opt.step()
-        assert torch.equal(p.detach(), torch.ones(8, device=x.device))
+        with L.tuned(team_spin=64, team_drop=1):
+            y, mean, var, dx, dw, db = _team_run(L, x, dy, w, b)
+            n = L.c.segx_team_status(0)
+            assert n >= 2                                          # forward AND backward launch of the last channel's team
+            assert torch.equal(mean[:C - 1], ref[1][:C - 1]) and torch.equal(y[:, :C - 1], ref[0][:, :C - 1]) and torch.equal(dx[:, :C - 1], ref[3][:, :C - 1])
+            assert torch.isnan(mean[C - 1]) and torch.isnan(var[C - 1]) and torch.isnan(dw[C - 1]) and torch.isnan(db[C - 1])
+            chunk = 1024 * 16                                      # floats per member (16 float4 per lane); the unlaunched member owns the last chunk of the last plane
+            assert torch.isnan(y[:, C - 1].reshape(-1)[:B * S - (S - chunk)]).all() and torch.isnan(dx[0, C - 1]).all()
+            with pytest.raises(RuntimeError, match='team exchange'):
+                L.team_check()
+            assert L.c.segx_team_status(0) == 0                    # team_check cleared the word
+            # the failed exchange must not reach the RUNNING statistics (a checkpoint written after the RuntimeError would keep them)
+            rm, rv = torch.zeros(C, device=x.device), torch.ones(C, device=x.device)
+            _team_run(L, x, dy, w, b, run=(rm, rv))
+            assert L.c.segx_team_status(1) >= 2
+            assert torch.isfinite(rm).all() and torch.isfinite(rv).all() and rm[C - 1] == 0 and rv[C - 1] == 1 and (rm[:C - 1] != 0).all()
+            # the training loop's hook: BertAdam.step() checks the word before it touches the weights
+            _team_run(L, x, dy, w, b)
+            from segtran_amd.optimization import BertAdam
+            p = torch.nn.Parameter(torch.ones(8, device=x.device)); p.grad = torch.ones(8, device=x.device)
+            opt = BertAdam([p], lr=1e-3, warmup=-1, t_total=-1)
+            with pytest.raises(RuntimeError, match='team exchange'):
+                opt.step()
+            assert torch.equal(p.detach(), torch.ones(8, device=x.device))
     finally:
-        assert L.c.segx_tune(12, 1 << 20) == 0 and L.c.segx_tune(13, 0) == 0
         L.c.segx_team_status(1)
     out = _team_run(L, x, dy, w, b)
     for a, r in zip(out, ref):
@@ -308,11 +305,8 @@ def test_bn_launch_refuses_a_buffer_sized_under_another_knob_setting(backend):
     w, b = torch.ones(C), torch.zeros(C)
     y, dx = torch.empty_like(x), torch.empty_like(x)
     mean, var, dw, db = (torch.empty(C, device=x.device) for _ in range(4))
-    assert L.c.segx_tune(3, 1) == 0
-    try:
+    with L.tuned(bn_path=1):
         small_p, small_w = L.bn_parts_floats(B, C, S), L.bn_ws(B, C, S)
-    finally:
-        assert L.c.segx_tune(3, 0) == 0
     need_p, need_w = L.bn_parts_floats(B, C, S), L.bn_ws(B, C, S)
     assert small_p < need_p and small_w < need_w
     with pytest.raises(RuntimeError, match='partials buffer holds'):
@@ -344,22 +338,21 @@ def test_team_batchnorm_next_to_a_kernel_that_holds_the_compute_units(hog, spin)
         assert L.c.segx_team_status(0) == 0
         side = torch.cuda.Stream()
         wgs = {'all_cus_80kb_lds': 512, 'most_cus_80kb_lds': 480, 'light': 2048}[hog]
-        assert L.c.segx_tune(12, spin) == 0
         try:
-            for rep in range(3):
-                with torch.cuda.stream(side):
-                    L.check(L.c.segx_occupy(wgs, 0 if hog == 'light' else 1, 30.0, None, L.stream(cases[0][0])), 'segx_occupy')
-                outs = [_team_run(L, *c) for c in cases]
-                torch.cuda.synchronize()
-                n = L.c.segx_team_status(1)
-                exact = all(torch.equal(a, r) for o, rf in zip(outs, refs) for a, r in zip(o, rf))
-                if spin == 1 << 20:
-                    assert n == 0 and exact, (hog, n, exact)
-                else:
-                    poisoned = any(bool(torch.isnan(o[1]).any()) or bool(torch.isnan(o[4]).any()) for o in outs)
-                    assert (n == 0 and exact) or (n > 0 and poisoned), (hog, n, exact, poisoned)
+            with L.tuned(team_spin=spin):
+                for rep in range(3):
+                    with torch.cuda.stream(side):
+                        L.check(L.c.segx_occupy(wgs, 0 if hog == 'light' else 1, 30.0, None, L.stream(cases[0][0])), 'segx_occupy')
+                    outs = [_team_run(L, *c) for c in cases]
+                    torch.cuda.synchronize()
+                    n = L.c.segx_team_status(1)
+                    exact = all(torch.equal(a, r) for o, rf in zip(outs, refs) for a, r in zip(o, rf))
+                    if spin == 1 << 20:
+                        assert n == 0 and exact, (hog, n, exact)
+                    else:
+                        poisoned = any(bool(torch.isnan(o[1]).any()) or bool(torch.isnan(o[4]).any()) for o in outs)
+                        assert (n == 0 and exact) or (n > 0 and poisoned), (hog, n, exact, poisoned)
         finally:
-            assert L.c.segx_tune(12, 1 << 20) == 0
             torch.cuda.synchronize()
             L.c.segx_team_status(1)
     finally:
@@ -630,8 +623,7 @@ def test_fixed_contributor_adjoints_equal_the_candidate_loops_bit_for_bit(backen
     G = rnd(planes, D, H, W, seed=95)
     outs = {}
     for variant in (0, 1):
-        assert L.c.segx_tune(1, variant) == 0
-        try:
+        with L.tuned(interp_variant=variant):
             g2 = torch.empty(planes * d * h * W); L.interp_bwd_axis2(G, g2, planes, D, d, H, h, W)
             g1 = torch.empty(planes * d * H * W); L.interp_bwd_axis(G, g1, planes, D, d, H * W, 0.0)
             gx = torch.empty(planes * D * H * (W // 4)) if W % 4 == 0 else None          # the contiguous axis (x4 / column-per-thread forms vs the per-cell form)
@@ -639,8 +631,6 @@ def test_fixed_contributor_adjoints_equal_the_candidate_loops_bit_for_bit(backen
                 L.interp_bwd_axis(G, gx, planes * D * H, W, W // 4, 1, 0.0)
             gy = torch.empty(planes * D * H * (W // 2)); L.interp_bwd_axis(G, gy, planes * D * H, W, W // 2, 1, 0.0)
             outs[variant] = (g2, g1, gx, gy)
-        finally:
-            assert L.c.segx_tune(1, 0) == 0
     for a, b in zip(outs[0], outs[1]):
         if a is None:
             continue
@@ -779,8 +769,7 @@ def test_bn_branches_write_their_slices_of_the_concatenation(backend, path, shap
     wide = rnd(B, 8, *shape[2:], seed=172)
     def inputs():
         return [(rnd(B, c, *shape[2:], seed=173 + i) * 1.3 + 0.2).requires_grad_(True) for i, c in enumerate(Cs)], wide.detach().clone().requires_grad_(True)
-    assert L.c.segx_tune(3, path) == 0
-    try:
+    with L.tuned(bn_path=path):
         bns, (xs, wd) = layers(), inputs()
         out = SF.bn_act_cat(wd[:, 3:8], list(zip(xs, bns)), SF.ACT_RELU)
         refs, (xr, wr) = layers(), inputs()
@@ -802,8 +791,6 @@ def test_bn_branches_write_their_slices_of_the_concatenation(backend, path, shap
         outt.backward(G)
         for x, t in zip(xs, xt):
             close(x.grad, t.grad, 1e-4)
-    finally:
-        assert L.c.segx_tune(3, 0) == 0
 
 
 def test_bn_forward_refuses_an_output_slice_it_cannot_write_in_quads(backend):

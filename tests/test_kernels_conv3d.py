@@ -3,6 +3,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 from segtran_amd import functional as SF
+from segtran_amd.segx import Knob
 
 
 def rnd(*shape, seed=0, scale=1.0):
@@ -69,9 +70,8 @@ def test_maxpool3d_stride1_slab_form(backend, size, policy):
     L = backend.L
     if backend.name == 'emu' and size[0] * size[1] * size[2] > 12000 and policy != 1:
         pytest.skip('large planes on the emulator: the slab policy only (the other kernels are covered at small sizes)')
-    assert L.c.segx_tune(14, 3) < 0
-    assert L.c.segx_tune(14, policy) == 0
-    try:
+    assert L.c.segx_tune(Knob.POOL_SLAB, 3) < 0
+    with L.tuned(pool_slab=policy):
         x = torch.relu(rnd(2, 2, *size, seed=14))
         x[0, 0, :2] = 0.0                                      # whole windows of zeros: the first tap (or the padding) wins
         x[1, 1, size[0] // 2, size[1] // 2, size[2] // 2] = float('nan')
@@ -86,8 +86,6 @@ def test_maxpool3d_stride1_slab_form(backend, size, policy):
             close(x.grad, xr.grad, 1e-6)                       # ATen's device backward accumulates with atomics: the order of a cell's <= 27 terms is not fixed there
         else:
             assert torch.equal(x.grad, xr.grad)
-    finally:
-        assert L.c.segx_tune(14, 0) == 0
 
 
 
@@ -107,16 +105,13 @@ def test_maxpool3d_stride1_depth_sliding_form(backend, size):
     geom = (D, H, W, D, H, W, 3, 3, 3, 1, 1, 1, 1, 1, 1)
     G = rnd(B, C, *size, seed=35)
     outs = {}
-    assert L.c.segx_tune(15, 2) < 0
+    assert L.c.segx_tune(Knob.POOL_DSLIDE, 2) < 0
     for knob in (1, 0):
-        assert L.c.segx_tune(15, knob) == 0
-        try:
+        with L.tuned(pool_dslide=knob):
             y, arg, dx = torch.empty_like(x0), torch.empty(x0.shape, dtype=torch.int32), torch.empty_like(x0)
             L.maxpool3d_fwd(x0, y, arg, B * C, geom)
             L.maxpool3d_bwd(G, arg, dx, B * C, geom)
             outs[knob] = (y, arg, dx)
-        finally:
-            assert L.c.segx_tune(15, 1) == 0
     assert torch.equal(torch.nan_to_num(outs[1][0], nan=-7.0), torch.nan_to_num(outs[0][0], nan=-7.0))
     assert torch.equal(outs[1][1], outs[0][1]) and torch.equal(outs[1][2], outs[0][2])
     xr = x0.clone().requires_grad_(True)
@@ -283,9 +278,7 @@ def test_conv3d_on_the_bf16x6_engine(backend, B, Cin, Cout, size, k, stride, wgr
     sticking out of the row on both sides, the first / last floats of a sample through the scalar form; OW = 12 / 20 / 28: the two-quad form whose
     second quad may lie on the next output row)."""
     L = backend.L
-    prev = L.set_engine('x6')
-    L.c.segx_tune(7, wgrad_all)          # 1: also the general (per-position decode) weight-gradient gather; 0: only rows of 8 consecutive floats (OW % 8 == 0)
-    try:
+    with L.tuned(engine=L.ENGINES['x6'], conv_x6_wgrad_all=wgrad_all):          # 1: also the general (per-position decode) weight-gradient gather; 0: only rows of 8 consecutive floats (OW % 8 == 0)
         L.x6_launches()
         dgrad = stride == (1, 1, 1)                      # the product differentiates strided convolutions w.r.t. x only for the 3-channel stem
         x = rnd(B, Cin, *size, seed=61).requires_grad_(dgrad)
@@ -300,9 +293,6 @@ def test_conv3d_on_the_bf16x6_engine(backend, B, Cin, Cout, size, k, stride, wgr
             close(x.grad, xr.grad, 1e-4)
         close(w.grad, wr.grad, 1e-4)
         assert L.x6_launches() >= 1                      # the engine really ran (forward; the backward passes where their operands are float4-legal)
-    finally:
-        L.c.segx_tune(7, 0)
-        L.set_engine(prev)
 
 
 # (B, Cin, Cout, size): W % 8 == 0 -> 4 x 4 x 8 tiles, W % 4 == 0 and D % 8 == 0 -> 8 x 4 x 4 tiles; Cout 24 / 72 / 136 / 200: the 64-, 128- and 192-row tiles with a
@@ -315,9 +305,7 @@ def test_conv3d_halo_kernel_forward_and_data_gradient(backend, B, Cin, Cout, siz
     """r06: the LDS-resident-halo form of the 3 x 3 x 3 stride-1 'same' convolutions (conv3d_halo.hip) through the C ABI -- forward with the pre-split filter bank
     of pack mode 0 and the data gradient (the same kernel on pack mode 1) against F.conv3d and its autograd; channel-slice operands (sample strides) included."""
     L = backend.L
-    prev = L.set_engine('x6')
-    assert L.c.segx_tune(17, 1) == 0
-    try:
+    with L.tuned(engine=L.ENGINES['x6'], conv_halo_min_tiles=1):
         D, H, W = size
         geom = (Cin, D, H, W, D, H, W, 3, 3, 3, 1, 1, 1, 1, 1, 1)
         assert L.conv3d_halo_ok(B, Cout, geom)
@@ -339,9 +327,6 @@ def test_conv3d_halo_kernel_forward_and_data_gradient(backend, B, Cin, Cout, siz
         dx = torch.empty(B, Cin, D, H, W)
         L.conv3d_halo_fwd(G, L.conv3d_halo_pack(w, Cin, Cout, 1), dx, B, Cin, g2, mtile=0)
         close(dx, xr.grad, 1e-5)
-    finally:
-        assert L.c.segx_tune(17, 256) == 0
-        L.set_engine(prev)
 
 
 # Cout 40 / 136: the 4-wave (128-row) form with a partial tile / two tiles; Cout 192 / 200: the 6-wave (192-row) form (+ a second, mostly empty tile); Cin 8 / 16 / 24;
@@ -352,9 +337,7 @@ def test_conv3d_halo_weight_gradient(backend, B, Cin, Cout, size):
     """r06: dW of the 3 x 3 x 3 stride-1 'same' convolutions with the halo resident as three x-shifted windows (conv3d_halo.hip), K-split over workgroups + deterministic
     slab reduction, against autograd's weight gradient of F.conv3d; X read as a channel slice of a wider tensor (x_bs)."""
     L = backend.L
-    prev = L.set_engine('x6')
-    assert L.c.segx_tune(17, 1) == 0
-    try:
+    with L.tuned(engine=L.ENGINES['x6'], conv_halo_min_tiles=1):
         D, H, W = size
         geom = (Cin, D, H, W, D, H, W, 3, 3, 3, 1, 1, 1, 1, 1, 1)
         assert L.conv3d_halo_wgrad_ok(B, Cout, geom)
@@ -370,19 +353,16 @@ def test_conv3d_halo_weight_gradient(backend, B, Cin, Cout, size):
         dw2 = torch.empty_like(w)
         L.conv3d_halo_wgrad(dy, xw[:, 8:], dw2, B, Cout, geom, x_bs=(Cin + 8) * D * H * W)
         assert torch.equal(dw, dw2)                                   # deterministic: fixed split order
-    finally:
-        assert L.c.segx_tune(17, 256) == 0
-        L.set_engine(prev)
 
 
 def test_conv3d_same_takes_the_halo_kernel_where_it_applies(backend):
     """SF.conv3d_same / SF.conv3d_slices route eligible layers (knob 16 on, >= knob 17 tiles) through the halo kernel -- same results as with the knob off."""
     L = backend.L
-    prev = L.set_engine('x6')
     outs = {}
-    try:
+    held = L.c.segx_tune_get(Knob.CONV_HALO)
+    with L.tuned(engine=L.ENGINES['x6'], conv_halo_min_tiles=1, conv_halo=1):    # conv_halo is named here so that the block puts it back
         for halo in (1, 0):
-            assert L.c.segx_tune(16, halo) == 0 and L.c.segx_tune(17, 1) == 0
+            L.tune(Knob.CONV_HALO, halo)
             x = rnd(1, 24, 4, 8, 8, seed=91).requires_grad_(True)
             w1, w2 = (rnd(16, 8, 3, 3, 3, seed=92) * 0.2).requires_grad_(True), (rnd(24, 16, 3, 3, 3, seed=93) * 0.2).requires_grad_(True)
             calls = []
@@ -400,9 +380,7 @@ def test_conv3d_same_takes_the_halo_kernel_where_it_applies(backend):
             outs[halo] = (y1.detach(), y3.detach(), x.grad.clone(), w1.grad.clone(), w2.grad.clone())
         for a, b in zip(outs[1], outs[0]):
             close(a, b, 2e-5)
-    finally:
-        assert L.c.segx_tune(16, 1) == 0 and L.c.segx_tune(17, 256) == 0
-        L.set_engine(prev)
+    assert L.c.segx_tune_get(Knob.CONV_HALO) == held == 1            # the default, and what the test leaves behind
 
 
 @pytest.mark.parametrize('engine', ['f32', 'x6'])

@@ -146,10 +146,8 @@ def test_gemm_skinny_weight_gradient_streams(backend, nb, M, N, K):
     ref = 0.25 * torch.einsum('xymk,xynk->mn', A.double(), B.double()).cpu() + bias.double().cpu()[:, None]
     args = (M, N, K, (nb[1] * M * K, M * K, K, 1), (nb[1] * N * K, N * K, K, 1), (0, 0, N))
     out = {}
-    assert L.c.segx_tune(9, 8) == 0
-    try:
-        for knob in (1, 0):
-            assert L.c.segx_tune(18, knob) == 0
+    for knob in (1, 0):
+        with L.tuned(ws_grid=8, skinny_nt=knob):
             d = segx.GemmDesc()
             d.M, d.N, d.K, d.nb0, d.nb1 = M, N, K, nb[0], nb[1]
             d.a_b0, d.a_b1, d.a_m, d.a_k = args[3]; d.b_b0, d.b_b1, d.b_n, d.b_k = args[4]
@@ -161,8 +159,6 @@ def test_gemm_skinny_weight_gradient_streams(backend, nb, M, N, K):
             L.gemm(A, B, C, *args, nb=nb, alpha=0.25, bias=bias, bias_mode=segx.BIAS_M, splitk=0, batch_reduce=True)
             out[knob] = C.double().cpu()
             assert (out[knob] - ref).abs().max().item() < 2e-5 * max(1.0, ref.abs().max().item())
-    finally:
-        assert L.c.segx_tune(18, 1) == 0 and L.c.segx_tune(9, 256) == 0
     assert (out[1] - out[0]).abs().max().item() < 2e-5 * max(1.0, ref.abs().max().item())
     # a caller that names the tile for a product the kernel does not serve (K not a multiple of 64) quietly gets the planner's tile
     A2, B2 = A[..., :K - 4].contiguous(), B[..., :K - 4].contiguous()
@@ -329,18 +325,14 @@ def test_x6_split_early_schedule_gives_the_same_result(backend):
     """segx_tune knob 6, value 6: the split-early schedule of the 128 x 128 k-contiguous kernel (conversion arithmetic of the next tile dealt
     out between the matrix instructions of the current one) is a scheduling variant -- bit-identical results to the product schedule."""
     L = backend.L
-    prev = L.set_engine('x6')
-    try:
+    with L.tuned(engine=L.ENGINES['x6']):
         out = []
         for v in (0, 6, 7):
-            assert L.c.segx_tune(6, v) == 0
-            A, B, C = _x6_case(L, backend.dev, 200, 136, 104, True, True, nb=2, tile=segx.TILE_128x128, seed=11)
+            with L.tuned(x6_variant=v):
+                A, B, C = _x6_case(L, backend.dev, 200, 136, 104, True, True, nb=2, tile=segx.TILE_128x128, seed=11)
             out.append(C.clone())
         assert torch.equal(out[0], out[1]) and torch.equal(out[0], out[2])
         assert (out[0].double() - _ref(A, B)).abs().max().item() < 3e-6 * _ref(A, B).abs().max().item()
-    finally:
-        L.c.segx_tune(6, 0)
-        L.set_engine(prev)
 
 
 @pytest.mark.parametrize('engine,tile', [('x6', segx.TILE_128x128), ('x6', segx.TILE_64x64), ('x6', segx.TILE_256x128), ('x6', segx.TILE_WS128x256), ('f32', segx.TILE_128x128)])
@@ -349,20 +341,15 @@ def test_tile_walk_order_gives_the_same_result(backend, engine, tile):
     an XCD's run (the tiles sharing a B column-panel next to each other) instead of N fastest -- a different ORDER of the same tiles: bit-identical results, on the
     4-wave kernels (tile_coord) and on the persistent wave-specialised ones (ws_item_coord), with ragged edges, a batch and split-K slabs."""
     L = backend.L
-    prev = L.set_engine(engine)
-    try:
-        assert L.c.segx_tune_get(19) == 1                                   # the default
-        if tile in (segx.TILE_256x128, segx.TILE_WS128x256):
-            assert L.c.segx_tune(9, 8) == 0                                 # 8 persistent workgroups: several rounds of items
+    grid = dict(ws_grid=8) if tile in (segx.TILE_256x128, segx.TILE_WS128x256) else {}      # 8 persistent workgroups: several rounds of items
+    with L.tuned(engine=L.ENGINES[engine], **grid):
+        assert L.c.segx_tune_get(segx.Knob.TILE_WALK) == 1                  # the default
         out = []
         for v in (1, 0):
-            assert L.c.segx_tune(19, v) == 0
-            A, B, C = _x6_case(L, backend.dev, 300, 1100, 64, True, False, nb=2, sk=2, tile=tile, seed=19)
+            with L.tuned(tile_walk=v):
+                A, B, C = _x6_case(L, backend.dev, 300, 1100, 64, True, False, nb=2, sk=2, tile=tile, seed=19)
             out.append(C.clone())
-        assert L.c.segx_tune(19, 2) == -1                                   # an unknown setting is an error
-    finally:
-        L.c.segx_tune(19, 1); L.c.segx_tune(9, 256)
-        L.set_engine(prev)
+        assert L.c.segx_tune(segx.Knob.TILE_WALK, 2) == -1                  # an unknown setting is an error
     assert torch.equal(out[0], out[1])
     ref = _ref(A, B)
     assert (out[0].double() - ref).abs().max().item() < 3e-6 * ref.abs().max().item()
@@ -377,17 +364,12 @@ def test_x6_wave_specialised_persistent_stream(backend, tile, M, N, K, akc, bkc,
     side is a row-contiguous operand): results must equal the 4-wave bf16x6 kernel bit for bit (same products,
     same order per accumulator) and fp64 to fp32 rounding."""
     L = backend.L
-    prev = L.set_engine('x6')
-    try:
-        assert L.c.segx_tune(9, 8) == 0
+    with L.tuned(engine=L.ENGINES['x6'], ws_grid=8):
         L.x6_launches()
         bias = torch.randn(N, generator=torch.Generator(device='cpu').manual_seed(2), device='cpu').to(backend.dev)
         A, B, C = _x6_case(L, backend.dev, M, N, K, akc, bkc, nb=nb, sk=sk, tile=tile, alpha=0.25, bias=bias, bias_mode=segx.BIAS_N, seed=5)
         assert L.x6_launches() == 1
         _, _, C0 = _x6_case(L, backend.dev, M, N, K, akc, bkc, nb=nb, sk=sk, tile=segx.TILE_128x128, alpha=0.25, bias=bias, bias_mode=segx.BIAS_N, seed=5)
-    finally:
-        L.c.segx_tune(9, 256)
-        L.set_engine(prev)
     ref = 0.25 * _ref(A, B) + bias.double()[None, None, :]
     assert (C.double() - ref).abs().max().item() < 3e-6 * max(1.0, ref.abs().max().item())
     assert torch.equal(C, C0)
@@ -430,9 +412,7 @@ def test_x6_presplit_b_operand_gives_identical_results(backend, tile, M, N, K, a
     splitting B in registers -- the LDS image is the same, so the results must agree bit for bit; ragged N (clamped rows), batches with their own
     or a shared B, split-K slabs, both layouts of A and of the fp32 B the planes are made from."""
     L = backend.L
-    prev = L.set_engine('x6')
-    try:
-        assert L.c.segx_tune(9, 8) == 0
+    with L.tuned(engine=L.ENGINES['x6'], ws_grid=8):
         g = torch.Generator(device='cpu').manual_seed(M + N + K)
         A = torch.randn(nb, M, K, generator=g, device='cpu').to(backend.dev)
         B = (torch.randn(1 if shared else nb, N, K, generator=g, device='cpu') * 0.3).to(backend.dev)
@@ -449,9 +429,6 @@ def test_x6_presplit_b_operand_gives_identical_results(backend, tile, M, N, K, a
             L.gemm(Am, Bm, C, M, N, K, a_str, b_str, (0, M * N, N), nb=(1, nb), splitk=sk, workspace=ws, tile=tile, alpha=0.5, b_planes=planes)
             assert L.x6_launches() == 1
             out.append(C)
-    finally:
-        L.c.segx_tune(9, 256)
-        L.set_engine(prev)
     ref = 0.5 * _ref(A, B.expand(nb, N, K))
     assert (out[0].double() - ref).abs().max().item() < 3e-6 * max(1.0, ref.abs().max().item())
     assert torch.equal(out[0], out[1])
@@ -465,9 +442,7 @@ def test_x6ws_matches_fp64_with_wide_ranging_rows(backend, tile, M, N, K, akc, b
     alpha and bias: error against fp64 at fp32-rounding level, measured per output element against sum |a||b| (a global bound would hide a small
     row computed badly) -- the three-way bf16 split is elementwise fp32-equivalent whatever the operand range."""
     L = backend.L
-    prev = L.set_engine('x6')
-    try:
-        assert L.c.segx_tune(9, 8) == 0
+    with L.tuned(engine=L.ENGINES['x6'], ws_grid=8):
         g = torch.Generator(device='cpu').manual_seed(M + 2 * N + K)
         A = torch.randn(nb, M, K, generator=g, device='cpu') * torch.logspace(-9, 6, M, device='cpu')[None, :, None]
         B = torch.randn(nb, N, K, generator=g, device='cpu') * torch.logspace(3, -6, N, device='cpu')[None, :, None]
@@ -483,9 +458,6 @@ def test_x6ws_matches_fp64_with_wide_ranging_rows(backend, tile, M, N, K, akc, b
         L.gemm(Am, Bm, C, M, N, K, a_str, b_str, (0, M * N, N), nb=(1, nb), splitk=sk, workspace=ws, tile=tile, alpha=0.5, bias=bias, bias_mode=segx.BIAS_N)
         assert L.x6_launches() == 1
         C = C.cpu().double()
-    finally:
-        L.c.segx_tune(9, 256)
-        L.set_engine(prev)
     ref = 0.5 * _ref(A, B) + bias.cpu().double()[None, None, :]
     mag = 0.5 * (A.double().abs() @ B.double().abs().transpose(-1, -2)) + bias.cpu().double().abs()[None, None, :]     # sum |a||b|: the scale of the rounding
     e6 = ((C - ref).abs() / mag).max().item()

@@ -1,7 +1,7 @@
 """Where the time of the short-contraction attention GEMMs goes (a measured statement of the bound): the 4-wave bf16x6 kernel on the
 K = 256 P.V shapes of cfg2 / cfg4 / cfg5 and, for contrast, a long contraction -- product schedule against the ablations of a -DSEGX_BENCH build (knob 6: 2 = no split
 arithmetic, 3 = no LDS stores, 4 = no global loads after the first k-tile, 5 = matrix instructions + fragment reads + epilogue only), random and all-zero operands.
-GPU box:  python tools/build_variant.py bench gemm.hip -DSEGX_BENCH && python tools/attn_bound.py"""
+GPU box:  python tools/build_variant.py bench gemm.hip,tune.hip -DSEGX_BENCH && python tools/attn_bound.py"""
 import glob, os, sys, statistics, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -40,9 +40,9 @@ for name, M, N, K, nb in SHAPES:
         C = torch.empty(nb, M, N, device=dev)
         row = '%s %-6s' % (name, data)
         for var in ((0, 2, 3, 4, 5) if bench_build else (0,)):
-            if L.c.segx_tune(6, var) != 0:
+            if L.c.segx_tune(segx.Knob.X6_VARIANT, var) != 0:
                 continue
             t = timed(lambda: L.gemm(A, B, C, M, N, K, (M * K, 0, K, 1), (N * K, 0, K, 1), (M * N, 0, N), nb=(nb, 1), tile=segx.TILE_128x128))
             row += ' | %s %6.3f ms %6.1f TF' % (NAMES[var], t, flops / t / 1e9)
-        L.c.segx_tune(6, 0)
+        L.c.segx_tune(segx.Knob.X6_VARIANT, 0)
         print(row, flush=True)

@@ -9,7 +9,7 @@ name, src, flags = sys.argv[1], sys.argv[2], sys.argv[3:]
 B.build()                                                                     # the product objects (segtran_amd/lib/*.o)
 out = os.path.join(ROOT, 'tools', 'variants')
 os.makedirs(out, exist_ok=True)
-srcs = src.split(',')                                                         # several sources: gemm.hip,fpn.hip (segx_tune lives in fpn.hip: -DSEGX_BENCH must reach it too)
+srcs = src.split(',')                                                         # several sources: gemm.hip,tune.hip (segx_tune lives in tune.hip: -DSEGX_BENCH must reach it too)
 objs = []
 for one in srcs:
     obj = os.path.join(out, '%s_%s.o' % (os.path.basename(one), name))

@@ -33,7 +33,7 @@ def main():
     which = sys.argv[1] if len(sys.argv) > 1 else 'all'
     B = 4
     g = torch.Generator(device='cpu').manual_seed(0)
-    L.c.segx_tune(17, 1)
+    L.c.segx_tune(segx.Knob.CONV_HALO_MIN_TILES, 1)
     for cfg in (['cfg4', 'cfg5'] if which == 'all' else [which]):
         for name, ci, co in LAYERS:
             D, H, W = SIZES[cfg][STAGE[name[0]]]
@@ -63,7 +63,7 @@ def main():
                 else:
                     line += ' | halo: not served'
                 print(line, flush=True)
-    L.c.segx_tune(17, 256)
+    L.c.segx_tune(segx.Knob.CONV_HALO_MIN_TILES, 256)
 
 
 def wgrad():
@@ -71,7 +71,7 @@ def wgrad():
     which = sys.argv[2] if len(sys.argv) > 2 else 'all'
     B = 4
     g = torch.Generator(device='cpu').manual_seed(0)
-    L.c.segx_tune(17, 1)
+    L.c.segx_tune(segx.Knob.CONV_HALO_MIN_TILES, 1)
     for cfg in (['cfg4', 'cfg5'] if which == 'all' else [which]):
         for name, Cin, Cout in LAYERS:
             D, H, W = SIZES[cfg][STAGE[name[0]]]
@@ -99,7 +99,7 @@ def wgrad():
             else:
                 line += ' | halo: not served'
             print(line, flush=True)
-    L.c.segx_tune(17, 256)
+    L.c.segx_tune(segx.Knob.CONV_HALO_MIN_TILES, 256)
 
 
 if __name__ == '__main__':

@@ -6,7 +6,7 @@ from segtran_amd import segx
 kind, Cin, Cout, D, H, W = sys.argv[1], *[int(v) for v in sys.argv[2:7]]
 reps = int(sys.argv[7]) if len(sys.argv) > 7 else 3
 dev = torch.device('cuda', 0)
-L = segx.lib(); L.set_engine('x6'); L.c.segx_tune(17, 1)
+L = segx.lib(); L.set_engine('x6'); L.c.segx_tune(segx.Knob.CONV_HALO_MIN_TILES, 1)
 B = 4
 g = torch.Generator(device='cpu').manual_seed(0)
 geom = (Cin, D, H, W, D, H, W, 3, 3, 3, 1, 1, 1, 1, 1, 1)

@@ -55,9 +55,9 @@ if len(sys.argv) > 2 and sys.argv[2] == 'variants':
     VN = {0: 'product', 1: 'setprio', 2: 'no split math', 3: 'no LDS stores', 4: 'no global loads', 5: 'MFMA + frag reads only'}
     for sh in (MAIN[0], MAIN[8], MAIN[9], MAIN[6]):
         for v in range(6):
-            L.c.segx_tune(6, v)
+            L.c.segx_tune(segx.Knob.X6_VARIANT, v)
             run('%s [%s]' % (sh[0][:14], VN[v]), *sh[1:7], nb=sh[7], engine='x6', tile=1)
-        L.c.segx_tune(6, 0)
+        L.c.segx_tune(segx.Knob.X6_VARIANT, 0)
     for sh in MAIN[:10] + [('expand 112->672', 672, 4096, 112, True, False, 1, 6)]:
         for tile in (1, 6, 5, 2):
             run(sh[0], *sh[1:7], nb=sh[7], engine='x6', tile=tile)

@@ -10,7 +10,7 @@ for (planes, d, h, w, D, H, W, with_base) in [(4096, 24, 56, 56, 48, 56, 56, Fal
     base = torch.randn(planes, D, H, W, device=dev) if with_base else None
     byt = 4.0 * (x.numel() + out.numel() * (2 if with_base else 1))
     for var in (1, 2):
-        L.c.segx_tune(1, var)
+        L.c.segx_tune(segx.Knob.INTERP_VARIANT, var)
         for _ in range(2): L.interp_fwd(x, base, out, planes, d, h, w, D, H, W)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -18,4 +18,4 @@ for (planes, d, h, w, D, H, W, with_base) in [(4096, 24, 56, 56, 48, 56, 56, Fal
         e1.record(); torch.cuda.synchronize()
         ms = e0.elapsed_time(e1) / 5
         print('planes %5d %s->%s base=%d variant %d: %7.3f ms  %6.0f GB/s (%.2f GB)' % (planes, (d, h, w), (D, H, W), with_base, var, ms, byt / ms / 1e6, byt / 1e9))
-L.c.segx_tune(1, 0)
+L.c.segx_tune(segx.Knob.INTERP_VARIANT, 0)

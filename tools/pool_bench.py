@@ -35,7 +35,7 @@ for name, C, (D, H, W) in CASES:
     nbytes = 3 * x.numel() * 4
     res, ref = {}, None
     for policy in (2, 0, 1):
-        assert L.c.segx_tune(14, policy) == 0
+        assert L.c.segx_tune(segx.Knob.POOL_SLAB, policy) == 0
         y, arg, dx = torch.empty_like(x), torch.empty(x.shape, dtype=torch.int32, device=dev), torch.empty_like(x)
         tf = timed(lambda: L.maxpool3d_fwd(x, y, arg, B * C, geom))
         tb = timed(lambda: L.maxpool3d_bwd(dy, arg, dx, B * C, geom))
@@ -43,7 +43,7 @@ for name, C, (D, H, W) in CASES:
             ref = (y.clone(), arg.clone(), dx.clone())
         same = torch.equal(y, ref[0]) and torch.equal(arg, ref[1]) and torch.equal(dx, ref[2])
         res[policy] = (tf, tb, same)
-    L.c.segx_tune(14, 0)
+    L.c.segx_tune(segx.Knob.POOL_SLAB, 0)
     print('%-14s C=%4d %2dx%2dx%2d  %6.1f MB/pass | ' % (name, C, D, H, W, nbytes / 3e6) +
           ' | '.join('policy %d: fwd %6.1f us %4.2f TB/s, bwd %6.1f us %4.2f TB/s%s' % (p, r[0] * 1e3, nbytes / r[0] / 1e9, r[1] * 1e3, nbytes / r[1] / 1e9, '' if r[2] else ' MISMATCH')
                      for p, r in res.items()), flush=True)

@@ -15,7 +15,7 @@ for M, N, K, nb in SHAPES:
     A = torch.randn(nb, M, K, device=dev); B = torch.randn(nb, N, K, device=dev); C = torch.empty(M, N, device=dev)
     t = {}
     for knob in (0, 1):
-        assert L.c.segx_tune(18, knob) == 0
+        assert L.c.segx_tune(segx.Knob.SKINNY_NT, knob) == 0
         for _ in range(3):
             L.gemm(A, B, C, M, N, K, (M * K, 0, K, 1), (N * K, 0, K, 1), (0, 0, N), nb=(nb, 1), splitk=0, batch_reduce=True)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -29,4 +29,4 @@ for M, N, K, nb in SHAPES:
     err = (C - ref).abs().max().item() / max(ref.abs().max().item(), 1e-20)
     by = 4.0 * (M + N) * K * nb
     print('%-28s %10.1f %10.1f %8.2f %8.2f   rel diff %.1e' % ((M, N, K, nb), t[0], t[1], by / t[0] / 1e6, by / t[1] / 1e6, err))
-L.c.segx_tune(18, 1)
+L.c.segx_tune(segx.Knob.SKINNY_NT, 1)

@@ -78,12 +78,12 @@ for sh in SHAPES[which]:
     times = {arm: [] for arm in ARMS}
     for arm in ARMS:                                       # warm-up, and which arms this shape supports
         L = LIBS[arm[0]]
-        L.c.segx_tune(6, arm[2])
+        L.c.segx_tune(segx.Knob.X6_VARIANT, arm[2])
         try:
             L.gemm(*args, tile=arm[1], **kw)
         except RuntimeError as e:
             times.pop(arm); print('  skip', arm, str(e)[:80])
-        L.c.segx_tune(6, 0)
+        L.c.segx_tune(segx.Knob.X6_VARIANT, 0)
     torch.cuda.synchronize()
     if which == 'main':                                    # every library computes the same values (the split variants are exact re-expressions)
         ref = None
@@ -94,14 +94,14 @@ for sh in SHAPES[which]:
     for r in range(rounds):
         for arm in list(times):
             L = LIBS[arm[0]]
-            L.c.segx_tune(6, arm[2])
+            L.c.segx_tune(segx.Knob.X6_VARIANT, arm[2])
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for _ in range(reps):
                 L.gemm(*args, tile=arm[1], **kw)
             e1.record(); torch.cuda.synchronize()
             times[arm].append(e0.elapsed_time(e1) / reps)
-            L.c.segx_tune(6, 0)
+            L.c.segx_tune(segx.Knob.X6_VARIANT, 0)
     fl = 2.0 * M * N * K * nb
     print('%-26s M=%6d N=%6d K=%6d nb=%2d sk=%d %s%s' % (name, M, N, K, nb, sk, 'NT'[0] if akc else 'T', 'T' if bkc else 'N'), flush=True)
     for arm, ts in times.items():
