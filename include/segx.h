@@ -34,7 +34,10 @@ int segx_last_error(char* buf, int buflen);
  * (segtran2d.py:245,287,304,427; segtran3d.py:300,348,367,490; efficientnet/model.py:96,113,280;
  * aj_i3d.py:92 for 1x1x1 kernels) and all of their backward GEMMs.
  * ------------------------------------------------------------------------------------------- */
-enum { SEGX_EPI_NONE = 0, SEGX_EPI_GELU = 1 /* aux = pre-activation, C = dropout(gelu(.)), :244-245 */ };
+enum { SEGX_EPI_NONE = 0, SEGX_EPI_GELU = 1 /* aux = pre-activation, C = dropout(gelu(.)), :244-245 */,
+       SEGX_EPI_SWISH = 2 /* C = swish(alpha * A B^T + bias): a pointwise convolution whose BatchNorm was folded into its weights and bias (inference,
+                             efficientnet/model.py:96-98, 280-282).  No aux, no dropout, no resid / gmax / split-K / batch_reduce; built for the operand layout of a
+                             pointwise convolution's forward (A k-contiguous, B row-contiguous) on the 128x128, 64x128 and 64x64 tiles of both engines */ };
 enum { SEGX_BIAS_NONE = 0, SEGX_BIAS_N = 1 /* bias[n] */, SEGX_BIAS_M = 2 /* bias[m] */ };
 /* tile engines (segx_tune knob 4): SEGX_ENGINE_F32 = v_mfma_f32_32x32x2_f32 on fp32 operands (bit-for-bit a k-ordered fmaf chain);
  * SEGX_ENGINE_BF16X6 = fp32 operands split in registers into three bf16 planes, six v_mfma_f32_32x32x16_bf16 per block (fp32-equivalent:
@@ -294,6 +297,12 @@ int segx_se_bwd2(const float* dWb, const float* Wproj, const float* dgate, const
  * padding N6, efficientnet/utils.py:248-275): Y[b,c,oy,ox] = sum w[c,ky,kx] X[b,c,oy*s+ky-pad_t, ox*s+kx-pad_l] */
 int segx_dwconv2d_fwd(const float* X, const float* W, float* Y, int B, int C, int H, int Wd, int OH, int OW, int k, int stride,
                       int pad_t, int pad_l, void* stream);
+/* Inference form with BatchNorm folded into W and bias (efficientnet/model.py:100-106): Y = swish(depthwise(X, W) + bias[c]) and the squeeze-excite pooling
+ * partials psum[B*C][nch] of Y (nch = segx_dwconv2d_pool_chunks(OH, OW), the chunk layout segx_se_fwd2 reads) from ONE pass: no BatchNorm launch, no pooling pass.
+ * Forward only.  act: 0 = none, 1 = swish. */
+int64_t segx_dwconv2d_pool_chunks(int OH, int OW);
+int segx_dwconv2d_bias_act_pool(const float* X, const float* W, const float* bias, float* Y, float* psum, int B, int C, int H, int Wd, int OH, int OW,
+                                int k, int stride, int pad_t, int pad_l, int act, void* stream);
 int segx_dwconv2d_bwd_data(const float* dY, const float* W, float* dX, int B, int C, int H, int Wd, int OH, int OW, int k,
                            int stride, int pad_t, int pad_l, void* stream);
 /* partial weight gradients part[B * rows][C][k*k], rows = segx_dwconv2d_wgrad_rows(OH, OW) row strips per sample;
@@ -541,6 +550,9 @@ int segx_stem_s2d_input(const float* X, float* Y, int B, int Cb, int H, int W, i
  * (segx_gemm_f32 with batch_reduce; SEGX_TILE_SKINNY_NT).  Cin = 3, K = 3, stride 1 or 2 only. */
 int segx_conv2d_stem_fwd(const float* X, const float* W, float* Y, int B, int Cin, int Cout, int H, int Wd, int OH, int OW, int K, int stride, int pt, int pl,
                          void* stream);
+/* the same forward with the stem's BatchNorm folded into W and bias (inference): Y = act(conv(X, W) + bias[co]), act: 0 = none, 1 = swish */
+int segx_conv2d_stem_bias_act_fwd(const float* X, const float* W, const float* bias, float* Y, int B, int Cin, int Cout, int H, int Wd, int OH, int OW, int K,
+                                  int stride, int pt, int pl, int act, void* stream);
 int segx_conv2d_stem_im2col(const float* X, float* Xcol, int B, int Cin, int H, int Wd, int OH, int OW, int K, int stride, int pt, int pl, int rows, void* stream);
 /* foreground-token mask (get_mask, segtran2d.py:229-233 / segtran3d.py:266-270): out[b][cell] = (sum_c avgpool_{kd,kh,kw}(|x|) > 0) as 0/1 floats */
 /* r05: get_mask(in_bridge_to3(batch)) of segtran3d.py:420-425 without materialising the bridged image: X = the raw batch [B][Cb][H][W][D], Wb [C3][Cb] / bb [C3]

@@ -912,6 +912,119 @@ __global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(4) void dwconv_rows4_k
     for (int i = 0; i < DW4_TY; ++i)
         if (oy0 + i < OH) *reinterpret_cast<float4*>(y + (int64_t)(oy0 + i) * OW) = make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
 }
+// ---- inference: depthwise convolution + per-channel bias (BatchNorm folded into the filter and this bias) + swish + the squeeze-excite pooling partials, ONE pass
+// (efficientnet/model.py:100-106 in eval mode; replaces dwconv2d_fwd -> bn_act_fwd2<POOL>: the convolution's output is never written un-normalised and read back).
+// Chunk geometry (both forms, a function of the output size alone: segx_dwconv2d_pool_chunks): the plane is cut into tiles of DW4_TY rows x (4 << l) columns, l as dw4_grid;
+// chunk = tile index; psum[plane][chunk] = the sum of act(y) over the tile -- the [B*C][nch] layout se_hidden2_kernel adds up.  Each partial is a fixed-order sum of one
+// thread group (no atomics): deterministic.
+// float4 form (dwconv_rows4_kernel's walk, FLIP = false): a group of (1 << l) lanes owns a tile; the group's sum comes from an xor butterfly inside its lanes.
+template <int K, int ST, int PL>
+__global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(4) void dwconv_rows4_bias_act_pool_kernel(const float* __restrict__ X, const float* __restrict__ Wt, const float* __restrict__ bias,
+                                                           float* __restrict__ Y, float* __restrict__ psum, int C, int H, int W, int OH, int OW, int pt, int tiles_x, int tiles_y,
+                                                           int tpr_log2, int64_t ngroups, int act) {
+    constexpr int NV = Dw4<K, ST>::NV;
+    static_assert(PL <= 4 && 4 + 3 * ST + K - 1 - PL < 4 * NV, "window does not fit the loaded float4s");
+    const int64_t gid_raw = ((int64_t)xcd_block(blockIdx.x, gridDim.x) * 256 + threadIdx.x) >> tpr_log2;
+    const bool glive = gid_raw < ngroups;                     // a whole group is live or not (every lane stays for the butterfly)
+    const int64_t gid = glive ? gid_raw : ngroups - 1;
+    const int gpp = tiles_x * tiles_y;
+    const int64_t plane = gid / gpp;
+    const int rem = (int)(gid - plane * gpp), tyi = rem / tiles_x, txi = rem - tyi * tiles_x;
+    const int ox_raw = ((txi << tpr_log2) + (threadIdx.x & ((1 << tpr_log2) - 1))) * 4, oy0 = tyi * DW4_TY;
+    const bool live = glive && ox_raw < OW;
+    const int ox = ox_raw < OW ? ox_raw : OW - 4;             // dead lanes recompute the last quad (loads stay inside the plane), store nothing, add nothing
+    const int c = (int)(plane % C);
+    const float* x = X + plane * H * W;
+    float w[K * K];
+#pragma unroll
+    for (int i = 0; i < K * K; ++i) w[i] = Wt[(int64_t)c * K * K + i];
+    float acc[DW4_TY][4];
+#pragma unroll
+    for (int i = 0; i < DW4_TY; ++i) { acc[i][0] = 0.f; acc[i][1] = 0.f; acc[i][2] = 0.f; acc[i][3] = 0.f; }
+    int xo[NV]; bool okv[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) { const int col = ox * ST - 4 + 4 * i; okv[i] = col >= 0 && col < W; xo[i] = min(max(col, 0), W - 4); }
+    const int iy0 = oy0 * ST - pt;
+    constexpr int NR = (DW4_TY - 1) * ST + K;
+    float e[DW4_AHEAD + 1][4 * NV];
+#pragma unroll
+    for (int r = 0; r < DW4_AHEAD && r < NR; ++r)
+        dw4_load_row<NV>(e[r], x + (int64_t)min(max(iy0 + r, 0), H - 1) * W, xo, okv, iy0 + r >= 0 && iy0 + r < H);
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        if (r + DW4_AHEAD < NR) {
+            const int iy = iy0 + r + DW4_AHEAD;
+            dw4_load_row<NV>(e[(r + DW4_AHEAD) % (DW4_AHEAD + 1)], x + (int64_t)min(max(iy, 0), H - 1) * W, xo, okv, iy >= 0 && iy < H);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int ky = 0; ky < K; ++ky) {
+            if ((r - ky) < 0 || (r - ky) % ST != 0 || (r - ky) / ST >= DW4_TY) continue;     // compile-time
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int kx = 0; kx < K; ++kx)
+                    acc[(r - ky) / ST][j] += w[ky * K + kx] * e[r % (DW4_AHEAD + 1)][4 + j * ST + kx - PL];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) SEGX_PIN(acc[(r - ky) / ST][j]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    const float bc = bias[c];
+    float* y = Y + plane * OH * OW + ox;
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < DW4_TY; ++i) {
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { v[j] = acc[i][j] + bc; if (act == ACT_SWISH) v[j] = swish_fwd(v[j]); }
+        if (live && oy0 + i < OH) {
+            *reinterpret_cast<float4*>(y + (int64_t)(oy0 + i) * OW) = make_float4(v[0], v[1], v[2], v[3]);
+            sum += (v[0] + v[1]) + (v[2] + v[3]);
+        }
+    }
+    for (int o = 1; o < (1 << tpr_log2); o <<= 1) sum += __shfl_xor(sum, o);          // the group's lanes are consecutive, aligned to its size (<= 64): the butterfly stays inside it
+    if (glive && psum && (threadIdx.x & ((1 << tpr_log2) - 1)) == 0) psum[plane * gpp + rem] = sum;
+}
+// any other shape (rows that are no float4 multiples, unaligned planes, other pads): one workgroup per (tile, plane) of the SAME tile geometry; the 256 threads are
+// (256 / columns) row groups x the tile's columns, a thread computes DW4_TY / row groups outputs of its column; the tile's sum through block_sum.
+template <int K, int ST>
+__global__ __launch_bounds__(256) void dwconv_bias_act_pool_kernel(const float* __restrict__ X, const float* __restrict__ Wt, const float* __restrict__ bias, float* __restrict__ Y,
+                                                                   float* __restrict__ psum, int C, int H, int W, int OH, int OW, int pt, int pl, int tiles_x, int txw_log2, int act) {
+    __shared__ float red[4];
+    const int bc = blockIdx.y, c = bc % C, nch = gridDim.x;
+    const int tyi = blockIdx.x / tiles_x, txi = blockIdx.x - tyi * tiles_x;
+    const int txw = 1 << txw_log2, nrg = 256 >> txw_log2;     // txw in {32, 64, 128, 256} columns; nrg row groups of DW4_TY / nrg rows each
+    const int ox = txi * txw + (threadIdx.x & (txw - 1)), rg = threadIdx.x >> txw_log2, rpg = DW4_TY / nrg;
+    const float* x = X + (int64_t)bc * H * W;
+    float w[K * K];
+#pragma unroll
+    for (int i = 0; i < K * K; ++i) w[i] = Wt[(int64_t)c * K * K + i];
+    const float bv = bias[c];
+    float sum = 0.f;
+    for (int i = 0; i < rpg; ++i) {
+        const int oy = tyi * DW4_TY + rg * rpg + i;
+        if (ox < OW && oy < OH) {
+            float a = 0.f;
+#pragma unroll
+            for (int ky = 0; ky < K; ++ky) {
+                const int iy = oy * ST + ky - pt;
+#pragma unroll
+                for (int kx = 0; kx < K; ++kx) {
+                    const int ix = ox * ST + kx - pl;
+                    const float q = x[(int64_t)min(max(iy, 0), H - 1) * W + min(max(ix, 0), W - 1)];
+                    a += w[ky * K + kx] * ((iy >= 0 && iy < H && ix >= 0 && ix < W) ? q : 0.f);
+                }
+            }
+            a += bv;
+            if (act == ACT_SWISH) a = swish_fwd(a);
+            Y[((int64_t)bc * OH + oy) * OW + ox] = a;
+            sum += a;
+        }
+    }
+    sum = block_sum<4>(sum, red);
+    if (psum && threadIdx.x == 0) psum[(int64_t)bc * nch + blockIdx.x] = sum;
+}
 // weight gradient, float4 variant: ONE WAVE per (plane, strip); it walks every strips-th tile of the plane ((64 >> tpr_log2)
 // row groups x 4 rows x (4 << tpr_log2) columns), then reduces its K*K sums with wave shuffles -- no LDS, no barrier.
 constexpr int DWG_TY = 4;
@@ -1751,6 +1864,38 @@ extern "C" int segx_dwconv2d_fwd(const float* X, const float* W, float* Y, int B
     dim3 grid(g.tiles_x * g.tiles_y, B * C);
     SEGX_DW_ROWS_DISPATCH(false, X, W, Y, C, H, Wd, OH, OW, pad_t, pad_l, g.tiles_x, g.txw_log2);
     return check_launch("segx_dwconv2d_fwd");
+}
+// the tile geometry of the fused inference form: DW4_TY rows x (4 << l) columns, l as dw4_grid -- from the output size alone, so that the pooling chunk count does not
+// depend on which of the two kernels serves the call
+extern "C" int64_t segx_dwconv2d_pool_chunks(int OH, int OW) {
+    if (OH <= 0 || OW <= 0) return 0;
+    return (int64_t)dw4_grid(OW).tiles_x * ((OH + segx::DW4_TY - 1) / segx::DW4_TY);
+}
+extern "C" int segx_dwconv2d_bias_act_pool(const float* X, const float* W, const float* bias, float* Y, float* psum, int B, int C, int H, int Wd, int OH, int OW,
+                                           int k, int stride, int pad_t, int pad_l, int act, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(X && W && bias && Y && B > 0 && C > 0 && H > 0 && Wd > 0 && OH > 0 && OW > 0 && (int64_t)B * C <= 65535 && (act == 0 || act == 1) && pad_t >= 0 && pad_l >= 0,
+                              "segx_dwconv2d_bias_act_pool: bad args");
+    // every window starts inside the padded plane (the kernels clamp addresses and zero what lies outside)
+    SEGX_REQUIRE((int64_t)(OH - 1) * stride - pad_t < H && (int64_t)(OW - 1) * stride - pad_l < Wd, "segx_dwconv2d_bias_act_pool: output %d x %d does not fit input %d x %d", OH, OW, H, Wd);
+    const Dw4Grid g = dw4_grid(OW);
+    const int tiles_y = (OH + segx::DW4_TY - 1) / segx::DW4_TY, planes = B * C;
+    if (dw4_ok(X, Y, Wd, OW)) {
+        const int64_t ngroups = (int64_t)planes * g.tiles_x * tiles_y;
+        const int64_t nblocks = ((ngroups << g.tpr_log2) + 255) / 256;
+        if (nblocks <= 2147483647LL) {
+#define SEGX_DW4P(KK, SS, PP)                                                                                                                          \
+            if (k == KK && stride == SS && pad_l == PP) {                                                                                               \
+                hipLaunchKernelGGL((segx::dwconv_rows4_bias_act_pool_kernel<KK, SS, PP>), dim3((unsigned)nblocks), dim3(256), 0, stream, X, W, bias, Y, \
+                                   psum, C, H, Wd, OH, OW, pad_t, g.tiles_x, tiles_y, g.tpr_log2, ngroups, act);                                        \
+                return check_launch("segx_dwconv2d_bias_act_pool");                                                                                     \
+            }
+            SEGX_DW4P(3, 1, 1) SEGX_DW4P(5, 1, 2) SEGX_DW4P(3, 2, 0) SEGX_DW4P(3, 2, 1) SEGX_DW4P(5, 2, 1) SEGX_DW4P(5, 2, 2)
+#undef SEGX_DW4P
+        }
+    }
+    const dim3 grid(g.tiles_x * tiles_y, planes);
+    SEGX_DW_DISPATCH(segx::dwconv_bias_act_pool_kernel, X, W, bias, Y, psum, C, H, Wd, OH, OW, pad_t, pad_l, g.tiles_x, g.tpr_log2 + 2, act);
+    return check_launch("segx_dwconv2d_bias_act_pool");
 }
 extern "C" int segx_dwconv2d_bwd_data(const float* dY, const float* W, float* dX, int B, int C, int H, int Wd, int OH, int OW, int k, int stride,
                                       int pad_t, int pad_l, void* stream_) {

@@ -261,6 +261,8 @@ __device__ __forceinline__ float dropout_scale(uint64_t seed, uint64_t offset, u
     return keep_of(u, p, inv_keep);
 }
 
+// swish (efficientnet/utils.py:64-79) as the BatchNorm + activation kernels of backbone.hip compute it
+__device__ __forceinline__ float swish_fwd(float x) { return x * (1.0f / (1.0f + __expf(-x))); }
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 __device__ __forceinline__ float gelu_erf_grad(float x) {
     const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752440f));

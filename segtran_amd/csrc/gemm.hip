@@ -157,7 +157,7 @@ static int price(const TileInfo& c, int M, int N, int K, int nbatch, bool may_sp
 // runs on four of the eight waves there and measured 63 against 91 TFLOP/s)
 // nrc = number of row-contiguous operands (0..2): their loaders cost the 4-wave kernels 9 % / 34 % per k-tile (r03_f: 201 / 185 / 150 TFLOP/s for
 // NT / NN / TN at 24576 x 1792 x 1792), the wave-specialised ones 1 % / 5 % (220 / 218 / 198 incl. the slab reduction)
-static void plan6(int M, int N, int K, int nbatch, bool gelu, bool may_split, int splitk_fixed, bool ws_ok, int nrc, int* tile, int* splitk) {
+static void plan6(int M, int N, int K, int nbatch, bool gelu, bool may_split, int splitk_fixed, bool ws_ok, int nrc, int* tile, int* splitk) {   // (the fused swish: ws_ok = false)
     double best_t = -1.0;
     const float f4 = nrc == 0 ? 1.0f : nrc == 1 ? 1.09f : 1.34f, fws = nrc == 0 ? 1.0f : nrc == 1 ? 1.01f : 1.05f;
     for (const TileInfo6& c6 : kTiles6) {
@@ -182,11 +182,12 @@ static bool gemm_lean_ok(const segx_gemm_desc* d) {
 // a residual operand keeps the call on the 4-wave kernels: their epilogue reads it as 16-byte quads next to the 16-byte stores, the wave-specialised
 // kernels' 4-byte epilogue would read it scalar (r04_c: the 160 x 4096 x 960 x 6 dX GEMM 0.47 -> 0.76 ms/step with the residual on the 256 x 128 tile)
 static bool gemm_ws_ok(const segx_gemm_desc* d) { return !d->resid && gemm_lean_ok(d); }
-static void plan(int M, int N, int K, int nbatch, bool vec, bool may_split, int splitk_fixed, int* tile, int* splitk) {
+// skinny_ok = false: the 32-row tiles are not built for this call's epilogue (the fused swish)
+static void plan(int M, int N, int K, int nbatch, bool vec, bool may_split, int splitk_fixed, int* tile, int* splitk, bool skinny_ok = true) {
     const TileInfo* cand[3]; int nc = 0;
     if (!vec) cand[nc++] = &kTiles[0];
-    else if (N <= 48 && M > N) cand[nc++] = &tile_info(SEGX_TILE_128x32);
-    else if (M <= 48) cand[nc++] = &tile_info(SEGX_TILE_32x128);
+    else if (skinny_ok && N <= 48 && M > N) cand[nc++] = &tile_info(SEGX_TILE_128x32);
+    else if (skinny_ok && M <= 48) cand[nc++] = &tile_info(SEGX_TILE_32x128);
     else { cand[nc++] = &kTiles[0]; cand[nc++] = &kTiles[1]; cand[nc++] = &kTiles[2]; }
     double best_t = -1.0;
     for (int i = 0; i < nc; ++i) {
@@ -218,7 +219,7 @@ static int skinny_nt_splitk(const float* A, const float* B, const segx_gemm_desc
 
 static int gemm_plan_impl(const float* A, const float* B, const segx_gemm_desc* d, int* tile, int* splitk, bool use_table) {
     SEGX_REQUIRE(A && B && d && tile && splitk && d->M > 0 && d->N > 0 && d->K > 0 && d->nb0 > 0 && d->nb1 > 0, "segx_gemm_plan: bad args");
-    const bool plain = d->epilogue == SEGX_EPI_NONE;
+    const bool plain = d->epilogue == SEGX_EPI_NONE, swish = d->epilogue == SEGX_EPI_SWISH;
     int t = SEGX_TILE_128x128, sk = 1;
     const bool vec = gemm_vec_ok(A, B, d);
     if (const int ssk = skinny_nt_splitk(A, B, d)) { *tile = SEGX_TILE_SKINNY_NT; *splitk = ssk; return 0; }
@@ -232,8 +233,10 @@ static int gemm_plan_impl(const float* A, const float* B, const segx_gemm_desc* 
                 return 0;
             }
     }
-    if (x6_eligible(call_engine(d), d->M, d->N, vec) && (plain || d->a_k == 1)) plan6(d->M, d->N, d->K, d->nb0 * d->nb1, !plain, plain && !d->gmax, 0, gemm_ws_ok(d), (d->a_k != 1) + (d->b_k != 1), &t, &sk);
-    else plan(d->M, d->N, d->K, d->nb0 * d->nb1, vec && plain, plain && !d->gmax, 0, &t, &sk);
+    // the fused swish is built for the three four-wave tiles of either engine (no wave-specialised, no 32-row tile) and never splits
+    if (x6_eligible(call_engine(d), d->M, d->N, vec) && (plain || d->a_k == 1))
+        plan6(d->M, d->N, d->K, d->nb0 * d->nb1, !plain && !swish, plain && !d->gmax, 0, gemm_ws_ok(d) && !swish, (d->a_k != 1) + (d->b_k != 1), &t, &sk);
+    else plan(d->M, d->N, d->K, d->nb0 * d->nb1, vec && (plain || swish), plain && !d->gmax, 0, &t, &sk, !swish);
     *tile = t; *splitk = sk;
     return 0;
 }
@@ -268,7 +271,7 @@ static int gemm_route(const float* A, const float* B, const segx_gemm_desc* d, G
     r.epi = d->epilogue; r.sched = 0; r.splitk = d->splitk > 1 ? d->splitk : 1;
     r.ws_grid = kget(knobs().ws_grid); r.walk = kget(knobs().tile_walk) != 0;
     const int nbatch = d->nb0 * d->nb1;
-    const bool gelu = d->epilogue == SEGX_EPI_GELU, ws_forced = ws_tile_id(d->tile);
+    const bool gelu = d->epilogue == SEGX_EPI_GELU, swish = d->epilogue == SEGX_EPI_SWISH, ws_forced = ws_tile_id(d->tile);
     const int engine = call_engine(d);
     SEGX_REQUIRE(!ws_forced || engine == SEGX_ENGINE_BF16X6, "segx_gemm_f32: tile %d exists on the bf16x6 engine only", d->tile);
     int tile = d->tile;
@@ -285,9 +288,11 @@ static int gemm_route(const float* A, const float* B, const segx_gemm_desc* d, G
                     (tile == SEGX_TILE_AUTO || tile == SEGX_TILE_128x128 || tile == SEGX_TILE_64x128 || tile == SEGX_TILE_64x64 || ws_forced);
     if (tile == SEGX_TILE_AUTO) {                            // the caller chose the split factor (or 1): the tile is priced for that one
         int sk_unused = 1;
-        if (x6) plan6(d->M, d->N, d->K, nbatch, gelu, false, r.splitk, ws_ok, (!r.akc) + (!r.bkc), &tile, &sk_unused);
-        else plan(d->M, d->N, d->K, nbatch, r.vec && !gelu, false, r.splitk, &tile, &sk_unused);
+        if (x6) plan6(d->M, d->N, d->K, nbatch, gelu, false, r.splitk, ws_ok && !swish, (!r.akc) + (!r.bkc), &tile, &sk_unused);
+        else plan(d->M, d->N, d->K, nbatch, r.vec && !gelu, false, r.splitk, &tile, &sk_unused, !swish);
     }
+    // the fused swish (a folded pointwise convolution's forward) is built for the three four-wave tiles of either engine: any other tile a caller names takes the default one
+    if (swish && tile != SEGX_TILE_64x128 && tile != SEGX_TILE_64x64) tile = SEGX_TILE_128x128;
     if (ws_forced && !ws_ok) tile = SEGX_TILE_128x128;
     // the 96-row tiles (channel counts 272 / 160 / 192 / 672 / 960 of the backbone: 3 x 96 = 288 rows cover 272 where 3 x 128 compute 384) stage their 96-row
     // side with the k-contiguous loader only (the row-contiguous one deals 64 / 128 / 256 rows over a workgroup); no fused GELU
@@ -347,7 +352,13 @@ using Cfg128x256 = TileCfg<2, 2, 2, 4>; using Cfg64x256 = TileCfg<2, 2, 1, 4>; u
 template <class Cfg> static GemmLaunch f32_tile(const GemmRoute& r) {
     return built_for<Cfg>(by_layout(r, [](auto ak, auto bk) -> GemmKernel { return gemm_f32_kernel<Cfg, decltype(ak)::value, decltype(bk)::value, true, SEGX_EPI_NONE>; }));
 }
+// the fused swish: k-contiguous A, row-contiguous B (segx_gemm_f32 refuses other layouts)
+template <class Cfg> static GemmLaunch f32_swish_tile() { return built_for<Cfg>(gemm_f32_kernel<Cfg, true, false, true, SEGX_EPI_SWISH>); }
 static GemmLaunch f32_kernel(const GemmRoute& r) {
+    if (r.epi == SEGX_EPI_SWISH) {
+        if (!r.vec) return built_for<Cfg128>(gemm_f32_kernel<Cfg128, true, false, false, SEGX_EPI_SWISH>);
+        return r.tile == SEGX_TILE_64x64 ? f32_swish_tile<Cfg64>() : r.tile == SEGX_TILE_64x128 ? f32_swish_tile<Cfg64x128>() : f32_swish_tile<Cfg128>();
+    }
     if (r.epi == SEGX_EPI_GELU)
         return built_for<Cfg128>(by_flag(r.bkc, [&](auto bk) { return by_flag(r.vec, [](auto v) -> GemmKernel {
             return gemm_f32_kernel<Cfg128, true, decltype(bk)::value, decltype(v)::value, SEGX_EPI_GELU>; }); }));
@@ -370,6 +381,12 @@ template <bool LEAN, class Cfg, int W> static GemmLaunch x6_tile(const GemmRoute
 }
 template <bool LEAN> static GemmLaunch x6_kernel(const GemmRoute& r) {
     if (r.epi == SEGX_EPI_GELU) return built_for<Cfg128>(by_flag(r.bkc, [](auto bk) { return x6_form<LEAN, Cfg128, true, decltype(bk)::value, SEGX_EPI_GELU, 3>(); }));
+    if (r.epi == SEGX_EPI_SWISH)
+        switch (r.tile) {
+            case SEGX_TILE_64x64: return built_for<Cfg64>(x6_form<LEAN, Cfg64, true, false, SEGX_EPI_SWISH, 5>());
+            case SEGX_TILE_64x128: return built_for<Cfg64x128>(x6_form<LEAN, Cfg64x128, true, false, SEGX_EPI_SWISH, 4>());
+            default: return built_for<Cfg128>(x6_form<LEAN, Cfg128, true, false, SEGX_EPI_SWISH, 3>());
+        }
     switch (r.tile) {
         case SEGX_TILE_64x64: return x6_tile<LEAN, Cfg64, 5>(r);
         case SEGX_TILE_64x128: return x6_tile<LEAN, Cfg64x128, 4>(r);
@@ -465,7 +482,9 @@ extern "C" int segx_gemm_f32(const float* A, const float* B, float* C, const seg
                  d->M, d->N, d->K, d->nb0, d->nb1);
     SEGX_REQUIRE(d->a_m == 1 || d->a_k == 1, "segx_gemm_f32: A needs a unit stride (a_m=%lld a_k=%lld)", (long long)d->a_m, (long long)d->a_k);
     SEGX_REQUIRE(d->b_n == 1 || d->b_k == 1, "segx_gemm_f32: B needs a unit stride (b_n=%lld b_k=%lld)", (long long)d->b_n, (long long)d->b_k);
-    SEGX_REQUIRE(d->epilogue == SEGX_EPI_NONE || d->epilogue == SEGX_EPI_GELU, "segx_gemm_f32: bad epilogue %d", d->epilogue);
+    SEGX_REQUIRE(d->epilogue == SEGX_EPI_NONE || d->epilogue == SEGX_EPI_GELU || d->epilogue == SEGX_EPI_SWISH, "segx_gemm_f32: bad epilogue %d", d->epilogue);
+    SEGX_REQUIRE(d->epilogue != SEGX_EPI_SWISH || (d->a_k == 1 && d->b_n == 1 && d->b_k != 1 && !d->resid && !d->gmax && d->dropout_p == 0.f),
+                 "segx_gemm_f32: the swish epilogue is built for a pointwise convolution's forward (A k-contiguous, B row-contiguous; no resid, gmax or dropout)");
     SEGX_REQUIRE(d->epilogue != SEGX_EPI_GELU || d->aux, "segx_gemm_f32: GELU epilogue needs aux");
     SEGX_REQUIRE(d->bias_mode == SEGX_BIAS_NONE || d->bias, "segx_gemm_f32: bias_mode set but bias null");
     SEGX_REQUIRE(d->dropout_p >= 0.f && d->dropout_p < 1.f, "segx_gemm_f32: dropout_p out of range");

@@ -314,6 +314,7 @@ __device__ __forceinline__ void gemm_epilogue(const f32x16 (&acc)[Cfg::MI][Cfg::
                     if (bias_m) v += ok ? bias[row] : 0.f;
                     pre[q] = v;
                     if (EPI == SEGX_EPI_GELU) v = gelu_erf(v) * keep[q];
+                    if (EPI == SEGX_EPI_SWISH) v = swish_fwd(v);            // a pointwise convolution with its BatchNorm folded in (inference)
                     out[q] = v;
                     if (ok) vmax = fmaxf(vmax, v);
                     if (!vec_st && ok) {

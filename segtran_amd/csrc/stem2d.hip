@@ -10,9 +10,10 @@
 
 namespace segx {
 
-template <int CIN, int K>
-__global__ __launch_bounds__(256) void conv2d_stem_fwd_kernel(const float* __restrict__ X, const float* __restrict__ Wt, float* __restrict__ Y, int Cout, int H, int W,
-                                                              int OH, int OW, int st, int pt, int pl) {
+// FOLD: the inference form -- BatchNorm folded into Wt and `bias`, the activation applied in the store (Y = act(conv + bias[co]))
+template <int CIN, int K, bool FOLD = false>
+__global__ __launch_bounds__(256) void conv2d_stem_fwd_kernel(const float* __restrict__ X, const float* __restrict__ Wt, const float* __restrict__ bias, float* __restrict__ Y,
+                                                              int Cout, int H, int W, int OH, int OW, int st, int pt, int pl, int act) {
     constexpr int T = CIN * K * K;
     const int64_t P = (int64_t)OH * OW;
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -38,6 +39,7 @@ __global__ __launch_bounds__(256) void conv2d_stem_fwd_kernel(const float* __res
         float a = 0.f;
 #pragma unroll
         for (int t = 0; t < T; ++t) a += w[t] * v[t];
+        if (FOLD) { a += bias[co]; if (act == 1) a = swish_fwd(a); }
         if (live) y[(int64_t)co * P] = a;
     }
 }
@@ -80,8 +82,19 @@ extern "C" int segx_conv2d_stem_fwd(const float* X, const float* Wt, float* Y, i
     hipStream_t stream = (hipStream_t)stream_;
     SEGX_REQUIRE(X && Wt && Y && stem2d_ok(B, Cin, Cout, H, W, OH, OW, K, stride, pt, pl), "segx_conv2d_stem_fwd: 3 input channels, 3 x 3 window, stride 1 or 2 (B=%d Cin=%d K=%d stride=%d)", B, Cin, K, stride);
     const int64_t P = (int64_t)OH * OW;
-    hipLaunchKernelGGL((conv2d_stem_fwd_kernel<3, 3>), dim3((unsigned)((P + 255) / 256), (unsigned)B), dim3(256), 0, stream, X, Wt, Y, Cout, H, W, OH, OW, stride, pt, pl);
+    hipLaunchKernelGGL((conv2d_stem_fwd_kernel<3, 3>), dim3((unsigned)((P + 255) / 256), (unsigned)B), dim3(256), 0, stream, X, Wt, (const float*)nullptr, Y, Cout, H, W, OH, OW,
+                       stride, pt, pl, 0);
     return check_launch("segx_conv2d_stem_fwd");
+}
+extern "C" int segx_conv2d_stem_bias_act_fwd(const float* X, const float* Wt, const float* bias, float* Y, int B, int Cin, int Cout, int H, int W, int OH, int OW, int K,
+                                             int stride, int pt, int pl, int act, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    SEGX_REQUIRE(X && Wt && bias && Y && (act == 0 || act == 1) && stem2d_ok(B, Cin, Cout, H, W, OH, OW, K, stride, pt, pl),
+                 "segx_conv2d_stem_bias_act_fwd: 3 input channels, 3 x 3 window, stride 1 or 2, act 0 / 1 (B=%d Cin=%d K=%d stride=%d act=%d)", B, Cin, K, stride, act);
+    const int64_t P = (int64_t)OH * OW;
+    hipLaunchKernelGGL((conv2d_stem_fwd_kernel<3, 3, true>), dim3((unsigned)((P + 255) / 256), (unsigned)B), dim3(256), 0, stream, X, Wt, bias, Y, Cout, H, W, OH, OW,
+                       stride, pt, pl, act);
+    return check_launch("segx_conv2d_stem_bias_act_fwd");
 }
 extern "C" int segx_conv2d_stem_im2col(const float* X, float* Xcol, int B, int Cin, int H, int W, int OH, int OW, int K, int stride, int pt, int pl, int rows, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;

@@ -79,6 +79,16 @@ def drop_connect(x, p, training):
     return x / keep * torch.floor(r)
 
 
+def fold_conv_bn(weight, bn):
+    """BatchNorm in eval mode is the per-channel affine map y = x * s + (beta - mu * s), s = gamma / sqrt(var + eps): folded into the convolution that feeds it,
+    w' = w * s[out channel], b' = beta - mu * s.  Derived in fp64 on the parameters' device and rounded once to fp32; plain tensors (no Parameter, no buffer)."""
+    with torch.no_grad():
+        s = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
+        w = (weight.double() * s.view(-1, *([1] * (weight.dim() - 1)))).float().contiguous()
+        b = (bn.bias.double() - bn.running_mean.double() * s).float().contiguous()
+    return w, b
+
+
 class MBConvBlock(nn.Module):
     def __init__(self, k, s, e, cin, cout, se_ratio, image_size):
         super().__init__()
@@ -96,6 +106,25 @@ class MBConvBlock(nn.Module):
         self._bn2 = nn.BatchNorm2d(cout, momentum=BN_MOM, eps=BN_EPS)
 
     gate_in_weights = True     # False: the reference's op order (gate applied to the activation, model.py:110), as a separate pass
+
+    def folded_operands(self):
+        """(w0, b0) | None, (w1, b1), (w2, b2): expansion / depthwise / projection convolution with _bn0 / _bn1 / _bn2 folded in (EfficientNet.fold_batchnorm)"""
+        f0 = fold_conv_bn(self._expand_conv.weight, self._bn0) if self.expand_ratio != 1 else None
+        return f0, fold_conv_bn(self._depthwise_conv.weight, self._bn1), fold_conv_bn(self._project_conv.weight, self._bn2)
+
+    def forward_folded(self, inputs, folded):
+        """forward() in eval mode on folded operands: no BatchNorm launch.  swish(_bn0(.)) is the expansion GEMM's epilogue; the depthwise kernel adds b1, applies swish
+        and leaves the squeeze-excite pooling partials; the _bn2 scale sits in the projection weights BEFORE the gate forms the per-sample weights, its shift and the skip
+        input are the bias / resid operands of the per-sample GEMM."""
+        f0, (w1, b1), (w2, b2) = folded
+        x = inputs
+        skip = self.stride == 1 and self.input_filters == self.output_filters
+        if f0 is not None:
+            x = SF.conv1x1(x, f0[0], f0[1], act=SF.ACT_SWISH)
+        dw = self._depthwise_conv
+        y, psum, nch = SF.dwconv2d_bias_act_pool(x, w1, b1, dw.stride[0], dw.static_pad, SF.ACT_SWISH)
+        Wb = SF.se_gate_weights(y, psum, nch, self._se_reduce.weight, self._se_reduce.bias, self._se_expand.weight, self._se_expand.bias, w2)
+        return SF.conv1x1_per_sample_bias(y, Wb, b2, resid=inputs if skip else None)
 
     def forward(self, inputs, drop_connect_rate=None):
         """efficientnet/model.py:82-126"""
@@ -145,6 +174,66 @@ class EfficientNet(nn.Module):
         self._bn1 = nn.BatchNorm2d(chead, momentum=BN_MOM, eps=BN_EPS)
         self._fc = nn.Linear(chead, num_classes)               # kept for checkpoint compatibility; never used (N3)
 
+    # ---- inference with BatchNorm folded into the convolutions (opt-in) -------------------------------------------------------------
+    _folded = None             # None, or (stem, [per block], head, sources, versions): derived tensors, neither Parameters nor buffers -- never in state_dict()
+
+    def _fold_sources(self):
+        """every tensor the folded operands were derived from (convolution weights, BatchNorm parameters and running statistics)"""
+        src = []
+        for conv, bn in [(self._conv_stem, self._bn0), (self._conv_head, self._bn1)] + \
+                [(c, b) for blk in self._blocks for c, b in ((getattr(blk, '_expand_conv', None), getattr(blk, '_bn0', None)), (blk._depthwise_conv, blk._bn1),
+                                                            (blk._project_conv, blk._bn2)) if c is not None]:
+            src += [conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var]
+        return src
+
+    def fold_batchnorm(self):
+        """Derive the folded operands of every conv -> BatchNorm pair (stem, the three pairs of each MBConv block, head).  Eval mode only.  extract_endpoints then
+        issues no BatchNorm launch.  train(), load_state_dict(), a device / dtype move and an in-place change of a source tensor (torch's version counters) drop the fold again."""
+        if self.training:
+            raise RuntimeError('fold_batchnorm() is for inference: call .eval() first (in training mode BatchNorm uses batch statistics and cannot be folded)')
+        src = self._fold_sources()
+        self._folded = (fold_conv_bn(self._conv_stem.weight, self._bn0), [blk.folded_operands() for blk in self._blocks],
+                        fold_conv_bn(self._conv_head.weight, self._bn1), src, [t._version for t in src])
+        return self
+
+    def unfold_batchnorm(self):
+        self._folded = None
+
+    @property
+    def batchnorm_folded(self):
+        """True while extract_endpoints runs on folded operands; a source tensor changed in place since fold_batchnorm() drops the fold here"""
+        f = self._folded
+        if f is not None and (self.training or any(t._version != v for t, v in zip(f[3], f[4]))):
+            self._folded = f = None
+        return f is not None
+
+    def train(self, mode=True):
+        if mode:
+            self._folded = None
+        return super().train(mode)
+
+    def _apply(self, fn, *args, **kwargs):
+        self._folded = None                # .to() / .cuda() / .float(): the derived tensors would stay behind
+        return super()._apply(fn, *args, **kwargs)
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        self._folded = None                # reached from load_state_dict() of this module and of any module that contains it
+        return super()._load_from_state_dict(*args, **kwargs)
+
+    def _extract_endpoints_folded(self, inputs):
+        (ws, bs), blocks, (wh, bh) = self._folded[:3]
+        endpoints = {}
+        with torch.no_grad():
+            x = SF.conv2d_stem_bias_act(inputs, ws, bs, self._conv_stem.stride[0], self._conv_stem.static_pad, SF.ACT_SWISH)
+            prev_x = x
+            for idx, block in enumerate(self._blocks):
+                x = block.forward_folded(x, blocks[idx])
+                if idx in self.endpoint_blk_indices:
+                    endpoints['reduction_%d' % (len(endpoints) + 1)] = prev_x
+                prev_x = x
+            endpoints['reduction_%d' % (len(endpoints) + 1)] = SF.conv1x1(x, wh, bh, act=SF.ACT_SWISH)
+        return endpoints
+
     @classmethod
     def from_name(cls, model_name, stem_stride=2, **kw):
         return cls(model_name, stem_stride=stem_stride, **kw)
@@ -160,6 +249,8 @@ class EfficientNet(nn.Module):
         return model
 
     def extract_endpoints(self, inputs):
+        if self.batchnorm_folded:
+            return self._extract_endpoints_folded(inputs)
         endpoints = {}
         x = SF.bn_act(self._conv_stem(inputs), self._bn0, SF.ACT_SWISH)
         prev_x = x

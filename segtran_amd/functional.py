@@ -6,7 +6,7 @@ import math
 import torch
 import torch.nn.functional as F
 from . import segx
-from .segx import EPI_NONE, EPI_GELU, BIAS_NONE, BIAS_N, BIAS_M
+from .segx import EPI_NONE, EPI_GELU, EPI_SWISH, BIAS_NONE, BIAS_N, BIAS_M
 
 LN_EPS = 1e-12      # every LayerNorm of the Squeeze-and-Expansion transformer (segtran_shared.py:262,361,889,985)
 
@@ -620,12 +620,30 @@ def transpose12(x):
 # Pointwise (1x1 / 1x1x1) convolution on NC[D]HW tensors = one batched GEMM, no layout change:
 #   Y[b][co][s] = sum_ci W[co][ci] X[b][ci][s] + bias[co]      (s = flattened spatial index, contiguous)
 # -------------------------------------------------------------------------------------------------
-def conv1x1(x, weight, bias=None, pass_input=False):
+def _no_grad_operands(what, *ts):
+    """the inference-only ops (BatchNorm folded into their operands) have no backward: refuse an operand a gradient would flow through"""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
+        raise RuntimeError(what + ' is forward-only (inference with BatchNorm folded): call it under torch.no_grad() or on tensors without gradient')
+
+
+def conv1x1(x, weight, bias=None, pass_input=False, act=0):
     """x [B, Cin, *spatial]; weight [Cout, Cin, 1, 1(, 1)] (nn.Conv2d / nn.Conv3d layout).  pass_input: -> (y, x_alias); route a second use of x
-    (a skip connection) through x_alias and its gradient is added inside the dX GEMM (see _BGemm)."""
+    (a skip connection) through x_alias and its gradient is added inside the dX GEMM (see _BGemm).
+    act = ACT_SWISH: y = swish(conv + bias) from the GEMM's epilogue (SEGX_EPI_SWISH) -- forward only: a pointwise convolution whose BatchNorm was folded
+    into weight and bias (EfficientNet.fold_batchnorm)."""
     B, Cin = x.shape[0], x.shape[1]
     S = x.numel() // (B * Cin)
     Cout = weight.shape[0]
+    if act != ACT_NONE:
+        if act != ACT_SWISH or pass_input:
+            raise NotImplementedError('conv1x1: the only fused activation is swish (act = ACT_SWISH), without pass_input')
+        _no_grad_operands('conv1x1(act=ACT_SWISH)', x, weight, bias)
+        L = segx.lib()
+        x, W = _c(x), _c(weight.reshape(Cout, Cin))
+        y = _empty(x, B, Cout, *x.shape[2:])
+        _run_gemm(L, W, x, y, Cout, S, Cin, (0, 0, Cin, 1), (Cin * S, 0, 1, S), (Cout * S, 0, S), (B, 1), 1.0, bias=bias,
+                  bias_mode=BIAS_M if bias is not None else BIAS_NONE, epilogue=EPI_SWISH)
+        return y
     spec = GemmSpec(Cout, S, Cin, (0, 0, Cin, 1), (Cin * S, 0, 1, S), (Cout * S, 0, S),
                     (B, Cout) + tuple(x.shape[2:]), nb=(B, 1), bias_mode=BIAS_M)
     if pass_input and x.is_contiguous() and _live(x):
@@ -1112,6 +1130,49 @@ def conv1x1_per_sample(x, Wb, bias=None):
         return bgemm(Wb, x, spec)
     spec = GemmSpec(Cout, S, Cin, (Cout * Cin, 0, Cin, 1), (Cin * S, 0, 1, S), (Cout * S, 0, S), (B, Cout) + tuple(x.shape[2:]), nb=(B, 1), bias_mode=BIAS_M, bias_b0=Cout)
     return bgemm(Wb, x, spec, bias=_c(bias))
+
+
+def dwconv2d_bias_act_pool(x, w, bias, stride, pad, act=ACT_SWISH, pool=True):
+    """Inference form of depthwise conv -> BatchNorm -> activation -> squeeze-excite pooling with the BatchNorm folded into w [C, 1, k, k] and bias [C]:
+    y = act(dwconv2d(x, w) + bias) and the pooling partials of y from ONE pass (segx_dwconv2d_bias_act_pool).  -> (y, psum [B * C * nch] or None, nch);
+    psum / nch are what segx_se_fwd2 takes (se_gate_weights).  Forward only.  pad = (left, right, top, bottom)."""
+    if act not in (ACT_NONE, ACT_SWISH):
+        raise NotImplementedError('dwconv2d_bias_act_pool: act is ACT_NONE or ACT_SWISH')
+    _no_grad_operands('dwconv2d_bias_act_pool', x, w, bias)
+    L = segx.lib()
+    x, w = _c(x), _c(w)
+    B, C, H, W = x.shape
+    k, stride = w.shape[-1], int(stride)
+    pl, pr, pt, pb = (int(v) for v in pad)
+    OH, OW = (H + pt + pb - k) // stride + 1, (W + pl + pr - k) // stride + 1
+    y = _empty(x, B, C, OH, OW)
+    nch = L.dwconv2d_pool_chunks(OH, OW) if pool else 0
+    psum = _empty(x, B * C * nch) if pool else None
+    L.dwconv2d_bias_act_pool(x, w, _c(bias), y, psum, B, C, H, W, OH, OW, k, stride, pt, pl, act)
+    return y, psum, nch
+
+
+def se_gate_weights(y, psum, nch, w1, b1, w2, b2, proj_weight):
+    """Per-sample projection weights [B, Cout, C] = proj_weight * squeeze-excite gate, from the pooling partials of y (dwconv2d_bias_act_pool); forward only."""
+    _no_grad_operands('se_gate_weights', psum, w1, b1, w2, b2, proj_weight)
+    B, C = y.shape[0], y.shape[1]
+    S = y.numel() // (B * C)
+    return _se_excite(segx.lib(), y, psum, nch, S, w1, b1, w2, b2, _c(proj_weight.reshape(proj_weight.shape[0], C)))[5]
+
+
+def conv1x1_per_sample_bias(x, Wb, bias, resid=None):
+    """conv1x1_per_sample with ONE bias vector [Cout] for every sample and an optional skip input added in the GEMM's epilogue: y[b] = Wb[b] x[b] + bias (+ resid[b]).
+    Forward only: the projection of an MBConv block with its BatchNorm folded (scale in Wb, shift = bias, efficientnet/model.py:113-122 in eval mode)."""
+    _no_grad_operands('conv1x1_per_sample_bias', x, Wb, bias, resid)
+    B, Cin = x.shape[0], x.shape[1]
+    S = x.numel() // (B * Cin)
+    Cout = Wb.shape[1]
+    x, Wb = _c(x), _c(Wb)
+    y = _empty(x, B, Cout, *x.shape[2:])
+    kw = dict(resid=_c(resid)) if resid is not None else {}
+    assert resid is None or resid.shape == y.shape
+    _run_gemm(segx.lib(), Wb, x, y, Cout, S, Cin, (Cout * Cin, 0, Cin, 1), (Cin * S, 0, 1, S), (Cout * S, 0, S), (B, 1), 1.0, bias=_c(bias), bias_mode=BIAS_M, **kw)
+    return y
 
 
 def bn_act_se(x, bn, act, w1, b1, w2, b2):
@@ -1928,6 +1989,26 @@ def conv2d_dense(x, w, stride, pad):
     if _ConvStem2d.enabled and x.dim() == 4 and x.shape[1] == 3 and tuple(w.shape[1:]) == (3, 3, 3) and s in (1, 2) and not x.requires_grad and x.shape[0] <= 65535:
         return _ConvStem2d.apply(x, w, s, tuple(int(v) for v in pad))
     return _Conv3d.apply(x.unsqueeze(2), w.unsqueeze(2), (1, s, s), ((0, 0), (int(pad[2]), int(pad[3])), (int(pad[0]), int(pad[1])))).squeeze(2)
+
+
+def conv2d_stem_bias_act(x, w, bias, stride, pad, act=ACT_SWISH):
+    """The EfficientNet stem with its BatchNorm folded into w [Cout, 3, 3, 3] and bias [Cout]: y = act(conv2d_dense(x, w) + bias) in the direct stem kernel's store
+    (segx_conv2d_stem_bias_act_fwd).  Forward only; 3 input channels, 3 x 3, stride 1 or 2 -- anything else is an error (no other kernel carries the epilogue)."""
+    if act not in (ACT_NONE, ACT_SWISH):
+        raise NotImplementedError('conv2d_stem_bias_act: act is ACT_NONE or ACT_SWISH')
+    _no_grad_operands('conv2d_stem_bias_act', x, w, bias)
+    s = int(stride)
+    if not (x.dim() == 4 and x.shape[1] == 3 and tuple(w.shape[1:]) == (3, 3, 3) and s in (1, 2) and x.shape[0] <= 65535):
+        raise NotImplementedError('conv2d_stem_bias_act: only the 3-channel 3 x 3 stem at stride 1 or 2 is built')
+    L = segx.lib()
+    x, w = _c(x), _c(w)
+    B, Cin, H, W = x.shape
+    Cout, K = w.shape[0], 3
+    pl, pr, pt, pb = (int(v) for v in pad)
+    OH, OW = (H + pt + pb - K) // s + 1, (W + pl + pr - K) // s + 1
+    y = _empty(x, B, Cout, OH, OW)
+    L.conv2d_stem_bias_act_fwd(x, w, _c(bias), y, B, Cin, Cout, H, W, OH, OW, K, s, pt, pl, act)
+    return y
 
 
 class _PlaneBias(_Fn):

@@ -179,7 +179,27 @@ class Segtran2d(SegtranInitWeights):
         scores = _up(SF.conv1x1_tokens(fused_tokens, grid_shape, wo), size1, base=lateral)
         return _up(scores, size)
 
+    def fold_batchnorm(self):
+        """Inference only (eval mode, else RuntimeError): fold every BatchNorm of the EfficientNet backbone into the convolution in front of it (scale into the weights,
+        shift into a bias, swish into the producer's epilogue), so that a forward issues no BatchNorm launch.  The folded operands are derived tensors: state_dict() is
+        unchanged.  train() and load_state_dict() drop the fold; the model is then exactly the one that was never folded.  GroupNorm (FPNs) is data-dependent and stays."""
+        if self.training:
+            raise RuntimeError('fold_batchnorm() is for inference: call .eval() first')
+        self.backbone.fold_batchnorm()
+        return self
+
+    def unfold_batchnorm(self):
+        self.backbone.unfold_batchnorm()
+        return self
+
+    @property
+    def batchnorm_folded(self):
+        return self.backbone.batchnorm_folded
+
     def forward(self, batch):
+        if self.backbone.batchnorm_folded:                 # inference on folded operands: forward-only kernels, no autograd graph
+            with torch.no_grad():
+                return self._forward(batch)
         SF.defer_bn_ticks()
         try:
             return self._forward(batch)

@@ -203,6 +203,11 @@ class Segtran3d(SegtranInitWeights):
             scores = _up(scores, [scores.shape[2] * self.D_pool_K, scores.shape[3], scores.shape[4]])
         return _up(scores.permute(0, 1, 3, 4, 2), size)
 
+    batchnorm_folded = False
+
+    def fold_batchnorm(self):
+        raise NotImplementedError('fold_batchnorm: only Segtran2d (EfficientNet backbone) is built; the I3D backbone keeps its BatchNorm launches')
+
     def forward(self, batch):
         SF.defer_bn_ticks()
         try:

@@ -33,7 +33,7 @@ class GemmDesc(ctypes.Structure):
                 ('b_planes', c_p), ('bp_b0', c_l), ('bp_b1', c_l), ('resid', c_p)]
 
 
-EPI_NONE, EPI_GELU = 0, 1
+EPI_NONE, EPI_GELU, EPI_SWISH = 0, 1, 2
 (TILE_AUTO, TILE_128x128, TILE_64x64, TILE_128x32, TILE_32x128, TILE_64x128, TILE_256x128, TILE_WS128x128, TILE_WS128x256, TILE_WS64x256,
  TILE_WS96x256, TILE_WS256x96, TILE_SKINNY_NT) = range(13)
 BIAS_NONE, BIAS_N, BIAS_M = 0, 1, 2
@@ -391,6 +391,12 @@ class SegxLib:
     def dwconv2d_fwd(self, X, W, Y, B, C, H, Wd, OH, OW, k, stride, pt, pl):
         self._call('segx_dwconv2d_fwd', X, X, W, Y, B, C, H, Wd, OH, OW, k, stride, pt, pl)
 
+    def dwconv2d_pool_chunks(self, OH, OW):
+        return int(self.c.segx_dwconv2d_pool_chunks(OH, OW))
+
+    def dwconv2d_bias_act_pool(self, X, W, bias, Y, psum, B, C, H, Wd, OH, OW, k, stride, pt, pl, act):
+        self._call('segx_dwconv2d_bias_act_pool', X, X, W, bias, Y, psum, B, C, H, Wd, OH, OW, k, stride, pt, pl, act)
+
     def dwconv2d_bwd_data(self, dY, W, dX, B, C, H, Wd, OH, OW, k, stride, pt, pl):
         self._call('segx_dwconv2d_bwd_data', dY, dY, W, dX, B, C, H, Wd, OH, OW, k, stride, pt, pl)
 
@@ -605,6 +611,9 @@ class SegxLib:
     def conv2d_stem_fwd(self, X, W, Y, B, Cin, Cout, H, Wd, OH, OW, K, stride, pt, pl):
         self._call('segx_conv2d_stem_fwd', X, X, W, Y, B, Cin, Cout, H, Wd, OH, OW, K, stride, pt, pl)
 
+    def conv2d_stem_bias_act_fwd(self, X, W, bias, Y, B, Cin, Cout, H, Wd, OH, OW, K, stride, pt, pl, act):
+        self._call('segx_conv2d_stem_bias_act_fwd', X, X, W, bias, Y, B, Cin, Cout, H, Wd, OH, OW, K, stride, pt, pl, act)
+
     def conv2d_stem_im2col(self, X, Xcol, B, Cin, H, Wd, OH, OW, K, stride, pt, pl, rows):
         self._call('segx_conv2d_stem_im2col', X, X, Xcol, B, Cin, H, Wd, OH, OW, K, stride, pt, pl, rows)
 
@@ -705,6 +714,7 @@ _SIGS = {
     'segx_maxpool3d_fwd': 'ppplpp', 'segx_maxpool3d_bwd': 'ppplppp',
     'segx_bn_ws_floats': 'iil', 
     'segx_dwconv2d_fwd': 'pppiiiiiiiiiip', 'segx_dwconv2d_bwd_data': 'pppiiiiiiiiiip',
+    'segx_dwconv2d_pool_chunks': 'ii', 'segx_dwconv2d_bias_act_pool': 'pppppiiiiiiiiiiip', 'segx_conv2d_stem_bias_act_fwd': 'ppppiiiiiiiiiiiip',
     'segx_dwconv2d_bwd_weight': 'pppiiiiiiiiiip', 'segx_dwconv2d_bwd_weight_direct': 'pppiiiiiiiiiip', 'segx_dwconv2d_wgrad_rows': 'ii', 'segx_dwconv2d_bwd_fused_rows': 'iiiiiiii', 'segx_dwconv2d_bwd_fused': 'pppppiiiiiiiiiip', 'segx_plane_scale': 'pppllp', 'segx_plane_dot': 'pppllp',
      'segx_plane_bias_add': 'ppplilp', 
     'segx_plane_chunks': 'l', 'segx_bn_pool_chunks': 'ili', 'segx_bn_parts_floats': 'iil', 'segx_bn_stats_local': 'pppiilp',
