@@ -583,6 +583,22 @@ int segx_window_accum(const float* scores, float* acc, float* cnt, int B, int C,
  * acc/soft/hard [B, C, S] (hard as 0/1 floats), cnt [B, S]; soft may be NULL */
 int segx_harden_segmap(const float* acc, const float* cnt, float* soft, float* hard, int B, int C, int64_t S, int mode, float T,
                        void* stream);
+/* The whole sliding-window evaluation as a fixed sequence: segx_window_gather, the network on the stacked windows, segx_window_merge.
+ * origins: DEVICE int32 [nwin][3] = {oz, oy, ox} per window, in padded-canvas coordinates, in the order the eager loops visit the windows;
+ * origins_host: the same table in HOST memory -- the refusals (a window outside the canvas) are decided on it, the kernels read the device copy
+ * (and check every access themselves, whatever it holds).  2-D: depth extents 1, oz = pz = 0.
+ * segx_window_gather: out[k * B + b][c] = padded[b][c][window k], where `padded` is the image zero-padded to the canvas with the left pads (pz, py, px) -- it
+ *   never exists in memory.  image [B, C, ID, IH, IW]; out [nwin * B, C, D, H, W];
+ *   geom (int32[12]) = {ID, IH, IW (image), pz, py, px (left pads), D, H, W (window), CD, CH, CW (padded canvas)} */
+int segx_window_gather(const float* image, const int* origins, const int* origins_host, float* out, int nwin, int B, int C, const int* geom,
+                       void* stream);
+/* segx_window_merge: what nwin segx_window_accum calls (ascending k, on zeroed acc / cnt) and one segx_harden_segmap leave, restricted to the image:
+ *   soft[b][c][cell] = (sum over the windows k covering the cell of sigmoid(F.interpolate(scores[k * B + b][c], size=window))) / (their number), bit for bit;
+ *   hard as segx_harden_segmap (mode 0 / mode 1 with C == 4, threshold T).  acc and cnt never exist.
+ *   scores [nwin * B, C, d, h, w]; soft, hard [B, C, ID, IH, IW];
+ *   geom (int32[15]) = {d, h, w (scores), D, H, W (window), CD, CH, CW (padded canvas), pz, py, px (left pads), ID, IH, IW (image)} */
+int segx_window_merge(const float* scores, const int* origins, const int* origins_host, float* soft, float* hard, int nwin, int B, int C,
+                      const int* geom, int mode, float T, void* stream);
 /* calc_dice sums (test_util2d.py:233-240) per plane: part [chunks][planes][3] = {sum pred*gt, sum pred^2, sum gt^2},
  * chunks*planes*3 = segx_dice_ws_floats(planes, S); reduce over chunks with segx_colsum */
 int64_t segx_dice_ws_floats(int64_t planes, int64_t S);

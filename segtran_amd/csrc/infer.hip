@@ -11,6 +11,13 @@ namespace segx {
 
 struct Canvas { int CD, CH, CW, oz, oy, ox; };          // canvas spatial dims and the window's origin inside it
 
+// probability one window contributes at its position (z, y, x): sigmoid of the score plane s[d][h][w] resampled to the window (window_accum_kernel and
+// window_merge_kernel both call it: the same expression, hence the same bits)
+__device__ __forceinline__ float window_prob(const float* __restrict__ s, const InterpDims& q, bool same, int z, int y, int x) {
+    const float v = same ? s[((int64_t)z * q.h + y) * q.w + x] : interp_at(s, q, z, y, x);
+    return 1.0f / (1.0f + expf(-v));
+}
+
 // acc[b][c][oz+z][oy+y][ox+x] += sigmoid(resample(scores[b][c]))(z, y, x);  cnt[b][oz+z][oy+y][ox+x] += 1.   One thread per
 // window voxel (all classes), so a launch never touches a canvas cell twice; overlapping windows are separate launches.
 __global__ __launch_bounds__(256) void window_accum_kernel(const float* __restrict__ scores, float* __restrict__ acc, float* __restrict__ cnt,
@@ -23,17 +30,35 @@ __global__ __launch_bounds__(256) void window_accum_kernel(const float* __restri
         const int y = (int)(r / q.W), x = (int)(r - (int64_t)y * q.W);
         const int64_t cell = ((int64_t)(cv.oz + z) * cv.CH + (cv.oy + y)) * cv.CW + (cv.ox + x);
         for (int c = 0; c < C; ++c) {
-            const float* s = scores + ((int64_t)b * C + c) * ssz;
-            const float v = same ? s[((int64_t)z * q.h + y) * q.w + x] : interp_at(s, q, z, y, x);
-            acc[((int64_t)b * C + c) * csz + cell] += 1.0f / (1.0f + expf(-v));
+            acc[((int64_t)b * C + c) * csz + cell] += window_prob(scores + ((int64_t)b * C + c) * ssz, q, same, z, y, x);
         }
         cnt[(int64_t)b * csz + cell] += 1.0f;
     }
 }
 
-// soft = acc / cnt (cnt == NULL: acc already is the soft map); mode 1 first makes a BraTS prediction consistent, the permissive way
-// (is_conservative=False): P(WT) = max(P(ET), P(WT), P(TC)), P(TC) = max(P(ET), P(TC));  then hard[c >= 1] = soft[c] >= T and
-// hard[0] = (no other class is on).  One thread per voxel.
+// the mean of the covering windows' probabilities
+__device__ __forceinline__ float mean_prob(float a, float n) { return a / n; }
+// One cell's C soft values p[] -> soft / hard planes (both already offset to the cell of class 0; classes lie S floats apart).  mode 1 first makes a BraTS
+// prediction consistent, the permissive way (is_conservative=False): P(WT) = max(P(ET), P(WT), P(TC)), P(TC) = max(P(ET), P(TC));  then
+// hard[c >= 1] = soft[c] >= T and hard[0] = (no other class is on).  harden_kernel and window_merge_kernel both call it.
+__device__ __forceinline__ void harden_cell(float* p, int C, int mode, float T, float* __restrict__ soft, float* __restrict__ hard, int64_t S) {
+    if (mode == 1) {                                   // C == 4: [bg, ET, WT, TC]
+        const float et = p[1], wt = p[2], tc = p[3];
+        p[2] = fmaxf(fmaxf(et, wt), tc);
+        p[3] = fmaxf(et, tc);
+    }
+    bool any = false;
+    for (int c = 1; c < C; ++c) {
+        const bool on = p[c] >= T;
+        any = any || on;
+        hard[c * S] = on ? 1.0f : 0.0f;
+        if (soft) soft[c * S] = p[c];
+    }
+    hard[0] = any ? 0.0f : 1.0f;
+    if (soft) soft[0] = p[0];
+}
+
+// soft = acc / cnt (cnt == NULL: acc already is the soft map), then harden_cell.  One thread per voxel.
 __global__ __launch_bounds__(256) void harden_kernel(const float* __restrict__ acc, const float* __restrict__ cnt, float* __restrict__ soft,
                                                      float* __restrict__ hard, int B, int C, int64_t S, int mode, float T) {
     const int64_t total = (int64_t)B * S;
@@ -41,21 +66,52 @@ __global__ __launch_bounds__(256) void harden_kernel(const float* __restrict__ a
         const int64_t b = idx / S, s = idx - b * S;
         const float n = cnt ? cnt[idx] : 1.0f;
         float p[8];
-        for (int c = 0; c < C; ++c) p[c] = cnt ? acc[(b * C + c) * S + s] / n : acc[(b * C + c) * S + s];
-        if (mode == 1) {                                   // C == 4: [bg, ET, WT, TC]
-            const float et = p[1], wt = p[2], tc = p[3];
-            p[2] = fmaxf(fmaxf(et, wt), tc);
-            p[3] = fmaxf(et, tc);
+        for (int c = 0; c < C; ++c) p[c] = cnt ? mean_prob(acc[(b * C + c) * S + s], n) : acc[(b * C + c) * S + s];
+        harden_cell(p, C, mode, T, soft ? soft + (b * C) * S + s : nullptr, hard + (b * C) * S + s, S);
+    }
+}
+
+// ---- the whole sliding-window evaluation as gather -> network on stacked windows -> merge (two launches around the forwards, capturable) ----
+// origins: int32 [nwin][3] = {oz, oy, ox} of each window in PADDED-canvas coordinates, in the order the eager loops visit the windows.
+struct Sliding { int CD, CH, CW, pz, py, px, ID, IH, IW; };   // padded canvas, left pads, image (the un-padded region of the canvas)
+
+// out[k * B + b][c] = the window crop of image[b][c] at origin k; canvas cells outside the image read 0 (the zero padding never exists in memory).  One thread per
+// output element; every read is checked against the image, whatever the table holds.
+__global__ __launch_bounds__(256) void window_gather_kernel(const float* __restrict__ image, const int* __restrict__ origins, float* __restrict__ out,
+                                                            int nwin, int B, int C, int D, int H, int W, Sliding sl) {
+    const int64_t wsz = (int64_t)D * H * W, total = (int64_t)nwin * B * C * wsz;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        const int64_t pl = idx / wsz; int64_t r = idx - pl * wsz;            // pl = (k * B + b) * C + c
+        const int z = (int)(r / ((int64_t)H * W)); r -= (int64_t)z * H * W;
+        const int y = (int)(r / W), x = (int)(r - (int64_t)y * W);
+        const int c = (int)(pl % C), kb = (int)(pl / C), b = kb % B, k = kb / B;
+        const int iz = origins[3 * k] - sl.pz + z, iy = origins[3 * k + 1] - sl.py + y, ix = origins[3 * k + 2] - sl.px + x;      // image coordinates
+        const bool in = (unsigned)iz < (unsigned)sl.ID && (unsigned)iy < (unsigned)sl.IH && (unsigned)ix < (unsigned)sl.IW;
+        out[idx] = in ? image[((((int64_t)b * C + c) * sl.ID + iz) * sl.IH + iy) * sl.IW + ix] : 0.0f;
+    }
+}
+
+// soft[b][c][cell] = (sum over the windows k covering the cell, ascending k, of window_prob(scores[k * B + b][c])) / (their count), then harden_cell: what
+// nwin segx_window_accum passes over zeroed acc / cnt followed by segx_harden_segmap leave, restricted to the image (the un-padded region), without acc / cnt
+// in memory.  One thread per image cell (all classes); the covering windows are found by a pass over the table (uniform loads: k is the same in every lane).
+__global__ __launch_bounds__(256) void window_merge_kernel(const float* __restrict__ scores, const int* __restrict__ origins, float* __restrict__ soft,
+                                                           float* __restrict__ hard, int nwin, int B, int C, InterpDims q, Sliding sl, int mode, float T) {
+    const int64_t isz = (int64_t)sl.ID * sl.IH * sl.IW, ssz = (int64_t)q.d * q.h * q.w, total = (int64_t)B * isz;
+    const bool same = q.d == q.D && q.h == q.H && q.w == q.W;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        const int64_t b = idx / isz, cell = idx - b * isz; int64_t r = cell;
+        const int z = (int)(r / ((int64_t)sl.IH * sl.IW)); r -= (int64_t)z * sl.IH * sl.IW;
+        const int y = (int)(r / sl.IW), x = (int)(r - (int64_t)y * sl.IW);
+        float p[8], n = 0.0f;
+        for (int c = 0; c < C; ++c) p[c] = 0.0f;
+        for (int k = 0; k < nwin; ++k) {
+            const int wz = z + sl.pz - origins[3 * k], wy = y + sl.py - origins[3 * k + 1], wx = x + sl.px - origins[3 * k + 2];
+            if ((unsigned)wz >= (unsigned)q.D || (unsigned)wy >= (unsigned)q.H || (unsigned)wx >= (unsigned)q.W) continue;
+            for (int c = 0; c < C; ++c) p[c] += window_prob(scores + (((int64_t)k * B + b) * C + c) * ssz, q, same, wz, wy, wx);
+            n += 1.0f;
         }
-        bool any = false;
-        for (int c = 1; c < C; ++c) {
-            const bool on = p[c] >= T;
-            any = any || on;
-            hard[(b * C + c) * S + s] = on ? 1.0f : 0.0f;
-            if (soft) soft[(b * C + c) * S + s] = p[c];
-        }
-        hard[(b * C) * S + s] = any ? 0.0f : 1.0f;
-        if (soft) soft[(b * C) * S + s] = p[0];
+        for (int c = 0; c < C; ++c) p[c] = mean_prob(p[c], n);
+        harden_cell(p, C, mode, T, soft + (b * C) * isz + cell, hard + (b * C) * isz + cell, isz);
     }
 }
 
@@ -99,6 +155,44 @@ extern "C" int segx_harden_segmap(const float* acc, const float* cnt, float* sof
     const int64_t total = (int64_t)B * S;
     hipLaunchKernelGGL(harden_kernel, dim3((unsigned)i64min(65536, (total + 255) / 256)), dim3(256), 0, stream, acc, cnt, soft, hard, B, C, S, mode, T);
     return check_launch("segx_harden_segmap");
+}
+// every window of the host copy of the table inside the padded canvas, and the image inside it at the left pads
+static bool sliding_ok(const int* o, int nwin, int D, int H, int W, const Sliding& sl) {
+    if (sl.CD <= 0 || sl.CH <= 0 || sl.CW <= 0 || sl.ID <= 0 || sl.IH <= 0 || sl.IW <= 0 || sl.pz < 0 || sl.py < 0 || sl.px < 0 ||
+        sl.pz + sl.ID > sl.CD || sl.py + sl.IH > sl.CH || sl.px + sl.IW > sl.CW) return false;
+    for (int k = 0; k < nwin; ++k)
+        if (o[3 * k] < 0 || o[3 * k + 1] < 0 || o[3 * k + 2] < 0 || o[3 * k] + D > sl.CD || o[3 * k + 1] + H > sl.CH || o[3 * k + 2] + W > sl.CW) return false;
+    return true;
+}
+/* image [B, C, ID, IH, IW] -> out [nwin * B, C, D, H, W] (window-major, then image);  origins: device int32 [nwin][3], origins_host: the same table in host
+ * memory (the refusals are decided on it);  geom (int32[12]) = {ID, IH, IW (image), pz, py, px (left pads), D, H, W (window), CD, CH, CW (padded canvas)} */
+extern "C" int segx_window_gather(const float* image, const int* origins, const int* origins_host, float* out, int nwin, int B, int C, const int* geom,
+                                  void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(image && origins && origins_host && out && geom, "segx_window_gather: null pointer");
+    SEGX_REQUIRE(nwin > 0 && B > 0 && C > 0, "segx_window_gather: nwin, B and C must be positive");
+    const Sliding sl{geom[9], geom[10], geom[11], geom[3], geom[4], geom[5], geom[0], geom[1], geom[2]};
+    const int D = geom[6], H = geom[7], W = geom[8];
+    SEGX_REQUIRE(D > 0 && H > 0 && W > 0, "segx_window_gather: bad window size");
+    SEGX_REQUIRE(sliding_ok(origins_host, nwin, D, H, W, sl), "segx_window_gather: window outside the padded canvas");
+    const int64_t total = (int64_t)nwin * B * C * D * H * W;
+    hipLaunchKernelGGL(window_gather_kernel, dim3((unsigned)i64min(65536, (total + 255) / 256)), dim3(256), 0, stream, image, origins, out, nwin, B, C, D, H, W, sl);
+    return check_launch("segx_window_gather");
+}
+/* scores [nwin * B, C, d, h, w] -> soft, hard [B, C, ID, IH, IW] (hard as 0/1 floats);  origins / origins_host as segx_window_gather;
+ * geom (int32[15]) = {d, h, w (scores), D, H, W (window), CD, CH, CW (padded canvas), pz, py, px (left pads), ID, IH, IW (image)};  mode, T as segx_harden_segmap */
+extern "C" int segx_window_merge(const float* scores, const int* origins, const int* origins_host, float* soft, float* hard, int nwin, int B, int C,
+                                 const int* geom, int mode, float T, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(scores && origins && origins_host && soft && hard && geom, "segx_window_merge: null pointer");
+    SEGX_REQUIRE(nwin > 0 && B > 0 && C >= 2 && C <= 8, "segx_window_merge: nwin and B must be positive, 2 <= C <= 8");
+    SEGX_REQUIRE(mode == 0 || (mode == 1 && C == 4), "segx_window_merge: mode is 0, or 1 with C == 4");
+    SEGX_REQUIRE(geom[0] > 0 && geom[1] > 0 && geom[2] > 0 && geom[3] > 0 && geom[4] > 0 && geom[5] > 0, "segx_window_merge: bad scores / window size");
+    const InterpDims q = make_dims(geom[0], geom[1], geom[2], geom[3], geom[4], geom[5]);
+    const Sliding sl{geom[6], geom[7], geom[8], geom[9], geom[10], geom[11], geom[12], geom[13], geom[14]};
+    SEGX_REQUIRE(sliding_ok(origins_host, nwin, q.D, q.H, q.W, sl), "segx_window_merge: window outside the padded canvas");
+    const int64_t total = (int64_t)B * sl.ID * sl.IH * sl.IW;
+    hipLaunchKernelGGL(window_merge_kernel, dim3((unsigned)i64min(65536, (total + 255) / 256)), dim3(256), 0, stream, scores, origins, soft, hard, nwin, B, C, q,
+                       sl, mode, T);
+    return check_launch("segx_window_merge");
 }
 extern "C" int64_t segx_dice_ws_floats(int64_t planes, int64_t S) { return 3 * planes * i64max(1, i64min(64, (S + 4095) / 4096)); }
 /* part: segx_dice_ws_floats(planes, S) floats laid out [chunks][planes][3]; sums[planes][3] = segx_colsum over the chunks */

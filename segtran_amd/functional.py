@@ -2271,6 +2271,73 @@ def harden_segmap(acc, cnt=None, mode=0, T=0.5, want_soft=True):
     return soft, hard
 
 
+class WindowTable:
+    """The window origins of one sliding-window evaluation: `origins` = one (start...) tuple per window (2-D (y0, x0), 3-D (z0, y0, x0)) in padded-canvas
+    coordinates, in the order the eager loops visit the windows.  Holds the device table the kernels read (int32 [nwin, 3]) and the host copy their refusals
+    are decided on; build it once and pass it to window_gather / window_merge (building one copies to the device, which a graph capture refuses)."""
+
+    def __init__(self, origins, device):
+        o = [tuple(int(v) for v in w) for w in origins]
+        if not o or any(len(w) != len(o[0]) or len(w) not in (2, 3) for w in o):
+            raise ValueError('WindowTable: one (y0, x0) or (z0, y0, x0) per window, at least one window')
+        self.nd, self.nwin = len(o[0]), len(o)
+        self.origins = tuple(o)
+        flat = [v for w in o for v in (0,) * (3 - self.nd) + w]
+        self.host = (segx.c_i * len(flat))(*flat)
+        self.dev = torch.tensor(flat, dtype=torch.int32, device=device).view(self.nwin, 3)
+
+
+def _window_geometry(what, table, nd, image_size, window, pads, canvas):
+    if not isinstance(table, WindowTable) or table.nd != nd:
+        raise TypeError('%s: `table` is a WindowTable of %d-D origins' % (what, nd))
+    image_size, window = tuple(int(v) for v in image_size), tuple(int(v) for v in window)
+    pads = tuple(int(v) for v in pads) if pads is not None else (0,) * nd
+    canvas = tuple(int(v) for v in canvas) if canvas is not None else tuple(max(i + p, w) for i, p, w in zip(image_size, pads, window))
+    if not len(image_size) == len(window) == len(pads) == len(canvas) == nd:
+        raise ValueError('%s: image size, window, pads and canvas must all have %d entries' % (what, nd))
+    one, zero = (1,) * (3 - nd), (0,) * (3 - nd)
+    return one + image_size, one + window, zero + pads, one + canvas
+
+
+def window_gather(image, table, window, patch_size=None, pads=None, canvas=None):
+    """The network's input for every window: image [B, C, *spatial] -> [nwin * B, C, *patch_size], window-major then image; entry k * B + b is
+    interp_linear(padded[b, :, window k], patch_size) bit for bit (the plain crop when patch_size == window), where `padded` is the image zero-padded to `canvas`
+    with the left pads `pads` -- it never exists in memory.  One launch (segx_window_gather) for the crops of all windows; when the patch size differs, ONE
+    interp_linear over the stacked crops follows (per-plane arithmetic: the bits of the per-window calls).  table: WindowTable; canvas defaults to
+    max(image + pads, window).  Forward only."""
+    _no_grad_operands('window_gather', image)
+    L = segx.lib()
+    image = _c(image.detach())
+    nd = image.dim() - 2
+    B, C = image.shape[:2]
+    i3, w3, p3, c3 = _window_geometry('window_gather', table, nd, image.shape[2:], window, pads, canvas)
+    out = _empty(image, table.nwin * B, C, *w3[3 - nd:])
+    L.window_gather(image, table.dev, table.host, out, table.nwin, B, C, i3 + p3 + w3 + c3)
+    if patch_size is not None and tuple(int(v) for v in patch_size) != w3[3 - nd:]:
+        out = interp_linear(out, patch_size)
+    return out
+
+
+def window_merge(scores, table, window, image_size, pads=None, canvas=None, mode=0, T=0.5):
+    """(soft, hard) [B, C, *image_size] of the whole sliding-window evaluation in one launch (segx_window_merge): scores [nwin * B, C, *s] (laid out as
+    window_gather's output).  Bit for bit what window_accum per window (in the table's order, on zeroed acc / cnt) followed by harden_segmap(mode, T) leaves in
+    the un-padded region of the canvas; acc and cnt never exist.  A cell that no window of a hand-built table covers is 0 / 0 = NaN, as on the eager path
+    (infer2d.sliding_windows never leaves one).  Forward only."""
+    _no_grad_operands('window_merge', scores)
+    L = segx.lib()
+    scores = _c(scores.detach())
+    nd = scores.dim() - 2
+    C = scores.shape[1]
+    if scores.shape[0] % table.nwin:
+        raise ValueError('window_merge: scores holds %d samples, no multiple of the %d windows' % (scores.shape[0], table.nwin))
+    B = scores.shape[0] // table.nwin
+    i3, w3, p3, c3 = _window_geometry('window_merge', table, nd, image_size, window, pads, canvas)
+    soft = _empty(scores, B, C, *i3[3 - nd:])
+    hard = torch.empty_like(soft)
+    L.window_merge(scores, table.dev, table.host, soft, hard, table.nwin, B, C, (1,) * (3 - nd) + tuple(scores.shape[2:]) + w3 + c3 + p3 + i3, mode, T)
+    return soft, hard
+
+
 def dice_scores(pred, gt, smooth=1e-5):
     """calc_dice (test_util2d.py:233-240) for every leading plane of pred/gt [..., *spatial] given as [P, S]-viewable tensors:
     (2 sum(p g) + s) / (sum p^2 + sum g^2 + s).  Returns a [P] tensor."""

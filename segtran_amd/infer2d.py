@@ -1,9 +1,14 @@
-"""2-D evaluation with BatchNorm folded into the backbone's kernels: test_util2d's sliding-window inference with a `fold_bn` switch.
+"""2-D evaluation with BatchNorm folded into the backbone's kernels: test_util2d's sliding-window inference with a `fold_bn` switch, a `fused` form
+(one gather launch, the network on stacked windows, one merge launch) and that form captured as one replayable hipGraph (GraphedSlidingWindow).
 
 test_util2d.py mirrors the reference's file of that name and keeps the reference's signatures; the switch lives here.  fold_bn=True folds the (eval-mode) net for
 the call if it is not folded already (Segtran2d.fold_batchnorm) and unfolds it afterwards; a net the caller folded stays folded."""
 import contextlib
+import math
 
+import torch
+
+from . import functional as SF
 from . import test_util2d as _T2
 from .test_util2d import calc_dice, calc_batch_metric          # noqa: F401  (same module surface)
 
@@ -20,16 +25,160 @@ def _folded(net, fold_bn):
             net.unfold_batchnorm()
 
 
-def test_single_batch(net, image_batch, orig_input_size, patch_size, stride, task_name, num_classes, model_type='segtran', fold_bn=False):
-    """test_util2d.test_single_batch; fold_bn: with the backbone's BatchNorm layers folded into its convolutions for this call."""
-    with _folded(net, fold_bn):
-        return _T2.test_single_batch(net, image_batch, orig_input_size, patch_size, stride, task_name, num_classes, model_type)
+def sliding_windows(H, W, orig_input_size, stride):
+    """The window geometry of test_util2d.test_single_batch for an H x W image: ((hl_pad, wl_pad), (H2, W2), origins) -- the left pads, the padded extent and
+    the (xs, ys) origin of every window in padded coordinates, visited x-outer, y-inner, the last row / column clamped to extent - window.  A stride above its
+    window extent leaves cells no window covers (the eager path divides 0 by 0 there): ValueError."""
+    dx, dy = (int(v) for v in orig_input_size)
+    s0, s1 = (int(v) for v in stride)
+    if s0 <= 0 or s1 <= 0 or s0 > dx or s1 > dy:
+        raise ValueError('sliding_windows: stride %r must be positive and at most the window %r' % (tuple(stride), tuple(orig_input_size)))
+    h_pad, w_pad = max(dx - H, 0), max(dy - W, 0)
+    hl_pad, wl_pad = h_pad // 2, w_pad // 2
+    H2, W2 = H + h_pad, W + w_pad
+    sx = math.ceil((H2 - dx) / s0) + 1
+    sy = math.ceil((W2 - dy) / s1) + 1
+    origins = [(min(s0 * x, H2 - dx), min(s1 * y, W2 - dy)) for x in range(sx) for y in range(sy)]
+    return (hl_pad, wl_pad), (H2, W2), origins
 
 
-def test_all_cases(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, mask_prepred_mapping_func=None, fold_bn=False):
-    """test_util2d.test_all_cases; fold_bn: ONE fold for all the batches."""
+# The per-plane kernels of the backbone and the FPNs take (sample, channel) planes as a grid axis and refuse more: `SEGX_REQUIRE((int64_t)B * C <= 65535, ...)` in
+# segx_dwconv2d_fwd / segx_dwconv2d_bias_act_pool / segx_plane_scale / segx_plane_bias_add (backbone.hip) and segx_groupnorm_fwd (fpn.hip).
+MAX_PLANES = 65535
+
+
+def max_stacked_samples(net):
+    """the largest batch one net() call accepts: MAX_PLANES over the widest convolution output of the model (EfficientNet-B4: 2688 expanded channels -> 24)"""
+    widest = max((m.weight.shape[0] for m in net.modules() if isinstance(getattr(m, 'weight', None), torch.Tensor) and m.weight.dim() >= 4), default=1)
+    return max(1, MAX_PLANES // int(widest))
+
+
+class _Plan:
+    """what the fused sequence needs beyond the image: the window table on the device and the geometry"""
+
+    def __init__(self, net, image_shape, orig_input_size, patch_size, stride, device, window_batch):
+        self.shape = tuple(int(v) for v in image_shape)
+        self.window, self.patch = tuple(int(v) for v in orig_input_size), tuple(int(v) for v in patch_size)
+        self.pads, self.canvas, origins = sliding_windows(self.shape[2], self.shape[3], self.window, stride)
+        self.table = SF.WindowTable(origins, device)
+        nwin = self.table.nwin
+        fit = max(1, max_stacked_samples(net) // self.shape[0])          # windows per call the library's plane limit leaves room for
+        self.window_batch = min(nwin, fit) if window_batch is None else min(nwin, int(window_batch))
+        if self.window_batch < 1:
+            raise ValueError('window_batch must be at least 1')
+
+    def run(self, net, image_batch):
+        """gather -> net() on chunks of window_batch windows (window_batch * B samples each) -> merge; the caller holds torch.no_grad()"""
+        B, nwin = self.shape[0], self.table.nwin
+        patches = SF.window_gather(image_batch, self.table, self.window, self.patch, self.pads, self.canvas)
+        if self.window_batch >= nwin:
+            scores = net(patches)
+        else:
+            scores = None
+            for k in range(0, nwin, self.window_batch):
+                part = net(patches[k * B:(k + self.window_batch) * B])
+                if scores is None:
+                    scores = part.new_empty((nwin * B,) + tuple(part.shape[1:]))
+                scores[k * B:k * B + part.shape[0]] = part               # plumbing: the chunks' scores side by side, as merge reads them
+        preds_soft, preds_hard = SF.window_merge(scores, self.table, self.window, self.shape[2:], self.pads, self.canvas, mode=0)
+        return preds_hard.to(torch.int32), preds_soft
+
+
+def test_single_batch(net, image_batch, orig_input_size, patch_size, stride, task_name, num_classes, model_type='segtran', fold_bn=False, fused=False,
+                      window_batch=None):
+    """test_util2d.test_single_batch; fold_bn: with the backbone's BatchNorm layers folded into its convolutions for this call.
+    fused: one window_gather launch, net() on chunks of `window_batch` windows (window_batch * B samples each; default: all windows in one call, or the largest chunks
+    max_stacked_samples(net) allows), one
+    window_merge launch -- no canvas copy, no per-window accumulate pass.  With window_batch=1 the forwards are the eager path's, and so are the results, bit
+    for bit; stacked windows change the GEMMs' shapes, hence the summation order inside the network."""
+    if fused and model_type not in ('segtran',):
+        raise NotImplementedError("model_type '%s': only segtran is built" % model_type)
     with _folded(net, fold_bn):
-        return _T2.test_all_cases(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, mask_prepred_mapping_func)
+        if not fused:
+            return _T2.test_single_batch(net, image_batch, orig_input_size, patch_size, stride, task_name, num_classes, model_type)
+        plan = _Plan(net, image_batch.shape, orig_input_size, patch_size, stride, image_batch.device, window_batch)
+        with torch.no_grad():
+            return plan.run(net, image_batch)
+
+
+def test_all_cases(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, mask_prepred_mapping_func=None, fold_bn=False, fused=False,
+                   window_batch=None):
+    """test_util2d.test_all_cases; fold_bn: ONE fold for all the batches; fused / window_batch: as test_single_batch."""
+    with _folded(net, fold_bn):
+        if not fused:
+            return _T2.test_all_cases(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, mask_prepred_mapping_func)
+        total, count = _T2.np.zeros(num_classes - 1), 0
+        for image_batch, mask_batch in batches:
+            gt = mask_prepred_mapping_func(mask_batch) if mask_prepred_mapping_func else mask_batch
+            _, preds_soft = test_single_batch(net, image_batch, orig_input_size, patch_size, stride, task_name, num_classes, fused=True, window_batch=window_batch)
+            m = calc_batch_metric(preds_soft, gt, num_classes)
+            total += m.sum(axis=0); count += len(m)
+        return total / max(count, 1), count
+
+
+class GraphedSlidingWindow:
+    """The fused sliding-window evaluation of one image-batch shape captured into a hipGraph and replayed: gather, the forward(s) and merge -- a few hundred
+    launches per forward -- become one graph launch, which takes the host out of a launch-bound evaluation (as engine.GraphedTrainStep does for the train step).
+
+    net must be in eval mode (RuntimeError otherwise).  fold_bn folds its BatchNorm layers if they are not folded already; close() unfolds what the constructor
+    folded.  __call__(image_batch) copies the batch into a static buffer, replays and returns (preds_hard int32, preds_soft) [B, num_classes, H, W]: STATIC
+    tensors that the next call overwrites -- clone what must outlive it.  The captured kernels read the weights (and the folded operands) at fixed addresses, so
+    a call raises RuntimeError once the net was put in train mode or its fold state differs from the one captured (train(), load_state_dict() and in-place edits
+    of a folded tensor all drop the fold)."""
+
+    def __init__(self, net, image_shape, orig_input_size, patch_size, stride, num_classes, fold_bn=True, window_batch=None, warmup=2):
+        from . import segx
+        if net.training:
+            raise RuntimeError('GraphedSlidingWindow is for inference: call net.eval() first')
+        assert segx.lib().gemm_prof is None, 'per-launch event profiling cannot run inside a captured evaluation'
+        device = next(net.parameters()).device
+        self.net, self.num_classes = net, num_classes
+        self._folded_here = bool(fold_bn) and not net.batchnorm_folded
+        if self._folded_here:
+            net.fold_batchnorm()
+        try:
+            self.folded = net.batchnorm_folded
+            self.plan = _Plan(net, image_shape, orig_input_size, patch_size, stride, device, window_batch)
+            self.image = torch.zeros(self.plan.shape, dtype=torch.float32, device=device)
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side), torch.no_grad():            # eager warm-up: GEMM plans, derived operands, allocator pools
+                for _ in range(warmup):
+                    self.plan.run(net, self.image)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.no_grad(), torch.cuda.graph(self.graph):
+                self.preds_hard, self.preds_soft = self.plan.run(net, self.image)
+            assert self.preds_soft.shape[1] == num_classes, 'the net has %d classes, not %d' % (self.preds_soft.shape[1], num_classes)
+        except BaseException:                                   # leave the net as it was found
+            if self._folded_here and net.batchnorm_folded:
+                net.unfold_batchnorm()
+            raise
+        self.replays = 0
+
+    def __call__(self, image_batch):
+        if self.graph is None:
+            raise RuntimeError('GraphedSlidingWindow: closed')
+        if self.net.training:
+            raise RuntimeError('GraphedSlidingWindow: the net is in train mode; the captured evaluation is the eval-mode forward')
+        if self.net.batchnorm_folded != self.folded:
+            raise RuntimeError('GraphedSlidingWindow: the BatchNorm fold of the net changed since capture (train(), load_state_dict() or an in-place edit); '
+                               'build a new GraphedSlidingWindow')
+        if tuple(image_batch.shape) != self.plan.shape:
+            raise ValueError('GraphedSlidingWindow: captured for images %r, got %r' % (self.plan.shape, tuple(image_batch.shape)))
+        if image_batch is not self.image:
+            self.image.copy_(image_batch, non_blocking=True)
+        self.graph.replay()
+        self.replays += 1
+        return self.preds_hard, self.preds_soft
+
+    def close(self):
+        """drop the graph and its static tensors; unfold the net if the constructor folded it"""
+        self.graph = self.preds_hard = self.preds_soft = None
+        if self._folded_here and self.net.batchnorm_folded:
+            self.net.unfold_batchnorm()
+        self._folded_here = False
 
 
 # reference function names; not pytest tests

@@ -541,6 +541,18 @@ class SegxLib:
     def harden_segmap(self, acc, cnt, soft, hard, B, C, S, mode, T=0.5):
         self._call('segx_harden_segmap', hard, acc, cnt, soft, hard, B, C, S, mode, T)
 
+    def window_gather(self, image, origins, origins_host, out, nwin, B, C, geom):
+        """origins: device int32 [nwin, 3]; origins_host: a ctypes int32 array holding the same table"""
+        self._chk_t(image, origins, out)
+        g = (c_i * 12)(*[int(v) for v in geom])
+        self.check(self.c.segx_window_gather(_ptr(image), _ptr(origins), origins_host, _ptr(out), nwin, B, C, g, self.stream(out)), 'segx_window_gather')
+
+    def window_merge(self, scores, origins, origins_host, soft, hard, nwin, B, C, geom, mode, T=0.5):
+        self._chk_t(scores, origins, soft, hard)
+        g = (c_i * 15)(*[int(v) for v in geom])
+        self.check(self.c.segx_window_merge(_ptr(scores), _ptr(origins), origins_host, _ptr(soft), _ptr(hard), nwin, B, C, g, mode, T, self.stream(hard)),
+                   'segx_window_merge')
+
     def dice_sums(self, pred, gt, planes, S):
         n = int(self.c.segx_dice_ws_floats(planes, S))
         part = torch.empty(n, dtype=torch.float32, device=pred.device)
@@ -707,7 +719,7 @@ _SIGS = {
     'segx_axis_gather': 'pplpp', 'segx_pixel_shuffle2': 'ppliiip', 'segx_add_noise': 'ppplffiuup', 'segx_resize2d': 'ppliiiiiip', 'segx_color_blend': 'ppilippip',
     'segx_gray_mean_ws_floats': 'il', 'segx_gray_mean': 'pppilip', 'segx_normalize': 'ppiilfppp',
     'segx_x6_presplit_elems': 'iiii', 'segx_x6_presplit': 'piilliillpp',
-    'segx_tune': 'ii', 'segx_tune_get': 'i', 'segx_set_rng_base': 'p', 'segx_rng_advance': 'pup', 'segx_resized_crop3d': 'pplpp', 'segx_stem_compose_fwd': 'ppppiiiiip', 'segx_stem_compose_bwd': 'pppppppiiiiip', 'segx_bridge_input': 'ppiiiiiip', 'segx_stem_s2d_input': 'ppiiiiiip', 'segx_conv2d_stem_fwd': 'pppiiiiiiiiiiip', 'segx_conv2d_stem_im2col': 'ppiiiiiiiiiiip', 'segx_dropout': 'pplfuup', 'segx_avgpool2_fwd': 'ppliip', 'segx_avgpool2_bwd': 'ppliip', 'segx_transpose': 'ppliip', 'segx_interp_linear_fwd_axis': 'pppliilfp', 'segx_window_accum': 'pppiipp', 'segx_harden_segmap': 'ppppiilifp', 'segx_dice_ws_floats': 'll', 'segx_dice_sums': 'pppllp',
+    'segx_tune': 'ii', 'segx_tune_get': 'i', 'segx_set_rng_base': 'p', 'segx_rng_advance': 'pup', 'segx_resized_crop3d': 'pplpp', 'segx_stem_compose_fwd': 'ppppiiiiip', 'segx_stem_compose_bwd': 'pppppppiiiiip', 'segx_bridge_input': 'ppiiiiiip', 'segx_stem_s2d_input': 'ppiiiiiip', 'segx_conv2d_stem_fwd': 'pppiiiiiiiiiiip', 'segx_conv2d_stem_im2col': 'ppiiiiiiiiiiip', 'segx_dropout': 'pplfuup', 'segx_avgpool2_fwd': 'ppliip', 'segx_avgpool2_bwd': 'ppliip', 'segx_transpose': 'ppliip', 'segx_interp_linear_fwd_axis': 'pppliilfp', 'segx_window_accum': 'pppiipp', 'segx_harden_segmap': 'ppppiilifp', 'segx_window_gather': 'ppppiiipp', 'segx_window_merge': 'pppppiiipifp', 'segx_dice_ws_floats': 'll', 'segx_dice_sums': 'pppllp',
     'segx_conv3d_fwd': 'pppiipipp', 'segx_conv3d_fwd_packed': 'pppiipipp', 'segx_conv3d_fwd_packed_bs': 'pppiipipllp', 'segx_conv3d_bwd_weight_packed_bs': 'pppiipipllp', 'segx_conv3d_pack_weights': 'ppiiiip', 'segx_conv3d_splitk': 'iipi', 'segx_conv3d_flip_weights': 'ppiiip', 'segx_conv3d_bwd_weight': 'pppiipipp', 'segx_conv3d_bwd_weight_packed': 'pppiipipp', 'segx_conv3d_unpack_wgrad': 'ppiiip',
     'segx_conv3d_halo_ok': 'iip', 'segx_conv3d_halo_wq_floats': 'ii', 'segx_conv3d_halo_pack': 'ppiiip', 'segx_conv3d_halo_fwd': 'pppiipllip', 'segx_conv3d_halo_wgrad_ok': 'iip', 'segx_conv3d_halo_wgrad_ws_floats': 'iip', 'segx_conv3d_halo_wgrad': 'ppppiipllp',
     'segx_conv3d_bwd_data_direct': 'ppppiipp', 'segx_nonzero_mask': 'ppiiiiiiiip', 'segx_label_nhot': 'ppiilip',
