@@ -90,6 +90,10 @@ int segx_gemm_plan(const float* A, const float* B, const segx_gemm_desc* d, int*
 /* The cost model's pick alone, without the table of measured choices segx_gemm_plan consults first (csrc/gemm_tuned.h): what tools/tune_gemm.py compares
  * its device sweep with when it decides which shapes need a table entry.  Not used on the step. */
 int segx_gemm_plan_model(const float* A, const float* B, const segx_gemm_desc* d, int* tile, int* splitk);
+/* The route segx_gemm_f32 would take for this descriptor (tile / splitk / engine as the call would pass them) under the knobs as they are now; nothing is
+ * launched.  out[0] = kernel family (0 fp32 MFMA, 1 bf16 four-wave, 2 bf16 four-wave with lean loaders, 3 wave-specialised, 4 wave-specialised with a pre-split B,
+ * 5 streaming skinny), out[1] = the SEGX_TILE_* the kernel is built for, out[2] = bf16 products per block (6, 3; 0 off the bf16 tile engine), out[3] = k slabs. */
+int segx_gemm_route(const float* A, const float* B, const segx_gemm_desc* d, int32_t* out);
 /* The three-plane bf16 image of an fp32 operand for segx_gemm_desc.b_planes (bf16x6 engine): W is nb0 x nb1 matrices of rows x K floats
  * with element strides (s_b0, s_b1, s_row, s_k), one of s_row / s_k equal to 1, K % 8 == 0; planes receives, per matrix, [3][rows][K] bf16
  * (x = hi + mid + lo, each step rounded to nearest even: the split the kernels otherwise do in registers), matrices in (z0, z1) order:
@@ -413,10 +417,18 @@ enum {
                                          * L2 (<= 2 MiB) and B is the big operand -- pointwise convolutions over 10^5 positions: B crosses the fabric once instead of once per row of
                                          * tiles --, 0 = N fastest always (rounds 1-5) */
 };
+/* One more id of segx_tune / segx_tune_get, kept OUT of the enum above because it is no tuning knob -- its settings do not give identical results, it selects a
+ * precision: bf16 products per block of segx_gemm_f32's bf16 tile engine.  6 (default) = fp32-equivalent; 3 = hi.mid + mid.hi + hi.hi on two bf16 planes per operand --
+ * accurate to (2^-15 + 2^-16) |A|.|B| per element, an INFERENCE opt-in -- on the routes that have a three-term kernel; every other route runs six-term
+ * (segx_x3_launches tells).  Only 6 and 3 are accepted.  The implicit-GEMM convolutions, the skinny kernel and the fp32 engine do not read it. */
+#define SEGX_KNOB_X6_TERMS 20
 int segx_tune(int knob, int value);
 /* r06: the value a knob holds now (-1 for an unknown knob and for the counter SEGX_KNOB_X6_LAUNCHES): a caller that changes a process-wide default for its own
  * lifetime (dist.GradReducer: SEGX_KNOB_BN_PATH) reads it first and puts it back instead of assuming the default */
 int segx_tune_get(int knob);
+/* Launches of segx_gemm_f32 that ran the three-term product (SEGX_KNOB_X6_TERMS = 3) since the last call; resets the count.  SEGX_KNOB_X6_LAUNCHES keeps counting
+ * every launch on the bf16 tile engine, so "asked for three terms, ran six" is the difference of the two. */
+int segx_x3_launches(void);
 /* r04: TWO adjacent outer axes of a linear resampling in one streaming pass over [outer, n1, n2, inner] (inner % 4 == 0: the contiguous extent, read
  * and written as float4; align_corners = False): the y and z axes of the 3-D feature pyramid's trilinear up-sampling (segtran3d.py:304,319,351,364,384)
  * after the x pass, with the lateral added in the same pass; and the adjoint (z and y before the x pass).  Same blends in the same order as the

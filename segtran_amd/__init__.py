@@ -9,6 +9,13 @@ def sliding_windows(H, W, orig_input_size, stride):
     return f(H, W, orig_input_size, stride)
 
 
+def inference_precision(name):
+    """Context manager: the precision of the bf16 tile engine's GEMMs inside the block (infer2d.inference_precision).  'fp32' (the default behaviour): six bf16
+    products per block, fp32-equivalent; 'bf16x3': three, ~2^-15 relative per product sum -- inference only: entering with gradients enabled raises RuntimeError."""
+    from .infer2d import inference_precision as f
+    return f(name)
+
+
 def __getattr__(name):
     if name == 'GraphedSlidingWindow':          # infer2d.GraphedSlidingWindow: the whole sliding-window evaluation of one image shape as one replayable hipGraph
         from .infer2d import GraphedSlidingWindow

@@ -282,6 +282,7 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
 //   knob 5  is no setting but the counter x6_launches: segx_tune(SEGX_KNOB_X6_LAUNCHES, any) reads and resets it, segx_tune_get answers -1;
 //   knob 6  the product build accepts {0, 1, 6, 7} of its range only: the ablations 2..5 need -DSEGX_BENCH (tools/build_variant.py);
 //   knob 9  must be a multiple of 8;
+//   knob 20 accepts 6 and 3 only (4 and 5 are inside its range and refused);
 //   ids 10 and 11 are retired: both calls answer -1 for them, like for any unknown id.
 #define SEGX_KNOB_TABLE(X)                                                                                                                                        \
     X(1, interp_variant, 0, 0, 2)                    /* interp_linear_fwd kernel: 0 auto, 1 scalar, 2 float4 rows */                                              \
@@ -299,12 +300,14 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
     X(16, conv_halo, 1, 0, 1)                        /* 3 x 3 x 3 stride-1 'same' convolutions on the LDS-resident-halo kernels (conv3d_halo.hip) where they apply; 0 = im2col kernels only */ \
     X(17, conv_halo_min_tiles, 256, 1, 1 << 24)      /* fewest 128-output spatial tiles (x batch) for which the halo kernels are used (below: split-K im2col) */   \
     X(18, skinny_nt, 1, 0, 1)                        /* batch-reduced skinny weight gradients on the streaming kernel (gemm_skinny.hip); 0 = the tile kernels' split-K slabs */ \
-    X(19, tile_walk, 1, 0, 1)                        /* 1 = the GEMM kernels walk M fastest where the A operand fits an XCD's L2 and B is the big one (gemm_core.h tile_walk), 0 = N fastest always (rounds 1-5) */
+    X(19, tile_walk, 1, 0, 1)                        /* 1 = the GEMM kernels walk M fastest where the A operand fits an XCD's L2 and B is the big one (gemm_core.h tile_walk), 0 = N fastest always (rounds 1-5) */ \
+    X(20, x6_terms, 6, 3, 6)                         /* products per block of the bf16 tile engine in segx_gemm_f32: 6 = fp32-equivalent, 3 = hi.mid + mid.hi + hi.hi (~2^-15 relative; inference opt-in) where a three-term kernel is built */
 struct Knobs {
 #define SEGX_KNOB_FIELD(id, field, def, lo, hi) std::atomic<int> field{def};
     SEGX_KNOB_TABLE(SEGX_KNOB_FIELD)
 #undef SEGX_KNOB_FIELD
     std::atomic<int> x6_launches{0};                // knob 5: launches that ran on the bf16x6 engine since the last query
+    std::atomic<int> x3_launches{0};                // segx_x3_launches: those of them (segx_gemm_f32 only) that ran the three-term product
 };
 inline Knobs& knobs() { static Knobs k; return k; }
 inline int kget(const std::atomic<int>& a) { return a.load(std::memory_order_relaxed); }

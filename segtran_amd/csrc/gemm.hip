@@ -37,37 +37,38 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(GemmArgs g) {
 
 // The same GEMM on the bf16x6 engine (gemm_x6.h): fp32 operands split into three bf16 planes on their way into LDS, six bf16 MFMAs per
 // block and 16 k.  WPE = resident waves per SIMD the register allocation must allow (LDS: 48 / 36 / 24 KB per workgroup).
-template <class Cfg, bool AKC, bool BKC, int EPI, int WPE, int VAR = 0>
+// TERMS = 3: the three-term product (two planes per operand: 32 / 24 / 16 KB per workgroup), segx_tune knob 20.
+template <class Cfg, bool AKC, bool BKC, int EPI, int WPE, int VAR = 0, int TERMS = 6>
 __global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(WPE) void gemm_x6_kernel(GemmArgs g) {
-    __shared__ __attribute__((aligned(16))) unsigned char lds[X6Lds<Cfg>::BYTES];
+    __shared__ __attribute__((aligned(16))) unsigned char lds[X6Lds<Cfg, TERMS>::BYTES];
     const TileCoord t = tile_coord<Cfg>(g);
     const DenseLoader6<AKC, Cfg::BM> la{g.A + t.z0 * g.a_b0 + t.z1 * g.a_b1, g.a_m, g.a_k, t.m0, g.M};
     const DenseLoader6<BKC, Cfg::BN> lb{g.B + t.z0 * g.b_b0 + t.z1 * g.b_b1, g.b_n, g.b_k, t.n0, g.N};
     f32x16 acc[Cfg::MI][Cfg::NJ];
-    gemm_mainloop_x6<Cfg, DenseLoader6<AKC, Cfg::BM>, DenseLoader6<BKC, Cfg::BN>, VAR>(acc, la, lb, t.kbeg, t.kend, lds);
+    gemm_mainloop_x6<Cfg, DenseLoader6<AKC, Cfg::BM>, DenseLoader6<BKC, Cfg::BN>, VAR, TERMS>(acc, la, lb, t.kbeg, t.kend, lds);
     gemm_epilogue<EPI, Cfg>(acc, g, t);
 }
 
 // The 4-wave kernel with the LEAN operand loaders of gemm_x6ws.h (one uniform base per k-tile + a 32-bit offset per piece computed once per tile:
 // no per-k-tile address arithmetic on the vector pipe -- ~80 of the ~280 vector instructions a thread issued per k-tile).  Whole 32-k tiles and
 // 32-bit operand offsets only (gemm_ws_ok): the host keeps gemm_x6_kernel for everything else.
-template <class Cfg, bool AKC, bool BKC, int EPI, int WPE>
+template <class Cfg, bool AKC, bool BKC, int EPI, int WPE, int TERMS = 6>
 __global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(WPE) void gemm_x6_lean_kernel(GemmArgs g) {
-    __shared__ __attribute__((aligned(16))) unsigned char lds[X6Lds<Cfg>::BYTES];
+    __shared__ __attribute__((aligned(16))) unsigned char lds[X6Lds<Cfg, TERMS>::BYTES];
     const TileCoord t = tile_coord<Cfg>(g);
     WsDense6<AKC, Cfg::BM> la; WsDense6<BKC, Cfg::BN> lb;
     la.begin(g.A + t.z0 * g.a_b0 + t.z1 * g.a_b1, g.a_m, g.a_k, t.m0, g.M, threadIdx.x);
     lb.begin(g.B + t.z0 * g.b_b0 + t.z1 * g.b_b1, g.b_n, g.b_k, t.n0, g.N, threadIdx.x);
     f32x16 acc[Cfg::MI][Cfg::NJ];
-    gemm_mainloop_x6<Cfg, WsDense6<AKC, Cfg::BM>, WsDense6<BKC, Cfg::BN>, 0>(acc, la, lb, t.kbeg, t.kend, lds);
+    gemm_mainloop_x6<Cfg, WsDense6<AKC, Cfg::BM>, WsDense6<BKC, Cfg::BN>, 0, TERMS>(acc, la, lb, t.kbeg, t.kend, lds);
     gemm_epilogue<EPI, Cfg>(acc, g, t);
 }
 
 // The wave-specialised persistent form (gemm_x6ws.h): 512 threads, one workgroup per CU (144 / 96 KB of LDS), grid = min(items, 256).
-template <class Cfg, bool AKC, bool BKC, int EPI, int PRIO = 0>
+template <class Cfg, bool AKC, bool BKC, int EPI, int PRIO = 0, int TERMS = 6>
 __global__ __launch_bounds__(512) void gemm_x6ws_kernel(GemmArgs g) {
-    __shared__ __attribute__((aligned(16))) unsigned char lds[X6WsLds<Cfg>::BYTES];
-    x6ws_body<Cfg, DenseMk6<Cfg, AKC, BKC>, EPI, PRIO>(g, DenseMk6<Cfg, AKC, BKC>{}, lds);
+    __shared__ __attribute__((aligned(16))) unsigned char lds[X6WsLds<Cfg, TERMS>::BYTES];
+    x6ws_body<Cfg, DenseMk6<Cfg, AKC, BKC>, EPI, PRIO, TERMS>(g, DenseMk6<Cfg, AKC, BKC>{}, lds);
 }
 
 // ... with the B operand split ahead of time (segx_x6_presplit; WsPre6): plain epilogue, whole 32-k stages, 256- or 128-row B tiles
@@ -261,15 +262,36 @@ struct GemmRoute {
     int splitk;      // k slabs (GEMM_SKINNY: x the batch size = its slabs = its grid)
     int ws_grid;     // knob 9: most workgroups of a persistent launch (GEMM_WS, GEMM_WS_PRE)
     bool walk;       // knob 19: the tiles may be walked M fastest (set_tiles)
+    int terms;       // knob 20 as it applies to THIS kernel: 3 = the three-term bf16 product (x3_built()), 6 = the six-term one; 0 off the bf16 tile engine
 };
 static bool ws_tile_id(int tile) { return tile >= SEGX_TILE_256x128 && tile <= SEGX_TILE_WS256x96; }
+// The routes that have a three-term kernel: those the eval forward of the 2-D model takes (launch counters around every GEMM of cfg1 / cfg2 / cfg3 at the fixture
+// and the product shapes, folded and unfolded), all on the product schedule:
+//   wave-specialised, plain, A k-contiguous: 256 x 128, 128 x 128, 128 x 256 and 96 x 256 with B in either layout, 64 x 256 with B row-contiguous, 256 x 96;
+//   four-wave, dense loaders (K no multiple of 32): A k-contiguous, B row-contiguous -- a pointwise convolution -- plain and fused swish, the three tiles;
+//   four-wave, lean loaders: the same; the plain products with a k-contiguous B: NT (nn.Linear, Q.K^T) on 128 x 128 and 64 x 64, A row-contiguous on all three tiles;
+//   the fused GELU (128 x 128, A k-contiguous) with B in either layout.
+// Every other route runs six-term whatever knob 20 says, and the counters show it (segx_x3_launches).
+static bool x3_built(const GemmRoute& r) {
+    if (r.sched != 0) return false;
+    const bool plain = r.epi == SEGX_EPI_NONE, conv = r.akc && !r.bkc;
+    switch (r.family) {
+        case GEMM_WS: return plain && r.akc && (r.tile != SEGX_TILE_WS64x256 || !r.bkc);       // 256 x 96 has a k-contiguous B by its route
+        case GEMM_X6: return conv && r.epi != SEGX_EPI_GELU;
+        case GEMM_X6_LEAN:
+            if (!plain) return r.akc;                        // swish: A k-contiguous, B row-contiguous by the entry point's contract; GELU: A k-contiguous
+            return conv || (r.bkc && (r.tile != SEGX_TILE_64x128 || !r.akc));
+        default: return false;
+    }
+}
 
 // Pure: reads the descriptor, the operand addresses (alignment only) and the knobs -- every knob a launch depends on is read here -- and launches nothing.
 static int gemm_route(const float* A, const float* B, const segx_gemm_desc* d, GemmRoute* out) {
     GemmRoute r;
     r.akc = d->a_k == 1; r.bkc = d->b_k == 1; r.vec = gemm_vec_ok(A, B, d);
     r.epi = d->epilogue; r.sched = 0; r.splitk = d->splitk > 1 ? d->splitk : 1;
-    r.ws_grid = kget(knobs().ws_grid); r.walk = kget(knobs().tile_walk) != 0;
+    r.ws_grid = kget(knobs().ws_grid); r.walk = kget(knobs().tile_walk) != 0; r.terms = 0;
+    const int want_terms = kget(knobs().x6_terms);
     const int nbatch = d->nb0 * d->nb1;
     const bool gelu = d->epilogue == SEGX_EPI_GELU, swish = d->epilogue == SEGX_EPI_SWISH, ws_forced = ws_tile_id(d->tile);
     const int engine = call_engine(d);
@@ -329,6 +351,7 @@ static int gemm_route(const float* A, const float* B, const segx_gemm_desc* d, G
 #endif
         }
     }
+    if (r.family != GEMM_F32) r.terms = want_terms == 3 && x3_built(r) ? 3 : 6;
     *out = r;
     return 0;
 }
@@ -373,8 +396,8 @@ static GemmLaunch f32_kernel(const GemmRoute& r) {
 }
 
 // the four-wave bf16x6 kernels; W = waves per SIMD the tile's registers and LDS allow
-template <bool LEAN, class Cfg, bool AK, bool BK, int E, int W> static GemmKernel x6_form() {
-    if constexpr (LEAN) return gemm_x6_lean_kernel<Cfg, AK, BK, E, W>; else return gemm_x6_kernel<Cfg, AK, BK, E, W>;
+template <bool LEAN, class Cfg, bool AK, bool BK, int E, int W, int T = 6> static GemmKernel x6_form() {
+    if constexpr (LEAN) return gemm_x6_lean_kernel<Cfg, AK, BK, E, W, T>; else return gemm_x6_kernel<Cfg, AK, BK, E, W, 0, T>;
 }
 template <bool LEAN, class Cfg, int W> static GemmLaunch x6_tile(const GemmRoute& r) {
     return built_for<Cfg>(by_layout(r, [](auto ak, auto bk) { return x6_form<LEAN, Cfg, decltype(ak)::value, decltype(bk)::value, SEGX_EPI_NONE, W>(); }));
@@ -391,6 +414,25 @@ template <bool LEAN> static GemmLaunch x6_kernel(const GemmRoute& r) {
         case SEGX_TILE_64x64: return x6_tile<LEAN, Cfg64, 5>(r);
         case SEGX_TILE_64x128: return x6_tile<LEAN, Cfg64x128, 4>(r);
         default: return x6_tile<LEAN, Cfg128, 3>(r);
+    }
+}
+// the three-term forms of the same kernels (exactly what x3_built() names), at the waves per SIMD of their six-term siblings
+template <bool LEAN, class Cfg, int W> static GemmLaunch x3_tile(const GemmRoute& r) {
+    if (r.epi == SEGX_EPI_SWISH) return built_for<Cfg>(x6_form<LEAN, Cfg, true, false, SEGX_EPI_SWISH, W, 3>());
+    if constexpr (LEAN) {
+        if constexpr (std::is_same<Cfg, Cfg64x128>::value) { if (r.bkc) return built_for<Cfg>(x6_form<true, Cfg, false, true, SEGX_EPI_NONE, W, 3>()); }
+        else if (r.bkc) return built_for<Cfg>(by_flag(r.akc, [](auto ak) { return x6_form<true, Cfg, decltype(ak)::value, true, SEGX_EPI_NONE, W, 3>(); }));
+    }
+    return built_for<Cfg>(x6_form<LEAN, Cfg, true, false, SEGX_EPI_NONE, W, 3>());
+}
+template <bool LEAN> static GemmLaunch x3_kernel(const GemmRoute& r) {
+    if constexpr (LEAN) {
+        if (r.epi == SEGX_EPI_GELU) return built_for<Cfg128>(by_flag(r.bkc, [](auto bk) { return x6_form<true, Cfg128, true, decltype(bk)::value, SEGX_EPI_GELU, 3, 3>(); }));
+    }
+    switch (r.tile) {
+        case SEGX_TILE_64x64: return x3_tile<LEAN, Cfg64, 5>(r);
+        case SEGX_TILE_64x128: return x3_tile<LEAN, Cfg64x128, 4>(r);
+        default: return x3_tile<LEAN, Cfg128, 3>(r);
     }
 }
 // the schedule variants of gemm_x6_kernel (plain NT, default tile): <waves per SIMD, VAR>
@@ -431,10 +473,32 @@ static GemmLaunch ws_kernel(const GemmRoute& r) {
         default: return built_for<Cfg256x96>(by_flag(r.akc, [&](auto ak) { return ws_form<Cfg256x96, decltype(ak)::value, true, SEGX_EPI_NONE>(r.sched); }));
     }
 }
+template <class Cfg> static GemmLaunch ws3_tile(const GemmRoute& r) {
+    return built_for<Cfg>(by_flag(r.bkc, [](auto bk) -> GemmKernel { return gemm_x6ws_kernel<Cfg, true, decltype(bk)::value, SEGX_EPI_NONE, 0, 3>; }));
+}
+static GemmLaunch ws3_kernel(const GemmRoute& r) {
+    switch (r.tile) {
+        case SEGX_TILE_256x128: return ws3_tile<Cfg256x128>(r);
+        case SEGX_TILE_WS128x128: return ws3_tile<Cfg128>(r);
+        case SEGX_TILE_WS128x256: return ws3_tile<Cfg128x256>(r);
+        case SEGX_TILE_WS64x256: return built_for<Cfg64x256>(gemm_x6ws_kernel<Cfg64x256, true, false, SEGX_EPI_NONE, 0, 3>);
+        case SEGX_TILE_WS96x256: return ws3_tile<Cfg96x256>(r);
+        default: return built_for<Cfg256x96>(gemm_x6ws_kernel<Cfg256x96, true, true, SEGX_EPI_NONE, 0, 3>);
+    }
+}
 template <class Cfg> static GemmLaunch ws_pre_tile(const GemmRoute& r) {
     return built_for<Cfg>(by_flag(r.akc, [](auto ak) -> GemmKernel { return gemm_x6ws_pre_kernel<Cfg, decltype(ak)::value>; }));
 }
 static GemmLaunch route_kernel(const GemmRoute& r) {
+    if (r.terms == 3) {                                      // gemm_route set it for the forms x3_built() names only
+        switch (r.family) {
+            case GEMM_X6: return x3_kernel<false>(r);
+#ifndef SEGX_NO_LEAN
+            case GEMM_X6_LEAN: return x3_kernel<true>(r);
+#endif
+            default: return ws3_kernel(r);
+        }
+    }
     switch (r.family) {
         case GEMM_X6: return r.sched ? x6_sched_kernel(r.sched) : x6_kernel<false>(r);
 #ifndef SEGX_NO_LEAN
@@ -473,6 +537,19 @@ static void slab_reduce(const segx_gemm_desc* d, float* C, const float* bias, in
 extern "C" int segx_gemm_plan(const float* A, const float* B, const segx_gemm_desc* d, int* tile, int* splitk) { return segx::gemm_plan_impl(A, B, d, tile, splitk, true); }
 // the cost model's own pick, without the measured table (tools/tune_gemm.py compares every candidate with it to decide which shapes need a table entry)
 extern "C" int segx_gemm_plan_model(const float* A, const float* B, const segx_gemm_desc* d, int* tile, int* splitk) { return segx::gemm_plan_impl(A, B, d, tile, splitk, false); }
+
+// the route segx_gemm_f32 would take for this descriptor under the knobs as they are now; launches nothing
+extern "C" int segx_gemm_route(const float* A, const float* B, const segx_gemm_desc* d, int32_t* out) {
+    using namespace segx;
+    SEGX_REQUIRE(A && B && d && out && d->M > 0 && d->N > 0 && d->K > 0 && d->nb0 > 0 && d->nb1 > 0, "segx_gemm_route: bad args");
+    SEGX_REQUIRE(d->tile >= SEGX_TILE_AUTO && d->tile <= SEGX_TILE_SKINNY_NT && d->engine >= SEGX_ENGINE_SEL_DEFAULT && d->engine <= SEGX_ENGINE_SEL_BF16X6,
+                 "segx_gemm_route: bad tile %d or engine selector %d", d->tile, d->engine);
+    GemmRoute r;
+    const int rc = gemm_route(A, B, d, &r);
+    if (rc) return rc;
+    out[0] = r.family; out[1] = r.tile; out[2] = r.terms; out[3] = r.splitk;
+    return 0;
+}
 
 extern "C" int segx_gemm_f32(const float* A, const float* B, float* C, const segx_gemm_desc* d, void* stream_) {
     using namespace segx;
@@ -529,6 +606,7 @@ extern "C" int segx_gemm_f32(const float* A, const float* B, float* C, const seg
     if (splitk > 1 || breduce) g.C = d->workspace;
 
     if (r.family != GEMM_F32) knobs().x6_launches.fetch_add(1, std::memory_order_relaxed);
+    if (r.terms == 3) knobs().x3_launches.fetch_add(1, std::memory_order_relaxed);
     const GemmLaunch k = route_kernel(r);
     set_tiles(g, k, r);
     if (r.family == GEMM_WS || r.family == GEMM_WS_PRE) {

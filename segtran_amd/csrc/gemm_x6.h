@@ -81,17 +81,48 @@ __device__ __forceinline__ Split2 split3_pair(float x0, float x1) {
     s.h = __builtin_bit_cast(unsigned, h); s.m = __builtin_bit_cast(unsigned, m); s.l = __builtin_bit_cast(unsigned, l);
     return s;
 }
+// The two-plane sibling (three-term product, TERMS == 3 below): the hi and mid planes of split3_pair, bit for bit (the same two round-to-nearest-even
+// conversions and the same exact residual), without the third conversion and the second pair of subtractions.
+struct Split2hm { unsigned h, m; };
+__device__ __forceinline__ Split2hm split2_pair(float x0, float x1) {
+    const f32v2 v0 = {x0, x1};
+    const unsigned hb = __builtin_bit_cast(unsigned, __builtin_convertvector(v0, bf16v2));
+    float a0 = x0 - __uint_as_float(hb << 16), a1 = x1 - __uint_as_float(hb & 0xFFFF0000u);
+#if SEGX_X6_SPLIT == 1
+    SEGX_PIN(a0);                                            // as split3_pair: scalar v_sub_f32, not re-packed
+#endif
+    const f32v2 v1 = {a0, a1};
+    Split2hm o; o.h = hb; o.m = __builtin_bit_cast(unsigned, __builtin_convertvector(v1, bf16v2));
+    return o;
+}
+// planes an operand is staged in: three for the six-term product, two (hi, mid) for the three-term one
+constexpr int x6_planes(int terms) { return terms == 3 ? 2 : 3; }
+
 // eight consecutive k of one row -> one 16-byte chunk in each plane
-template <int PLANE_BYTES>
+template <int PLANE_BYTES, int TERMS = 6>
 __device__ __forceinline__ void x6_store8(unsigned char* __restrict__ P, int off, const float (&v)[8]) {
+    if constexpr (TERMS == 3) {
+        const Split2hm a = split2_pair(v[0], v[1]), b = split2_pair(v[2], v[3]), c = split2_pair(v[4], v[5]), d = split2_pair(v[6], v[7]);
+        *reinterpret_cast<uint4*>(P + off) = make_uint4(a.h, b.h, c.h, d.h);
+        *reinterpret_cast<uint4*>(P + PLANE_BYTES + off) = make_uint4(a.m, b.m, c.m, d.m);
+        return;
+    }
     const Split2 a = split3_pair(v[0], v[1]), b = split3_pair(v[2], v[3]), c = split3_pair(v[4], v[5]), d = split3_pair(v[6], v[7]);
     *reinterpret_cast<uint4*>(P + off) = make_uint4(a.h, b.h, c.h, d.h);
     *reinterpret_cast<uint4*>(P + PLANE_BYTES + off) = make_uint4(a.m, b.m, c.m, d.m);
     *reinterpret_cast<uint4*>(P + 2 * PLANE_BYTES + off) = make_uint4(a.l, b.l, c.l, d.l);
 }
 // four consecutive k of one row -> half a chunk (8 bytes) in each plane
-template <int PLANE_BYTES>
+template <int PLANE_BYTES, int TERMS = 6>
 __device__ __forceinline__ void x6_store4(unsigned char* __restrict__ P, int off, float v0, float v1, float v2, float v3) {
+    if constexpr (TERMS == 3) {
+        const Split2hm a = split2_pair(v0, v1), b = split2_pair(v2, v3);
+        uint2 h, m;
+        h.x = a.h; h.y = b.h; m.x = a.m; m.y = b.m;
+        *reinterpret_cast<uint2*>(P + off) = h;
+        *reinterpret_cast<uint2*>(P + PLANE_BYTES + off) = m;
+        return;
+    }
     const Split2 a = split3_pair(v0, v1), b = split3_pair(v2, v3);
     uint2 h, m, l;
     h.x = a.h; h.y = b.h; m.x = a.m; m.y = b.m; l.x = a.l; l.y = b.l;
@@ -124,6 +155,7 @@ template <int PLANE_BYTES> __device__ __forceinline__ void x6_put4(unsigned char
 // Loader concept of this engine: NREG fp32 registers per thread and k-tile;
 //   unsigned load6(float (&r)[NREG], int k0, int kend, int tid) const   global -> registers (unconditional clamped loads) + validity mask
 //   void store6(float (&r)[NREG], unsigned okmask, unsigned char* P, int tid) const   zero the invalid ones, split, write the three planes
+// The dense loaders' store6 is a template on TERMS (6 default; 3: the hi and mid planes only, for the three-term product of gemm_mainloop_x6).
 template <bool KC, int ROWS>
 struct DenseLoader6;
 
@@ -139,6 +171,7 @@ struct DenseLoader6<true, ROWS> {
         for (int i = 0; i < NPT; ++i) { r[4 * i] = t4[i].x; r[4 * i + 1] = t4[i].y; r[4 * i + 2] = t4[i].z; r[4 * i + 3] = t4[i].w; }
         return ok;
     }
+    template <int TERMS = 6>
     __device__ __forceinline__ void store6(float (&r)[NREG], unsigned okmask, unsigned char* __restrict__ P, int tid) const {
         const unsigned full = NPT == 8 ? 0xFFFFFFFFu : ((1u << (4 * NPT)) - 1u);
         if (okmask != full) {
@@ -148,7 +181,7 @@ struct DenseLoader6<true, ROWS> {
 #pragma unroll
         for (int i = 0; i < NPT; ++i) {
             const int f = tid + 256 * i, row = f >> 3, kc = f & 7;
-            x6_store4<X6Plane<ROWS>::bytes>(P, x6_off(row, kc >> 1) + ((kc & 1) << 3), r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]);
+            x6_store4<X6Plane<ROWS>::bytes, TERMS>(P, x6_off(row, kc >> 1) + ((kc & 1) << 3), r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]);
         }
     }
     // split-early form (the split runs under the MFMAs of the previous k-tile, the packed registers are stored after the barrier)
@@ -194,6 +227,7 @@ struct DenseLoader6<false, ROWS> {
         }
         return okmask;
     }
+    template <int TERMS = 6>
     __device__ __forceinline__ void store6(float (&r)[NREG], unsigned okmask, unsigned char* __restrict__ P, int tid) const {
         const unsigned full = NREG >= 32 ? 0xFFFFFFFFu : ((1u << (NREG & 31)) - 1u);
         if (okmask != full) {
@@ -208,13 +242,13 @@ struct DenseLoader6<false, ROWS> {
                 for (int h = 0; h < 2; ++h) {
                     const float v[8] = {r[16 * h + e], r[16 * h + 2 + e], r[16 * h + 4 + e], r[16 * h + 6 + e], r[16 * h + 8 + e], r[16 * h + 10 + e],
                                         r[16 * h + 12 + e], r[16 * h + 14 + e]};
-                    x6_store8<X6Plane<ROWS>::bytes>(P, x6_off(row + e, 2 * kg + h), v);
+                    x6_store8<X6Plane<ROWS>::bytes, TERMS>(P, x6_off(row + e, 2 * kg + h), v);
                 }
             } else if (KQ == 8) {
                 const float v[8] = {r[e], r[2 + e], r[4 + e], r[6 + e], r[8 + e], r[10 + e], r[12 + e], r[14 + e]};
-                x6_store8<X6Plane<ROWS>::bytes>(P, x6_off(row + e, kg), v);
+                x6_store8<X6Plane<ROWS>::bytes, TERMS>(P, x6_off(row + e, kg), v);
             } else {
-                x6_store4<X6Plane<ROWS>::bytes>(P, x6_off(row + e, kg >> 1) + ((kg & 1) << 3), r[e], r[2 + e], r[4 + e], r[6 + e]);
+                x6_store4<X6Plane<ROWS>::bytes, TERMS>(P, x6_off(row + e, kg >> 1) + ((kg & 1) << 3), r[e], r[2 + e], r[4 + e], r[6 + e]);
             }
         }
     }
@@ -253,7 +287,9 @@ struct DenseLoader6<false, ROWS> {
     }
 };
 
-template <class Cfg> struct X6Lds { static constexpr int A_BYTES = 3 * X6Plane<Cfg::BM>::bytes, B_BYTES = 3 * X6Plane<Cfg::BN>::bytes, BYTES = A_BYTES + B_BYTES; };
+template <class Cfg, int TERMS = 6> struct X6Lds {
+    static constexpr int A_BYTES = x6_planes(TERMS) * X6Plane<Cfg::BM>::bytes, B_BYTES = x6_planes(TERMS) * X6Plane<Cfg::BN>::bytes, BYTES = A_BYTES + B_BYTES;
+};
 
 // acc += A_tile . B_tile^T over k in [kbeg, kend).  One LDS stage (48 KB at 128 x 128: three workgroups per CU cover each other's barriers --
 // measured in round 1: occupancy beats double buffering at this tile size), the next k-tile's global loads in flight under the MFMAs.
@@ -263,10 +299,14 @@ template <class Cfg> struct X6Lds { static constexpr int A_BYTES = 3 * X6Plane<C
 // VAR (bench / bisect only, segx_tune knob 6; results are only defined for 0, 1 and 6): 1 = raised wave priority during the MFMA phase;
 // ablations that leave parts of the k-tile loop out to price them: 2 = no split arithmetic, 3 = no LDS stores, 4 = no global loads after the
 // first tile, 5 = MFMAs and fragment reads only (no loads, stores or barriers).
-template <class Cfg, class LA, class LB, int VAR = 0>
+// TERMS (6 default; 3 with VAR 0 only): the three-term product keeps hi.mid, mid.hi and hi.hi of the chain -- the last three, smallest first -- and never
+// forms the lo plane: the loaders split into two planes, the LDS image is two planes per operand (X6Lds<Cfg, 3>), a block costs three matrix instructions
+// and two fragment reads less.  Accurate to ~2^-15 relative instead of fp32-equivalent (DESIGN.md 5m has the bound); swizzle, loads and barriers are unchanged.
+template <class Cfg, class LA, class LB, int VAR = 0, int TERMS = 6>
 __device__ __forceinline__ void gemm_mainloop_x6(f32x16 (&acc)[Cfg::MI][Cfg::NJ], const LA& la, const LB& lb, int kbeg, int kend,
                                                  unsigned char* __restrict__ lds) {
-    constexpr int MI = Cfg::MI, NJ = Cfg::NJ, PA = X6Plane<Cfg::BM>::bytes, PB = X6Plane<Cfg::BN>::bytes;
+    static_assert(TERMS == 6 || (TERMS == 3 && VAR == 0), "gemm_mainloop_x6: six terms, or three on the product schedule");
+    constexpr int MI = Cfg::MI, NJ = Cfg::NJ, PA = X6Plane<Cfg::BM>::bytes, PB = X6Plane<Cfg::BN>::bytes, NP = x6_planes(TERMS);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / Cfg::WN, wn = wave % Cfg::WN;
 #pragma unroll
@@ -277,7 +317,7 @@ __device__ __forceinline__ void gemm_mainloop_x6(f32x16 (&acc)[Cfg::MI][Cfg::NJ]
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     if (kbeg >= kend) return;
     unsigned char* const LA_ = lds;
-    unsigned char* const LB_ = lds + X6Lds<Cfg>::A_BYTES;
+    unsigned char* const LB_ = lds + X6Lds<Cfg, TERMS>::A_BYTES;
     float ra[LA::NREG], rb[LB::NREG];
     unsigned oka = la.load6(ra, kbeg, kend, tid), okb = lb.load6(rb, kbeg, kend, tid);
     const int arow = wm * (32 * MI) + (lane & 31), brow = wn * (32 * NJ) + (lane & 31), kh = lane >> 5;
@@ -338,8 +378,8 @@ __device__ __forceinline__ void gemm_mainloop_x6(f32x16 (&acc)[Cfg::MI][Cfg::NJ]
 #pragma unroll
             for (int e = 0; e + 3 < LB::NREG; e += 4) *reinterpret_cast<float4*>(wb + 1024 * (e / 4)) = make_float4(rb[e], rb[e + 1], rb[e + 2], rb[e + 3]);
         } else if (VAR != 3 && VAR != 5) {
-            la.store6(ra, oka, LA_, tid);
-            lb.store6(rb, okb, LB_, tid);
+            if constexpr (TERMS == 3) { la.template store6<3>(ra, oka, LA_, tid); lb.template store6<3>(rb, okb, LB_, tid); }
+            else { la.store6(ra, oka, LA_, tid); lb.store6(rb, okb, LB_, tid); }
         } else if (VAR == 3) {                            // keep the loaded values alive without storing them
 #pragma unroll
             for (int e = 0; e < LA::NREG; ++e) asm volatile("" :: "v"(ra[e]));
@@ -359,35 +399,42 @@ __device__ __forceinline__ void gemm_mainloop_x6(f32x16 (&acc)[Cfg::MI][Cfg::NJ]
     C = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_[0], B_[1], C, 0, 0, 0);     /* hi . mid  */                \
     C = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_[1], B_[0], C, 0, 0, 0);     /* mid . hi  */                \
     C = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_[0], B_[0], C, 0, 0, 0);     /* hi . hi   */
+#define SEGX_X6_MFMA3(C, A_, B_)                                                                               \
+    C = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_[0], B_[1], C, 0, 0, 0);     /* hi . mid  */                \
+    C = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_[1], B_[0], C, 0, 0, 0);     /* mid . hi  */                \
+    C = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_[0], B_[0], C, 0, 0, 0);     /* hi . hi   */
+#define SEGX_X6_CHAIN(C, A_, B_) if constexpr (TERMS == 3) { SEGX_X6_MFMA3(C, A_, B_) } else { SEGX_X6_MFMA6(C, A_, B_) }
             if (MI > NJ) {                                // tall wave tile: the NJ x 3 B fragments stay, the A fragments stream one row block at a time
-                bf16x8 b[NJ][3];
+                bf16x8 b[NJ][NP];
 #pragma unroll
                 for (int j = 0; j < NJ; ++j)
 #pragma unroll
-                    for (int p = 0; p < 3; ++p) b[j][p] = *reinterpret_cast<const bf16x8*>(LB_ + p * PB + x6_off(brow + 32 * j, chunk));
+                    for (int p = 0; p < NP; ++p) b[j][p] = *reinterpret_cast<const bf16x8*>(LB_ + p * PB + x6_off(brow + 32 * j, chunk));
 #pragma unroll
                 for (int i = 0; i < MI; ++i) {
-                    bf16x8 a[3];
+                    bf16x8 a[NP];
 #pragma unroll
-                    for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const bf16x8*>(LA_ + p * PA + x6_off(arow + 32 * i, chunk));
+                    for (int p = 0; p < NP; ++p) a[p] = *reinterpret_cast<const bf16x8*>(LA_ + p * PA + x6_off(arow + 32 * i, chunk));
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j) { f32x16 c = acc[i][j]; SEGX_X6_MFMA6(c, a, b[j]) acc[i][j] = c; }
+                    for (int j = 0; j < NJ; ++j) { f32x16 c = acc[i][j]; SEGX_X6_CHAIN(c, a, b[j]) acc[i][j] = c; }
                 }
             } else {                                      // the MI x 3 A fragments stay, one column block of B at a time
-                bf16x8 a[MI][3];
+                bf16x8 a[MI][NP];
 #pragma unroll
                 for (int i = 0; i < MI; ++i)
 #pragma unroll
-                    for (int p = 0; p < 3; ++p) a[i][p] = *reinterpret_cast<const bf16x8*>(LA_ + p * PA + x6_off(arow + 32 * i, chunk));
+                    for (int p = 0; p < NP; ++p) a[i][p] = *reinterpret_cast<const bf16x8*>(LA_ + p * PA + x6_off(arow + 32 * i, chunk));
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) {
-                    bf16x8 b[3];
+                    bf16x8 b[NP];
 #pragma unroll
-                    for (int p = 0; p < 3; ++p) b[p] = *reinterpret_cast<const bf16x8*>(LB_ + p * PB + x6_off(brow + 32 * j, chunk));
+                    for (int p = 0; p < NP; ++p) b[p] = *reinterpret_cast<const bf16x8*>(LB_ + p * PB + x6_off(brow + 32 * j, chunk));
 #pragma unroll
-                    for (int i = 0; i < MI; ++i) { f32x16 c = acc[i][j]; SEGX_X6_MFMA6(c, a[i], b) acc[i][j] = c; }
+                    for (int i = 0; i < MI; ++i) { f32x16 c = acc[i][j]; SEGX_X6_CHAIN(c, a[i], b) acc[i][j] = c; }
                 }
             }
+#undef SEGX_X6_CHAIN
+#undef SEGX_X6_MFMA3
 #undef SEGX_X6_MFMA6
         }
         if (VAR == 1) __builtin_amdgcn_s_setprio(0);

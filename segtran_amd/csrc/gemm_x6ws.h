@@ -26,7 +26,7 @@
 
 namespace segx {
 
-template <class Cfg> struct X6WsLds { static constexpr int STAGE = X6Lds<Cfg>::BYTES, BYTES = 2 * STAGE; };
+template <class Cfg, int TERMS = 6> struct X6WsLds { static constexpr int STAGE = X6Lds<Cfg, TERMS>::BYTES, BYTES = 2 * STAGE; };
 
 // work item `item` of a persistent launch -> tile coordinates (tile fastest, N fastest inside: neighbours share operand panels), then batch, then k-slab
 template <class Cfg>
@@ -49,28 +49,30 @@ __device__ __forceinline__ TileCoord ws_item_coord(const GemmArgs& g, int item) 
 __device__ __forceinline__ int ws_round_pos(int b, int G) { return (b & 7) * (G >> 3) + (b >> 3); }
 
 // one 32-k stage of matrix work of a consumer wave: acc[i][j] += A(rows arow + 32 i) . B(rows brow + 32 j)^T from the three-plane LDS images
-template <class Cfg>
+// (TERMS == 3: from the two-plane images, the last three products of the chain: hi.mid, mid.hi, hi.hi)
+template <class Cfg, int TERMS = 6>
 __device__ __forceinline__ void x6ws_stage_mfma(f32x16 (&acc)[Cfg::MI][Cfg::NJ], const unsigned char* __restrict__ LA_, const unsigned char* __restrict__ LB_,
                                                 int arow, int brow, int kh) {
-    constexpr int MI = Cfg::MI, NJ = Cfg::NJ, PA = X6Plane<Cfg::BM>::bytes, PB = X6Plane<Cfg::BN>::bytes;
+    constexpr int MI = Cfg::MI, NJ = Cfg::NJ, PA = X6Plane<Cfg::BM>::bytes, PB = X6Plane<Cfg::BN>::bytes, NP = x6_planes(TERMS);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         const int chunk = 2 * s + kh;                     // lane -> (row lane & 31, the 8 k of half lane >> 5 of this 16-k step)
-        bf16x8 b[NJ][3];
+        bf16x8 b[NJ][NP];
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
 #pragma unroll
-            for (int p = 0; p < 3; ++p) b[j][p] = *reinterpret_cast<const bf16x8*>(LB_ + p * PB + x6_off(brow + 32 * j, chunk));
+            for (int p = 0; p < NP; ++p) b[j][p] = *reinterpret_cast<const bf16x8*>(LB_ + p * PB + x6_off(brow + 32 * j, chunk));
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
-            bf16x8 a[3];
+            bf16x8 a[NP];
 #pragma unroll
-            for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const bf16x8*>(LA_ + p * PA + x6_off(arow + 32 * i, chunk));
+            for (int p = 0; p < NP; ++p) a[p] = *reinterpret_cast<const bf16x8*>(LA_ + p * PA + x6_off(arow + 32 * i, chunk));
             // six products per accumulator, small terms first (the order of gemm_x6.h); consecutive matrix instructions go to DIFFERENT
             // accumulators so that none waits for its predecessor's result
 #define SEGX_X6WS_P(PA_, PB_)                                                                                              \
     _Pragma("unroll") for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA_], b[j][PB_], acc[i][j], 0, 0, 0);
-            SEGX_X6WS_P(0, 2) SEGX_X6WS_P(2, 0) SEGX_X6WS_P(1, 1) SEGX_X6WS_P(0, 1) SEGX_X6WS_P(1, 0) SEGX_X6WS_P(0, 0)
+            if constexpr (TERMS == 6) { SEGX_X6WS_P(0, 2) SEGX_X6WS_P(2, 0) SEGX_X6WS_P(1, 1) }
+            SEGX_X6WS_P(0, 1) SEGX_X6WS_P(1, 0) SEGX_X6WS_P(0, 0)
 #undef SEGX_X6WS_P
         }
     }
@@ -100,7 +102,7 @@ struct X6WsStream {
 };
 
 // a producer's register set -> the three-plane LDS images of one stage (VAR: the bench ablations of x6ws_body)
-template <int VAR, class Cfg, class LA, class LB, int A_BYTES_ = X6Lds<Cfg>::A_BYTES>
+template <int VAR, class Cfg, class LA, class LB, int A_BYTES_ = X6Lds<Cfg>::A_BYTES, int TERMS = 6>
 __device__ __forceinline__ void x6ws_put(const LA& la, const LB& lb, float (&ra)[LA::NREG], float (&rb)[LB::NREG], unsigned oka, unsigned okb,
                                          unsigned char* __restrict__ P, int ptid) {
     if (VAR == 2) {                                        // stores of the same width and count without the conversion arithmetic
@@ -123,16 +125,19 @@ __device__ __forceinline__ void x6ws_put(const LA& la, const LB& lb, float (&ra)
         for (int e = 0; e < LA::NREG; ++e) asm volatile("" :: "v"(ra[e]));
 #pragma unroll
         for (int e = 0; e < LB::NREG; ++e) asm volatile("" :: "v"(rb[e]));
-    } else { la.store6(ra, oka, P, ptid); lb.store6(rb, okb, P + A_BYTES_, ptid); }
+    } else if constexpr (TERMS == 3) { la.template store6<3>(ra, oka, P, ptid); lb.template store6<3>(rb, okb, P + A_BYTES_, ptid); }
+    else { la.store6(ra, oka, P, ptid); lb.store6(rb, okb, P + A_BYTES_, ptid); }
 }
 
 // EPI as gemm_epilogue.  PRIO (segx_tune knob 6; results are only defined for 0 and 1): 1 = consumers run at raised wave priority; ablations that
 // price the producers' parts: 2 = no split arithmetic (raw bits stored), 3 = no global loads after a work item's first stage, 4 = no LDS stores,
 // 5 = producers only keep the barrier count (what the consumers reach alone).
-template <class Cfg, class MK, int EPI, int PRIO = 0>
+// TERMS == 3 (PRIO 0 or 1): two planes per operand and stage, three products per accumulator and 16 k; the item stream, the barriers and the epilogue are the same.
+template <class Cfg, class MK, int EPI, int PRIO = 0, int TERMS = 6>
 __device__ __forceinline__ void x6ws_body(const GemmArgs& g, const MK& mk, unsigned char* __restrict__ lds) {
     using LA = typename MK::LA; using LB = typename MK::LB;
-    constexpr int STAGE = X6Lds<Cfg>::BYTES, A_BYTES = X6Lds<Cfg>::A_BYTES;
+    static_assert(TERMS == 6 || (TERMS == 3 && PRIO <= 1), "x6ws_body: six terms, or three without the ablations");
+    constexpr int STAGE = X6Lds<Cfg, TERMS>::BYTES, A_BYTES = X6Lds<Cfg, TERMS>::A_BYTES;
     const int wave = SEGX_WAVE_UNIFORM((int)(threadIdx.x >> 6));
     const int G = gridDim.x, pos = ws_round_pos(blockIdx.x, G);
     const int total = g.tiles_m * g.tiles_n * g.nbatch * g.splitk;
@@ -156,7 +161,7 @@ __device__ __forceinline__ void x6ws_body(const GemmArgs& g, const MK& mk, unsig
         bool have1 = st.valid, have0;
         oka1 = st.la.load6(a1, st.k, st.kend, ptid); okb1 = st.lb.load6(b1, st.k, st.kend, ptid);
         r_seen = st.r; st.next(g, mk, pos, G, total);
-        x6ws_put<PRIO, Cfg, typename MK::LA, typename MK::LB, A_BYTES>(st.la, st.lb, a0, b0, oka0, okb0, lds, ptid);        // stage 0 -> buffer 0
+        x6ws_put<PRIO, Cfg, typename MK::LA, typename MK::LB, A_BYTES, TERMS>(st.la, st.lb, a0, b0, oka0, okb0, lds, ptid);        // stage 0 -> buffer 0
         int par = 0;
         for (;;) {
             SEGX_LDS_BARRIER();                            // the stage in buffer `par` is complete; buffer par ^ 1 has been read to the end
@@ -165,14 +170,14 @@ __device__ __forceinline__ void x6ws_body(const GemmArgs& g, const MK& mk, unsig
             have0 = st.valid;
             if (!((PRIO == 3 || PRIO == 5) && st.r == r_seen)) { oka0 = st.la.load6(a0, st.k, st.kend, ptid); okb0 = st.lb.load6(b0, st.k, st.kend, ptid); }
             r_seen = st.r; st.next(g, mk, pos, G, total);
-            if (PRIO != 5) x6ws_put<PRIO, Cfg, typename MK::LA, typename MK::LB, A_BYTES>(st.la, st.lb, a1, b1, oka1, okb1, lds + par * STAGE, ptid);
+            if (PRIO != 5) x6ws_put<PRIO, Cfg, typename MK::LA, typename MK::LB, A_BYTES, TERMS>(st.la, st.lb, a1, b1, oka1, okb1, lds + par * STAGE, ptid);
             SEGX_LDS_BARRIER();
             par ^= 1;
             if (!have0) break;
             have1 = st.valid;
             if (!((PRIO == 3 || PRIO == 5) && st.r == r_seen)) { oka1 = st.la.load6(a1, st.k, st.kend, ptid); okb1 = st.lb.load6(b1, st.k, st.kend, ptid); }
             r_seen = st.r; st.next(g, mk, pos, G, total);
-            if (PRIO != 5) x6ws_put<PRIO, Cfg, typename MK::LA, typename MK::LB, A_BYTES>(st.la, st.lb, a0, b0, oka0, okb0, lds + par * STAGE, ptid);
+            if (PRIO != 5) x6ws_put<PRIO, Cfg, typename MK::LA, typename MK::LB, A_BYTES, TERMS>(st.la, st.lb, a0, b0, oka0, okb0, lds + par * STAGE, ptid);
         }
         return;
     }
@@ -196,7 +201,7 @@ __device__ __forceinline__ void x6ws_body(const GemmArgs& g, const MK& mk, unsig
         for (int kt = t.kbeg; kt < t.kend; kt += BKT) {
             SEGX_LDS_BARRIER();
             const unsigned char* const P = lds + par * STAGE;
-            x6ws_stage_mfma<Cfg>(acc, P, P + A_BYTES, arow, brow, kh);
+            x6ws_stage_mfma<Cfg, TERMS>(acc, P, P + A_BYTES, arow, brow, kh);
             par ^= 1;
         }
         gemm_epilogue<EPI, Cfg, false>(acc, g, t);        // an empty split-K slab writes zeros

@@ -5,6 +5,7 @@ extern "C" int segx_tune(int knob, int value) {
     segx::Knobs& k = segx::knobs();
     if (knob == 5) return k.x6_launches.exchange(0);                                              // the launch counter: read and reset
     if (knob == 9 && value % 8) return -1;
+    if (knob == 20 && value != 6 && value != 3) return -1;
 #ifndef SEGX_BENCH
     if (knob == 6 && value >= 2 && value <= 5) return -1;                                         // ablations whose results are NOT the GEMM
 #endif
@@ -24,3 +25,4 @@ extern "C" int segx_tune_get(int knob) {
         default: return -1;
     }
 }
+extern "C" int segx_x3_launches(void) { return segx::knobs().x3_launches.exchange(0); }         // read and reset, like knob 5

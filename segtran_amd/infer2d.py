@@ -25,6 +25,37 @@ def _folded(net, fold_bn):
             net.unfold_batchnorm()
 
 
+PRECISIONS = {'fp32': 6, 'bf16x3': 3}           # name -> Knob.X6_TERMS: bf16 products per block of the bf16 tile engine
+
+
+@contextlib.contextmanager
+def inference_precision(name):
+    """with inference_precision('bf16x3'): the GEMMs of the bf16 tile engine run the three-term product (hi.mid + mid.hi + hi.hi on two bf16 planes per operand) on
+    the routes that have such a kernel -- accurate to (2^-15 + 2^-16) |A|.|B| per element instead of fp32-equivalent; 'fp32' is the default behaviour.
+    The setting is process-wide for the duration of the block (segx_tune knob X6_TERMS) and the value it held comes back at the end, also after an exception.
+    Inference only: the training parity bar rules the mode out, so entering with gradients enabled raises RuntimeError; an unknown name raises ValueError."""
+    if name not in PRECISIONS:
+        raise ValueError('inference_precision: %r is not one of %s' % (name, sorted(PRECISIONS)))
+    if torch.is_grad_enabled():
+        raise RuntimeError("inference_precision(%r) is for inference: enter it under torch.no_grad()" % (name,))
+    from . import segx
+    with segx.lib().tuned(x6_terms=PRECISIONS[name]):
+        yield
+
+
+@contextlib.contextmanager
+def _precision(precision):
+    """the `precision` argument of the evaluation entry points: 'fp32' leaves everything as the caller has it, 'bf16x3' runs the block without gradients inside
+    inference_precision('bf16x3')"""
+    if precision not in PRECISIONS:
+        raise ValueError('precision: %r is not one of %s' % (precision, sorted(PRECISIONS)))
+    if precision == 'fp32':
+        yield
+    else:
+        with torch.no_grad(), inference_precision(precision):
+            yield
+
+
 def sliding_windows(H, W, orig_input_size, stride):
     """The window geometry of test_util2d.test_single_batch for an H x W image: ((hl_pad, wl_pad), (H2, W2), origins) -- the left pads, the padded extent and
     the (xs, ys) origin of every window in padded coordinates, visited x-outer, y-inner, the last row / column clamped to extent - window.  A stride above its
@@ -85,15 +116,16 @@ class _Plan:
 
 
 def test_single_batch(net, image_batch, orig_input_size, patch_size, stride, task_name, num_classes, model_type='segtran', fold_bn=False, fused=False,
-                      window_batch=None):
+                      window_batch=None, precision='fp32'):
     """test_util2d.test_single_batch; fold_bn: with the backbone's BatchNorm layers folded into its convolutions for this call.
     fused: one window_gather launch, net() on chunks of `window_batch` windows (window_batch * B samples each; default: all windows in one call, or the largest chunks
     max_stacked_samples(net) allows), one
     window_merge launch -- no canvas copy, no per-window accumulate pass.  With window_batch=1 the forwards are the eager path's, and so are the results, bit
-    for bit; stacked windows change the GEMMs' shapes, hence the summation order inside the network."""
+    for bit; stacked windows change the GEMMs' shapes, hence the summation order inside the network.
+    precision: 'fp32' (default) or 'bf16x3' -- the forwards run inside inference_precision(precision)."""
     if fused and model_type not in ('segtran',):
         raise NotImplementedError("model_type '%s': only segtran is built" % model_type)
-    with _folded(net, fold_bn):
+    with _precision(precision), _folded(net, fold_bn):
         if not fused:
             return _T2.test_single_batch(net, image_batch, orig_input_size, patch_size, stride, task_name, num_classes, model_type)
         plan = _Plan(net, image_batch.shape, orig_input_size, patch_size, stride, image_batch.device, window_batch)
@@ -102,9 +134,9 @@ def test_single_batch(net, image_batch, orig_input_size, patch_size, stride, tas
 
 
 def test_all_cases(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, mask_prepred_mapping_func=None, fold_bn=False, fused=False,
-                   window_batch=None):
-    """test_util2d.test_all_cases; fold_bn: ONE fold for all the batches; fused / window_batch: as test_single_batch."""
-    with _folded(net, fold_bn):
+                   window_batch=None, precision='fp32'):
+    """test_util2d.test_all_cases; fold_bn: ONE fold for all the batches; fused / window_batch / precision: as test_single_batch."""
+    with _precision(precision), _folded(net, fold_bn):
         if not fused:
             return _T2.test_all_cases(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, mask_prepred_mapping_func)
         total, count = _T2.np.zeros(num_classes - 1), 0
@@ -124,12 +156,17 @@ class GraphedSlidingWindow:
     folded.  __call__(image_batch) copies the batch into a static buffer, replays and returns (preds_hard int32, preds_soft) [B, num_classes, H, W]: STATIC
     tensors that the next call overwrites -- clone what must outlive it.  The captured kernels read the weights (and the folded operands) at fixed addresses, so
     a call raises RuntimeError once the net was put in train mode or its fold state differs from the one captured (train(), load_state_dict() and in-place edits
-    of a folded tensor all drop the fold)."""
+    of a folded tensor all drop the fold).
+    precision ('fp32' default, 'bf16x3'): warm-up and capture run inside inference_precision(precision); a GEMM's route is fixed when it is captured, so a
+    replay needs no setting and leaves none behind.  The object reports it as .precision."""
 
-    def __init__(self, net, image_shape, orig_input_size, patch_size, stride, num_classes, fold_bn=True, window_batch=None, warmup=2):
+    def __init__(self, net, image_shape, orig_input_size, patch_size, stride, num_classes, fold_bn=True, window_batch=None, warmup=2, precision='fp32'):
         from . import segx
         if net.training:
             raise RuntimeError('GraphedSlidingWindow is for inference: call net.eval() first')
+        if precision not in PRECISIONS:
+            raise ValueError('precision: %r is not one of %s' % (precision, sorted(PRECISIONS)))
+        self.precision = precision
         assert segx.lib().gemm_prof is None, 'per-launch event profiling cannot run inside a captured evaluation'
         device = next(net.parameters()).device
         self.net, self.num_classes = net, num_classes
@@ -142,13 +179,13 @@ class GraphedSlidingWindow:
             self.image = torch.zeros(self.plan.shape, dtype=torch.float32, device=device)
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side), torch.no_grad():            # eager warm-up: GEMM plans, derived operands, allocator pools
+            with torch.cuda.stream(side), torch.no_grad(), _precision(precision):   # eager warm-up: GEMM plans, derived operands, allocator pools
                 for _ in range(warmup):
                     self.plan.run(net, self.image)
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             self.graph = torch.cuda.CUDAGraph()
-            with torch.no_grad(), torch.cuda.graph(self.graph):
+            with torch.no_grad(), _precision(precision), torch.cuda.graph(self.graph):
                 self.preds_hard, self.preds_soft = self.plan.run(net, self.image)
             assert self.preds_soft.shape[1] == num_classes, 'the net has %d classes, not %d' % (self.preds_soft.shape[1], num_classes)
         except BaseException:                                   # leave the net as it was found

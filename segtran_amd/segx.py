@@ -60,6 +60,20 @@ class Knob(enum.IntEnum):
     TILE_WALK = 19
 
 
+# SEGX_KNOB_X6_TERMS of include/segx.h: an id of segx_tune like the others, but a precision selector (6 or 3 bf16 products per block), not a tuning knob whose
+# settings all give the same results -- so, as in the header, it is no member of the enumeration; Knob.X6_TERMS and tuned(x6_terms=...) work like a member's
+# (tests/test_x3_precision.py holds header, this value and the library's table equal)
+Knob.X6_TERMS = 20
+
+
+def knob_id(name):
+    """'ws_grid' / 'x6_terms' -> the id segx_tune takes"""
+    v = getattr(Knob, name.upper(), None)
+    if not isinstance(v, int) or name.upper().startswith('_'):
+        raise KeyError(name)
+    return v
+
+
 def _ptr(t):
     return None if t is None else t.data_ptr()       # a plain int: ctypes converts it for a c_void_p parameter without an object per argument
 
@@ -111,7 +125,7 @@ class SegxLib:
     def tuned(self, **settings):
         """with L.tuned(ws_grid=8, skinny_nt=0): ... -- knobs by their lower-case Knob names, set for the block; the values they HELD (segx_tune_get, not
         the defaults) come back at its end."""
-        knobs = [Knob[name.upper()] for name in settings]
+        knobs = [knob_id(name) for name in settings]
         held = [(k, self.c.segx_tune_get(k)) for k in knobs]
         for k, v in held:
             if v < 0:                                        # Knob.X6_LAUNCHES is a counter, not a setting: nothing to put back
@@ -134,6 +148,11 @@ class SegxLib:
     def x6_launches(self):
         """launches that ran on the bf16x6 engine since the last call"""
         return int(self.c.segx_tune(Knob.X6_LAUNCHES, 0))
+
+    def x3_launches(self):
+        """launches of gemm() that ran the three-term bf16 product (Knob.X6_TERMS = 3) since the last call; x6_launches() - x3_launches() of the same span
+        asked for three terms and ran six"""
+        return int(self.c.segx_x3_launches())
 
     # ---- team exchange: loud failure (include/segx.h: segx_team_status) ---------------------------------
     def team_check(self):
@@ -220,6 +239,21 @@ class SegxLib:
         else:
             rc = self.c.segx_gemm_f32(_ptr(A), _ptr(B), _ptr(C), ctypes.byref(d), self.stream(C))
         self.check(rc, 'segx_gemm_f32')
+
+    ROUTE_FAMILIES = ('f32', 'x6', 'x6_lean', 'ws', 'ws_pre', 'skinny')
+
+    def gemm_route(self, A, B, M, N, K, a_strides, b_strides, nb=(1, 1), epilogue=EPI_NONE, splitk=1, tile=TILE_AUTO, engine=None):
+        """(family name, tile, terms, k slabs) of the kernel gemm() would launch for these operands under the knobs as they are now (segx_gemm_route)"""
+        self._chk_t(A, B)
+        d = GemmDesc()
+        d.M, d.N, d.K, d.nb0, d.nb1 = M, N, K, nb[0], nb[1]
+        d.a_b0, d.a_b1, d.a_m, d.a_k = a_strides
+        d.b_b0, d.b_b1, d.b_n, d.b_k = b_strides
+        d.epilogue, d.splitk, d.tile = epilogue, splitk, tile
+        d.engine = 0 if engine is None else 1 + self.ENGINES[engine]
+        out = (c_i * 4)()
+        self.check(self.c.segx_gemm_route(_ptr(A), _ptr(B), ctypes.byref(d), out), 'segx_gemm_route')
+        return self.ROUTE_FAMILIES[out[0]], out[1], out[2], out[3]
 
     def x6_presplit(self, W, rows, K, s_row, s_k, nb=(1, 1), s_b=(0, 0)):
         """Three-plane bf16 image of an fp32 operand (segx_x6_presplit) for gemm(b_planes=...): returns (planes, bp_b0, bp_b1).  A batch dimension
@@ -719,7 +753,7 @@ _SIGS = {
     'segx_axis_gather': 'pplpp', 'segx_pixel_shuffle2': 'ppliiip', 'segx_add_noise': 'ppplffiuup', 'segx_resize2d': 'ppliiiiiip', 'segx_color_blend': 'ppilippip',
     'segx_gray_mean_ws_floats': 'il', 'segx_gray_mean': 'pppilip', 'segx_normalize': 'ppiilfppp',
     'segx_x6_presplit_elems': 'iiii', 'segx_x6_presplit': 'piilliillpp',
-    'segx_tune': 'ii', 'segx_tune_get': 'i', 'segx_set_rng_base': 'p', 'segx_rng_advance': 'pup', 'segx_resized_crop3d': 'pplpp', 'segx_stem_compose_fwd': 'ppppiiiiip', 'segx_stem_compose_bwd': 'pppppppiiiiip', 'segx_bridge_input': 'ppiiiiiip', 'segx_stem_s2d_input': 'ppiiiiiip', 'segx_conv2d_stem_fwd': 'pppiiiiiiiiiiip', 'segx_conv2d_stem_im2col': 'ppiiiiiiiiiiip', 'segx_dropout': 'pplfuup', 'segx_avgpool2_fwd': 'ppliip', 'segx_avgpool2_bwd': 'ppliip', 'segx_transpose': 'ppliip', 'segx_interp_linear_fwd_axis': 'pppliilfp', 'segx_window_accum': 'pppiipp', 'segx_harden_segmap': 'ppppiilifp', 'segx_window_gather': 'ppppiiipp', 'segx_window_merge': 'pppppiiipifp', 'segx_dice_ws_floats': 'll', 'segx_dice_sums': 'pppllp',
+    'segx_tune': 'ii', 'segx_tune_get': 'i', 'segx_x3_launches': '', 'segx_gemm_route': 'pppp', 'segx_set_rng_base': 'p', 'segx_rng_advance': 'pup', 'segx_resized_crop3d': 'pplpp', 'segx_stem_compose_fwd': 'ppppiiiiip', 'segx_stem_compose_bwd': 'pppppppiiiiip', 'segx_bridge_input': 'ppiiiiiip', 'segx_stem_s2d_input': 'ppiiiiiip', 'segx_conv2d_stem_fwd': 'pppiiiiiiiiiiip', 'segx_conv2d_stem_im2col': 'ppiiiiiiiiiiip', 'segx_dropout': 'pplfuup', 'segx_avgpool2_fwd': 'ppliip', 'segx_avgpool2_bwd': 'ppliip', 'segx_transpose': 'ppliip', 'segx_interp_linear_fwd_axis': 'pppliilfp', 'segx_window_accum': 'pppiipp', 'segx_harden_segmap': 'ppppiilifp', 'segx_window_gather': 'ppppiiipp', 'segx_window_merge': 'pppppiiipifp', 'segx_dice_ws_floats': 'll', 'segx_dice_sums': 'pppllp',
     'segx_conv3d_fwd': 'pppiipipp', 'segx_conv3d_fwd_packed': 'pppiipipp', 'segx_conv3d_fwd_packed_bs': 'pppiipipllp', 'segx_conv3d_bwd_weight_packed_bs': 'pppiipipllp', 'segx_conv3d_pack_weights': 'ppiiiip', 'segx_conv3d_splitk': 'iipi', 'segx_conv3d_flip_weights': 'ppiiip', 'segx_conv3d_bwd_weight': 'pppiipipp', 'segx_conv3d_bwd_weight_packed': 'pppiipipp', 'segx_conv3d_unpack_wgrad': 'ppiiip',
     'segx_conv3d_halo_ok': 'iip', 'segx_conv3d_halo_wq_floats': 'ii', 'segx_conv3d_halo_pack': 'ppiiip', 'segx_conv3d_halo_fwd': 'pppiipllip', 'segx_conv3d_halo_wgrad_ok': 'iip', 'segx_conv3d_halo_wgrad_ws_floats': 'iip', 'segx_conv3d_halo_wgrad': 'ppppiipllp',
     'segx_conv3d_bwd_data_direct': 'ppppiipp', 'segx_nonzero_mask': 'ppiiiiiiiip', 'segx_label_nhot': 'ppiilip',
