@@ -492,6 +492,11 @@ int segx_interp_linear_bwd_axis(const float* dout, float* din, int64_t outer, in
 /* splitk > 1: the contraction (Cin*KV) is split over slabs in `workspace` (splitk*B*Cout*P floats) and reduced deterministically;
  * segx_conv3d_splitk returns the library's choice for the forward (wgrad = 0) or weight-gradient (wgrad = 1) GEMM */
 int64_t segx_conv3d_splitk(int B, int Cout, const int* geom, int wgrad);
+/* The route segx_conv3d_fwd* (wgrad = 0) / segx_conv3d_bwd_weight* (wgrad = 1) would take with this split factor under the knobs as they are now; nothing is
+ * launched.  aligned: the filters (forward) / dY (weight gradient) start on 16 bytes; packed: the *_packed entry points.  out (int32[9]): [0] = engine (0 fp32 MFMA,
+ * 1 bf16x6), [1] = output channels per tile (64 / 128), [2] = 16-byte loads of the dense operand, [3] = packed, [4] = the bf16x6 weight gradient's loader form
+ * (0 per-position decode, 1 rows of eight floats / two quads, 2 contiguous octet), [5] = k slabs, [6..8] = grid x, y, z */
+int segx_conv3d_route(int B, int Cout, const int* geom, int wgrad, int splitk, int aligned, int packed, int32_t* out);
 int segx_conv3d_fwd(const float* X, const float* W /* [Cout][Cin][KD][KH][KW] */, float* Y, int B, int Cout, const int* geom, int splitk,
                     float* workspace, void* stream);
 /* Packed contraction order for Cin % 8 == 0: k runs (channel block of 8, tap, channel in block), so eight consecutive k share one tap and

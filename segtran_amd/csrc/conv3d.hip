@@ -1236,6 +1236,75 @@ static bool pool_is_s1k3_same(const PoolGeom& q) {
 static bool aligned16c(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static bool conv_small(int Cout) { return kget(knobs().conv_small_policy) == 1 ? Cout <= 64 : (Cout % 128 >= 1 && Cout % 128 <= 64); }
 
+// ---- routing: which kernel runs an implicit-GEMM convolution (M = Cout; forward: N = positions, K = Cin * window; weight gradient: N = Cin * window, K = positions) ----
+enum ConvEngine { CONV_F32, CONV_X6 };   // conv3d_fwd_kernel / conv3d_wgrad_kernel (v_mfma_f32_32x32x2_f32) | conv3d_*_x6_kernel (gemm_x6.h: same tiles, same grid, same split-K slabs)
+struct ConvRoute {
+    int engine, rows;    // ConvEngine; output channels per tile: 64 (CfgCout64) or 128 (Cfg128)
+    bool wgrad, vec, packed;             // vec: 16-byte loads of the dense operand (filters / dY); packed: the order of segx_conv3d_pack_weights / ..._bwd_weight_packed
+    int fastw;           // FASTW of conv3d_wgrad_x6_kernel: 0 = per-position decode, 1 = rows of eight / two quads, 2 = contiguous octet (0 off that kernel)
+    int splitk, k_chunk, tiles_m, tiles_n;
+    dim3 grid;
+};
+constexpr int CONV_SPLITK_OPEN = 0;      // conv_route's split factor while segx_conv3d_splitk is still choosing it
+
+// stride-1 'same' geometry with rows of >= 7 floats that are not a multiple of 4 (the 14- / 7-wide Inception stages of cfg4): the contiguous-octet form (r05)
+static bool conv_same1(const ConvGeom& q) {
+    return q.sd == 1 && q.sh == 1 && q.sw == 1 && q.ID == q.OD && q.IH == q.OH && q.IW == q.OW && q.OW >= 7 && q.OW % 4 != 0 &&
+           2 * q.pd == q.KD - 1 && 2 * q.ph == q.KH - 1 && 2 * q.pw == q.KW - 1;
+}
+// geometry of the weight-gradient loader: the eight positions of a thread are eight floats of one input row (OW % 8 == 0), two quads (OW % 4 == 0 at unit stride along W:
+// the second may lie on the next output row) -- both FASTW 1 -- or one contiguous octet (conv_same1: FASTW 2, its own instantiation -- in one kernel with the row forms it
+// spilled 12 bytes); 0 = neither
+static int conv_row_form(const ConvGeom& q) { return conv_same1(q) ? 2 : (q.OW % 8 == 0 || (q.OW % 4 == 0 && q.sw == 1)) ? 1 : 0; }
+
+// Pure: reads the geometry and the knobs -- every knob a convolution launch depends on is read here -- and launches nothing.  aligned: the dense operand (filters / dY)
+// starts on 16 bytes.  The callers have validated the geometry (positions and contraction below 2^31).
+static ConvRoute conv_route(const ConvGeom& q, int B, int Cout, bool wgrad, int splitk, bool aligned, bool packed) {
+    const int P = (int)((int64_t)q.OD * q.OH * q.OW), CK = (int)((int64_t)q.Cin * q.KD * q.KH * q.KW);
+    const int N = wgrad ? CK : P, K = wgrad ? P : CK;
+    const bool pricing = splitk == CONV_SPLITK_OPEN, small = conv_small(Cout);
+    ConvRoute r;
+    r.wgrad = wgrad; r.packed = packed; r.fastw = 0;
+    r.rows = small ? CfgCout64::BM : Cfg128::BM;
+    r.splitk = pricing ? 1 : splitk;
+    r.k_chunk = r.splitk == 1 ? K : ceil_div(ceil_div(K, r.splitk), BKT) * BKT;
+    r.vec = aligned && K % 4 == 0;
+    bool x6 = packed && r.vec && kget(knobs().engine) == SEGX_ENGINE_BF16X6;
+    if (wgrad && x6) {
+        // bf16x6 engine: where the eight positions of a thread are eight floats of one input row (OW % 8 == 0: the 56 x 56 stages, 2/3 of the
+        // weight-gradient FLOPs of I3D); elsewhere its per-position gather decode costs more VALU time than the six-fold faster matrix instruction
+        // saves (r02_a: 63 against 96 TFLOP/s), and the fp32 engine's position-per-thread loader stays.  With unit stride along W the row's eight floats
+        // are two 16-byte loads (r02_l: 128-row tile 117 -> 153 TFLOP/s, 64-row tile 65 -> 119 against 92 on the fp32 engine); the strided case
+        // (the stride-2 composed stem, 64 filters) keeps eight gathers per row and, on the 64-row tile, stays on the fp32 engine (66 against 83).
+        // PRICING AGAINST LAUNCH -- the one place where they differ: the row forms read whole octets of every k slab, so a launch takes them for k_chunk % 8 == 0 only.
+        // k_chunk follows from the split factor, which pricing is there to choose: segx_conv3d_splitk prices the engine the geometry alone names.  The two disagree
+        // where the factor comes out as 1 and the positions are 4 modulo 8 (split slabs are multiples of BKT): DESIGN.md 5h-1 lists the product's cases.
+        const bool octets = pricing || r.k_chunk % 8 == 0;
+        const int all = kget(knobs().conv_x6_wgrad_all);  // 1: the bf16x6 engine for every weight gradient; 2: the row forms on the 64-row tile at any stride
+        r.fastw = octets ? conv_row_form(q) : 0;
+        x6 = (r.fastw && (!small || q.sw == 1 || all == 2)) || all == 1;
+        if (!x6) r.fastw = 0;
+    }
+    r.engine = x6 ? CONV_X6 : CONV_F32;
+    r.tiles_m = ceil_div(Cout, r.rows); r.tiles_n = ceil_div(N, BN);
+    r.grid = dim3(r.tiles_m * r.tiles_n, B, r.splitk);
+    return r;
+}
+
+// launch: the route's run-time choices -> template arguments
+using ConvKernel = void (*)(GemmArgs, ConvGeom);
+template <class Cfg, int WPE> static ConvKernel conv_tile_kernel(const ConvRoute& r) {
+    if (r.engine == CONV_X6) {
+        if (!r.wgrad) return conv3d_fwd_x6_kernel<Cfg, WPE>;
+        return r.fastw == 2 ? conv3d_wgrad_x6_kernel<Cfg, WPE, 2> : r.fastw == 1 ? conv3d_wgrad_x6_kernel<Cfg, WPE, 1> : conv3d_wgrad_x6_kernel<Cfg, WPE, 0>;
+    }
+    return by_flag(r.vec, [&](auto v) { return by_flag(r.packed, [&](auto p) -> ConvKernel {
+        constexpr bool V = decltype(v)::value, PK = decltype(p)::value;
+        return r.wgrad ? conv3d_wgrad_kernel<V, Cfg, PK> : conv3d_fwd_kernel<V, Cfg, PK>;
+    }); });
+}
+static ConvKernel conv_kernel(const ConvRoute& r) { return r.rows == CfgCout64::BM ? conv_tile_kernel<CfgCout64, 4>(r) : conv_tile_kernel<Cfg128, 3>(r); }
+
 }  // namespace segx
 
 using namespace segx;
@@ -1246,89 +1315,80 @@ static ConvGeom make_geom(const int* g) {
     q.KD = g[7]; q.KH = g[8]; q.KW = g[9]; q.sd = g[10]; q.sh = g[11]; q.sw = g[12]; q.pd = g[13]; q.ph = g[14]; q.pw = g[15];
     return q;
 }
-static void fill_common(GemmArgs& g, int M, int N, int K, int nbatch, int splitk, float* workspace) {
-    g.bias = nullptr; g.aux = nullptr; g.gmax = nullptr; g.nb1 = 1; g.bias_b1 = 0; g.bias_b0 = 0; g.alpha = 1.0f; g.epilogue = SEGX_EPI_NONE; g.bias_mode = SEGX_BIAS_NONE;
-    g.a_b1 = g.b_b1 = g.c_b1 = 0; g.b_n = g.b_k = 0; g.a_k = 1; g.vecA = g.vecB = 0;
-    g.M = M; g.N = N; g.K = K; g.tiles_m = ceil_div(M, BM); g.tiles_n = ceil_div(N, BN);
-    g.dropout_p = 0.f; g.seed = g.offset = 0; g.rbase = nullptr; g.splitk = splitk; g.slab = 0; g.resid = nullptr;
-    g.k_chunk = splitk == 1 ? K : ceil_div(ceil_div(K, splitk), BKT) * BKT;
-    g.c_split = (int64_t)nbatch * M * N;
-    if (splitk > 1) g.C = workspace;
-}
-
 /* geom = {Cin, ID, IH, IW, OD, OH, OW, KD, KH, KW, sd, sh, sw, pd, ph, pw} (front pads) */
-// split factor of the implicit GEMM (M = Cout, N, K, B samples) on the tile the convolution kernels use for this Cout
-// x6: the launch will run on the bf16x6 engine (3 / 4 resident workgroups per CU and its own k-tile times: a split factor chosen for the
-// fp32 engine's 512 slots left 1008 workgroups on 768 slots -- 1.3 rounds, 64.8 TFLOP/s on the 192 x 1728 x 150528 weight gradient, r02_c)
-static int conv_splitk(int M, int N, int K, int B, bool x6) {
-    const bool small = conv_small(M);
-    double t;
-    if (x6) {
-        const TileInfo6& c6 = small ? kTiles6[1] : kTiles6[0];
-        const TileInfo c{c6.id, c6.bm, c6.bn, c6.wg_per_cu, c6.ktile_us, c6.fixed_us};
-        return best_splitk(c, M, N, K, B, &t);
-    }
-    return best_splitk(tile_info(small ? SEGX_TILE_64x128 : SEGX_TILE_128x128), M, N, K, B, &t);
-}
 /* the library's split-K factor for segx_conv3d_fwd (wgrad = 0) / segx_conv3d_bwd_weight (wgrad = 1); workspace = splitk * output floats */
 extern "C" int64_t segx_conv3d_splitk(int B, int Cout, const int* geom, int wgrad) {
     if (!geom || B <= 0 || Cout <= 0) return 1;
     const ConvGeom q = make_geom(geom);
     const int64_t P = (int64_t)q.OD * q.OH * q.OW, CK = (int64_t)q.Cin * q.KD * q.KH * q.KW;
     if (P <= 0 || P >= 2147483647LL || CK <= 0 || CK >= 2147483647LL) return 1;
-    // which engine the launch will take (same tests as conv3d_fwd_impl / conv3d_wgrad_impl; the pointer alignment is the allocator's 256 B)
-    const bool packed = q.Cin % 8 == 0, x6 = kget(knobs().engine) == SEGX_ENGINE_BF16X6 && packed;
-    const bool same1 = q.sd == 1 && q.sh == 1 && q.sw == 1 && q.ID == q.OD && q.IH == q.OH && q.IW == q.OW && q.OW >= 7 && q.OW % 4 != 0 &&
-                       2 * q.pd == q.KD - 1 && 2 * q.ph == q.KH - 1 && 2 * q.pw == q.KW - 1;
-    if (wgrad) return conv_splitk(Cout, (int)CK, (int)P, B, x6 && P % 4 == 0 && (((q.OW % 8 == 0 || (q.OW % 4 == 0 && q.sw == 1) || same1) && (!conv_small(Cout) || q.sw == 1 || kget(knobs().conv_x6_wgrad_all) == 2)) || kget(knobs().conv_x6_wgrad_all) == 1));
-    return conv_splitk(Cout, (int)P, (int)CK, B, x6 && CK % 4 == 0);
+    // priced for the route the launch will take with the factor still open: the host packs wherever Cin % 8 == 0, the allocator aligns to 256 B
+    const ConvRoute r = conv_route(q, B, Cout, wgrad != 0, CONV_SPLITK_OPEN, true, q.Cin % 8 == 0);
+    // ... on that route's tile and engine: the bf16x6 engine has 3 / 4 resident workgroups per CU and its own k-tile times (a split factor chosen for the fp32 engine's
+    // 512 slots left 1008 workgroups on 768 slots -- 1.3 rounds, 64.8 TFLOP/s on the 192 x 1728 x 150528 weight gradient, r02_c)
+    const bool small = r.rows == CfgCout64::BM;
+    const TileInfo6& c6 = small ? kTiles6[1] : kTiles6[0];
+    const TileInfo c = r.engine == CONV_X6 ? TileInfo{c6.id, c6.bm, c6.bn, c6.wg_per_cu, c6.ktile_us, c6.fixed_us} : tile_info(small ? SEGX_TILE_64x128 : SEGX_TILE_128x128);
+    double t;
+    return wgrad ? best_splitk(c, Cout, (int)CK, (int)P, B, &t) : best_splitk(c, Cout, (int)P, (int)CK, B, &t);
 }
-/* geom = {Cin, ID, IH, IW, OD, OH, OW, KD, KH, KW, sd, sh, sw, pd, ph, pw} (front pads); splitk > 1: K = Cin*KV split over slabs in
- * workspace (splitk*B*Cout*P floats), reduced deterministically -- for the low-resolution Inception stages whose position grid alone
- * cannot fill the GPU (192 x 588 x 10368: 40 workgroups un-split) */
-// x_bs / y_bs: batch strides (floats) of X / Y when they are channel slices of wider NC... tensors; 0 = dense
-static int conv3d_fwd_impl(const float* X, const float* W, float* Y, int B, int Cout, const int* geom, int splitk, float* workspace, bool packed,
-                           hipStream_t stream, int64_t x_bs = 0, int64_t y_bs = 0) {
-    SEGX_REQUIRE(X && W && Y && geom && B > 0 && Cout > 0 && B <= 65535, "segx_conv3d_fwd: bad args");
+// the route a launch with this split factor would take under the knobs as they are now (include/segx.h); launches nothing
+extern "C" int segx_conv3d_route(int B, int Cout, const int* geom, int wgrad, int splitk, int aligned, int packed, int32_t* out) {
+    SEGX_REQUIRE(geom && out && B > 0 && Cout > 0 && B <= 65535, "segx_conv3d_route: bad args");
     const ConvGeom q = make_geom(geom);
-    const int64_t P = (int64_t)q.OD * q.OH * q.OW; const int K = q.Cin * q.KD * q.KH * q.KW;
-    SEGX_REQUIRE(P > 0 && P < 2147483647LL && K > 0, "segx_conv3d_fwd: bad geometry");
-    SEGX_REQUIRE((int64_t)q.Cin * q.ID * q.IH * q.IW < 2147483647LL && q.KD <= 32 && q.KH <= 32 && q.KW <= 32, "segx_conv3d_fwd: sample or window too large");
-    SEGX_REQUIRE(!packed || q.Cin % 8 == 0, "segx_conv3d_fwd_packed: Cin = %d is not a multiple of 8", q.Cin);
+    const int64_t P = (int64_t)q.OD * q.OH * q.OW, CK = (int64_t)q.Cin * q.KD * q.KH * q.KW;
+    SEGX_REQUIRE(P > 0 && P < 2147483647LL && CK > 0 && CK < 2147483647LL, "segx_conv3d_route: bad geometry");
+    SEGX_REQUIRE(!packed || q.Cin % 8 == 0, "segx_conv3d_route: packed needs Cin = %d in multiples of 8", q.Cin);
+    const ConvRoute r = conv_route(q, B, Cout, wgrad != 0, splitk < 1 ? 1 : splitk, aligned != 0, packed != 0);
+    out[0] = r.engine; out[1] = r.rows; out[2] = r.vec; out[3] = r.packed; out[4] = r.fastw; out[5] = r.splitk;
+    out[6] = (int32_t)r.grid.x; out[7] = (int32_t)r.grid.y; out[8] = (int32_t)r.grid.z;
+    return 0;
+}
+/* One host path for both passes -- validate, route, fill the arguments, launch, sum the k slabs -- as the GEMM  out = dense x im2col(X):
+ *   forward:          dense = the filters [Cout][Cin*KV], out = Y [B][Cout][P];
+ *   weight gradient:  dense = dY [B][Cout][P], out = dWb [B][Cout][Cin*KV], per-sample rows (sum over b with segx_colsum).
+ * splitk > 1: the contraction is split over slabs in workspace (splitk floats per output float) and summed deterministically -- for the low-resolution Inception
+ * stages whose position grid alone cannot fill the GPU (192 x 588 x 10368: 40 workgroups un-split).
+ * dense_bs / x_bs / out_bs: batch strides (floats) of dY / X / Y when they are channel slices of wider NC... tensors; 0 = dense */
+static int conv3d_impl(bool wgrad, const float* dense, const float* X, float* out, int B, int Cout, const int* geom, int splitk, float* workspace, bool packed,
+                       hipStream_t stream, int64_t dense_bs = 0, int64_t x_bs = 0, int64_t out_bs = 0) {
+    const char* who = wgrad ? "segx_conv3d_bwd_weight" : "segx_conv3d_fwd";
+    SEGX_REQUIRE(dense && X && out && geom && B > 0 && Cout > 0 && B <= 65535, "%s: bad args", who);
+    const ConvGeom q = make_geom(geom);
+    const int64_t P = (int64_t)q.OD * q.OH * q.OW, sample = (int64_t)q.Cin * q.ID * q.IH * q.IW; const int CK = q.Cin * q.KD * q.KH * q.KW;
+    SEGX_REQUIRE(P > 0 && P < 2147483647LL && CK > 0, "%s: bad geometry", who);
+    const int kmax = wgrad ? 1023 : 32;
+    SEGX_REQUIRE(sample < 2147483647LL && q.KD <= kmax && q.KH <= kmax && q.KW <= kmax, "%s: sample or window too large", who);
+    SEGX_REQUIRE(!packed || q.Cin % 8 == 0, "%s_packed: Cin = %d is not a multiple of 8", who, q.Cin);
     if (splitk < 1) splitk = 1;
-    SEGX_REQUIRE(splitk == 1 || workspace, "segx_conv3d_fwd: split-K needs a workspace");
-    GemmArgs g; g.A = W; g.B = X; g.C = Y;
-    g.a_b0 = 0; g.a_m = K; g.b_b0 = x_bs ? x_bs : (int64_t)q.Cin * q.ID * q.IH * q.IW; g.c_b0 = y_bs ? y_bs : (int64_t)Cout * P; g.c_m = P;
-    fill_common(g, Cout, (int)P, K, B, splitk, workspace);
-    const bool vec = aligned16c(W) && K % 4 == 0, small = conv_small(Cout);
-    if (small) g.tiles_m = ceil_div(Cout, CfgCout64::BM);
-    dim3 grid(g.tiles_m * g.tiles_n, B, splitk);
-#define SEGX_CONV_FWD(V, CFG) do { if (packed) hipLaunchKernelGGL((conv3d_fwd_kernel<V, CFG, true>), grid, dim3(256), 0, stream, g, q); \
-                                   else hipLaunchKernelGGL((conv3d_fwd_kernel<V, CFG, false>), grid, dim3(256), 0, stream, g, q); } while (0)
-    if (packed && vec && kget(knobs().engine) == SEGX_ENGINE_BF16X6) {          // bf16x6 engine (gemm_x6.h): same tiles, same grid, same split-K slabs
-        knobs().x6_launches.fetch_add(1, std::memory_order_relaxed);
-        if (small) hipLaunchKernelGGL((conv3d_fwd_x6_kernel<CfgCout64, 4>), grid, dim3(256), 0, stream, g, q);
-        else hipLaunchKernelGGL((conv3d_fwd_x6_kernel<Cfg128, 3>), grid, dim3(256), 0, stream, g, q);
-    } else if (small && vec) SEGX_CONV_FWD(true, CfgCout64);
-    else if (small) SEGX_CONV_FWD(false, CfgCout64);
-    else if (vec) SEGX_CONV_FWD(true, Cfg128);
-    else SEGX_CONV_FWD(false, Cfg128);
-#undef SEGX_CONV_FWD
-    int rc = check_launch("segx_conv3d_fwd");
+    SEGX_REQUIRE(splitk == 1 || workspace, "%s: split-K needs a workspace", who);
+    const ConvRoute r = conv_route(q, B, Cout, wgrad, splitk, aligned16c(dense), packed);
+    const int N = wgrad ? CK : (int)P, K = wgrad ? (int)P : CK;
+    GemmArgs g; g.A = dense; g.B = X; g.C = splitk > 1 ? workspace : out;
+    g.a_b0 = !wgrad ? 0 : dense_bs ? dense_bs : (int64_t)Cout * P; g.a_m = K; g.b_b0 = x_bs ? x_bs : sample; g.c_b0 = out_bs ? out_bs : (int64_t)Cout * N; g.c_m = N;
+    g.bias = nullptr; g.aux = nullptr; g.gmax = nullptr; g.nb1 = 1; g.bias_b1 = 0; g.bias_b0 = 0; g.alpha = 1.0f; g.epilogue = SEGX_EPI_NONE; g.bias_mode = SEGX_BIAS_NONE;
+    g.a_b1 = g.b_b1 = g.c_b1 = 0; g.b_n = g.b_k = 0; g.a_k = 1; g.vecA = g.vecB = 0;
+    g.M = Cout; g.N = N; g.K = K; g.tiles_m = r.tiles_m; g.tiles_n = r.tiles_n;
+    g.dropout_p = 0.f; g.seed = g.offset = 0; g.rbase = nullptr; g.splitk = splitk; g.slab = 0; g.resid = nullptr;
+    g.k_chunk = r.k_chunk; g.c_split = (int64_t)B * Cout * N;
+    if (r.engine == CONV_X6) knobs().x6_launches.fetch_add(1, std::memory_order_relaxed);
+    hipLaunchKernelGGL(conv_kernel(r), r.grid, dim3(256), 0, stream, g, q);
+    int rc = check_launch(who);
     if (rc || splitk == 1) return rc;
     const int64_t total = g.c_split;
-    SEGX_SPLITK_REDUCE((unsigned)i64min(2048, (total + 255) / 256), stream, (const float*)workspace, Y, (const float*)nullptr, Cout, (int)P, 1, splitk, g.c_split,
-                       (y_bs ? y_bs : (int64_t)Cout * P), (int64_t)0, (int64_t)P, 1.0f, (int)SEGX_BIAS_NONE, (int64_t)0, (int64_t)0, total, (const float*)nullptr);
-    return check_launch("segx_conv3d_fwd/reduce");
+    SEGX_SPLITK_REDUCE((unsigned)i64min(2048, (total + 255) / 256), stream, (const float*)workspace, out, (const float*)nullptr, Cout, N, 1, splitk, g.c_split,
+                       g.c_b0, (int64_t)0, (int64_t)N, 1.0f, (int)SEGX_BIAS_NONE, (int64_t)0, (int64_t)0, total, (const float*)nullptr);
+    return check_launch(wgrad ? "segx_conv3d_bwd_weight/reduce" : "segx_conv3d_fwd/reduce");
 }
+/* geom = {Cin, ID, IH, IW, OD, OH, OW, KD, KH, KW, sd, sh, sw, pd, ph, pw} (front pads) */
 extern "C" int segx_conv3d_fwd(const float* X, const float* W, float* Y, int B, int Cout, const int* geom, int splitk, float* workspace,
                                void* stream_) {
-    return conv3d_fwd_impl(X, W, Y, B, Cout, geom, splitk, workspace, false, (hipStream_t)stream_);
+    return conv3d_impl(false, W, X, Y, B, Cout, geom, splitk, workspace, false, (hipStream_t)stream_);
 }
 /* the same convolution with the filter bank in the packed contraction order of segx_conv3d_pack_weights (Cin % 8 == 0) */
 extern "C" int segx_conv3d_fwd_packed(const float* X, const float* Wp, float* Y, int B, int Cout, const int* geom, int splitk, float* workspace,
                                       void* stream_) {
-    return conv3d_fwd_impl(X, Wp, Y, B, Cout, geom, splitk, workspace, true, (hipStream_t)stream_);
+    return conv3d_impl(false, Wp, X, Y, B, Cout, geom, splitk, workspace, true, (hipStream_t)stream_);
 }
 /* Wp[o][c/8][t][c%8]: mode 0 = forward filters (o = Cout index, c = Cin index, value W[o][c][t]); mode 1 = backward-data filters
  * (o = Cin index, c = Cout index, value W[c][o][KV-1-t]); W is always the layer's [Cout][Cin][KV] tensor, C = contracted channels */
@@ -1345,75 +1405,26 @@ extern "C" int segx_conv3d_flip_weights(const float* W, float* Wt, int Cout, int
     return check_launch("segx_conv3d_flip_weights");
 }
 /* dWb[b][Cout][Cin*KV] per-sample weight gradients (sum over b with segx_colsum); workspace: splitk*B*Cout*Cin*KV floats when splitk > 1 */
-static int conv3d_wgrad_impl(const float* dY, const float* X, float* dWb, int B, int Cout, const int* geom, int splitk, float* workspace,
-                             bool packed, hipStream_t stream, int64_t dy_bs = 0, int64_t x_bs = 0) {
-    SEGX_REQUIRE(dY && X && dWb && geom && B > 0 && Cout > 0 && B <= 65535, "segx_conv3d_bwd_weight: bad args");
-    const ConvGeom q = make_geom(geom);
-    const int64_t P = (int64_t)q.OD * q.OH * q.OW; const int N = q.Cin * q.KD * q.KH * q.KW;
-    SEGX_REQUIRE(P > 0 && P < 2147483647LL && N > 0, "segx_conv3d_bwd_weight: bad geometry");
-    SEGX_REQUIRE((int64_t)q.Cin * q.ID * q.IH * q.IW < 2147483647LL && q.KD < 1024 && q.KH < 1024 && q.KW < 1024, "segx_conv3d_bwd_weight: sample too large");
-    SEGX_REQUIRE(!packed || q.Cin % 8 == 0, "segx_conv3d_bwd_weight_packed: Cin = %d is not a multiple of 8", q.Cin);
-    if (splitk < 1) splitk = 1;
-    SEGX_REQUIRE(splitk == 1 || workspace, "segx_conv3d_bwd_weight: split-K needs a workspace");
-    GemmArgs g; g.A = dY; g.B = X; g.C = dWb;
-    g.a_b0 = dy_bs ? dy_bs : (int64_t)Cout * P; g.a_m = P; g.b_b0 = x_bs ? x_bs : (int64_t)q.Cin * q.ID * q.IH * q.IW; g.c_b0 = (int64_t)Cout * N; g.c_m = N;
-    fill_common(g, Cout, N, (int)P, B, splitk, workspace);
-    const bool vec = aligned16c(dY) && P % 4 == 0, small = conv_small(Cout);
-    if (small) g.tiles_m = ceil_div(Cout, CfgCout64::BM);
-    dim3 grid(g.tiles_m * g.tiles_n, B, splitk);
-#define SEGX_CONV_WG(V, CFG) do { if (packed) hipLaunchKernelGGL((conv3d_wgrad_kernel<V, CFG, true>), grid, dim3(256), 0, stream, g, q); \
-                                  else hipLaunchKernelGGL((conv3d_wgrad_kernel<V, CFG, false>), grid, dim3(256), 0, stream, g, q); } while (0)
-    // bf16x6 engine: where the eight positions of a thread are eight floats of one input row (OW % 8 == 0: the 56 x 56 stages, 2/3 of the
-    // weight-gradient FLOPs of I3D); elsewhere its per-position gather decode costs more VALU time than the six-fold faster matrix instruction
-    // saves (r02_a: 63 against 96 TFLOP/s), and the fp32 engine's position-per-thread loader stays.  With unit stride along W the row's eight floats
-    // are two 16-byte loads (r02_l: 128-row tile 117 -> 153 TFLOP/s, 64-row tile 65 -> 119 against 92 on the fp32 engine); the strided case
-    // (the stride-2 composed stem, 64 filters) keeps eight gathers per row and, on the 64-row tile, stays on the fp32 engine (66 against 83).
-    // r05: stride-1 'same' geometry with rows of >= 7 floats that are not a multiple of 4 (the 14- / 7-wide Inception stages of cfg4): the contiguous-octet form
-    const bool same1 = q.sd == 1 && q.sh == 1 && q.sw == 1 && q.ID == q.OD && q.IH == q.OH && q.IW == q.OW && q.OW >= 7 && q.OW % 4 != 0 &&
-                       2 * q.pd == q.KD - 1 && 2 * q.ph == q.KH - 1 && 2 * q.pw == q.KW - 1;
-    const bool fastw = (q.OW % 8 == 0 || (q.OW % 4 == 0 && q.sw == 1) || same1) && g.k_chunk % 8 == 0;          // geometry: the row-of-eight (two-quads, contiguous-octet) loader applies
-    if (packed && vec && kget(knobs().engine) == SEGX_ENGINE_BF16X6 && ((fastw && (!small || q.sw == 1 || kget(knobs().conv_x6_wgrad_all) == 2)) || kget(knobs().conv_x6_wgrad_all) == 1)) {
-        knobs().x6_launches.fetch_add(1, std::memory_order_relaxed);
-        if (fastw && same1) {                                   // the contiguous-octet loader has its own instantiation (in one kernel with the row forms it spilled 12 bytes)
-            if (small) hipLaunchKernelGGL((conv3d_wgrad_x6_kernel<CfgCout64, 4, 2>), grid, dim3(256), 0, stream, g, q);
-            else hipLaunchKernelGGL((conv3d_wgrad_x6_kernel<Cfg128, 3, 2>), grid, dim3(256), 0, stream, g, q);
-        } else if (fastw) {
-            if (small) hipLaunchKernelGGL((conv3d_wgrad_x6_kernel<CfgCout64, 4, 1>), grid, dim3(256), 0, stream, g, q);
-            else hipLaunchKernelGGL((conv3d_wgrad_x6_kernel<Cfg128, 3, 1>), grid, dim3(256), 0, stream, g, q);
-        } else if (small) hipLaunchKernelGGL((conv3d_wgrad_x6_kernel<CfgCout64, 4, 0>), grid, dim3(256), 0, stream, g, q);
-        else hipLaunchKernelGGL((conv3d_wgrad_x6_kernel<Cfg128, 3, 0>), grid, dim3(256), 0, stream, g, q);
-    } else if (small && vec) SEGX_CONV_WG(true, CfgCout64);
-    else if (small) SEGX_CONV_WG(false, CfgCout64);
-    else if (vec) SEGX_CONV_WG(true, Cfg128);
-    else SEGX_CONV_WG(false, Cfg128);
-#undef SEGX_CONV_WG
-    int rc = check_launch("segx_conv3d_bwd_weight");
-    if (rc || splitk == 1) return rc;
-    const int64_t total = g.c_split;
-    SEGX_SPLITK_REDUCE((unsigned)i64min(2048, (total + 255) / 256), stream, (const float*)workspace, dWb, (const float*)nullptr, Cout, N, 1, splitk, g.c_split,
-                       (int64_t)Cout * N, (int64_t)0, (int64_t)N, 1.0f, (int)SEGX_BIAS_NONE, (int64_t)0, (int64_t)0, total, (const float*)nullptr);
-    return check_launch("segx_conv3d_bwd_weight/reduce");
-}
 extern "C" int segx_conv3d_bwd_weight(const float* dY, const float* X, float* dWb, int B, int Cout, const int* geom, int splitk,
                                       float* workspace, void* stream_) {
-    return conv3d_wgrad_impl(dY, X, dWb, B, Cout, geom, splitk, workspace, false, (hipStream_t)stream_);
+    return conv3d_impl(true, dY, X, dWb, B, Cout, geom, splitk, workspace, false, (hipStream_t)stream_);
 }
 /* the same with the gradient rows in the packed order [Cout][Cin/8][KV][8] (Cin % 8 == 0); segx_conv3d_unpack_wgrad restores [Cout][Cin][KV] */
 extern "C" int segx_conv3d_bwd_weight_packed(const float* dY, const float* X, float* dWb, int B, int Cout, const int* geom, int splitk,
                                              float* workspace, void* stream_) {
-    return conv3d_wgrad_impl(dY, X, dWb, B, Cout, geom, splitk, workspace, true, (hipStream_t)stream_);
+    return conv3d_impl(true, dY, X, dWb, B, Cout, geom, splitk, workspace, true, (hipStream_t)stream_);
 }
 /* Channel-slice forms (Inception branches reading / writing slices of a wider NCDHW tensor without a copy): X is the first channel of the slice
  * inside a tensor whose samples lie x_bstride floats apart, likewise Y / dY; every pointer 16-byte aligned; 0 = dense */
 extern "C" int segx_conv3d_fwd_packed_bs(const float* X, const float* Wp, float* Y, int B, int Cout, const int* geom, int splitk, float* workspace,
                                          int64_t x_bstride, int64_t y_bstride, void* stream_) {
     SEGX_REQUIRE(x_bstride >= 0 && y_bstride >= 0 && aligned16c(X) && aligned16c(Y), "segx_conv3d_fwd_packed_bs: bad strides / alignment");
-    return conv3d_fwd_impl(X, Wp, Y, B, Cout, geom, splitk, workspace, true, (hipStream_t)stream_, x_bstride, y_bstride);
+    return conv3d_impl(false, Wp, X, Y, B, Cout, geom, splitk, workspace, true, (hipStream_t)stream_, 0, x_bstride, y_bstride);
 }
 extern "C" int segx_conv3d_bwd_weight_packed_bs(const float* dY, const float* X, float* dWb, int B, int Cout, const int* geom, int splitk,
                                                 float* workspace, int64_t dy_bstride, int64_t x_bstride, void* stream_) {
     SEGX_REQUIRE(dy_bstride >= 0 && x_bstride >= 0 && aligned16c(X) && aligned16c(dY), "segx_conv3d_bwd_weight_packed_bs: bad strides / alignment");
-    return conv3d_wgrad_impl(dY, X, dWb, B, Cout, geom, splitk, workspace, true, (hipStream_t)stream_, dy_bstride, x_bstride);
+    return conv3d_impl(true, dY, X, dWb, B, Cout, geom, splitk, workspace, true, (hipStream_t)stream_, dy_bstride, x_bstride);
 }
 extern "C" int segx_conv3d_unpack_wgrad(const float* dWp, float* dW, int Cout, int Cin, int KV, void* stream_) {
     SEGX_STREAM; SEGX_REQUIRE(dWp && dW && Cout > 0 && Cin > 0 && Cin % 8 == 0 && KV > 0, "segx_conv3d_unpack_wgrad: bad args");

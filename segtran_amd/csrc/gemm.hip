@@ -361,8 +361,6 @@ static int gemm_route(const float* A, const float* B, const segx_gemm_desc* d, G
 using GemmKernel = void (*)(GemmArgs);
 struct GemmLaunch { GemmKernel fn; int bm, bn; };            // bm x bn: the tile the kernel was instantiated for
 template <class Cfg> static GemmLaunch built_for(GemmKernel fn) { return GemmLaunch{fn, Cfg::BM, Cfg::BN}; }
-// a run-time flag as a template argument: f(std::true_type) or f(std::false_type)
-template <class F> static GemmKernel by_flag(bool flag, F f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }
 // THE place where the layout flags become template arguments: f(A k-contiguous, B k-contiguous)
 template <class F> static GemmKernel by_layout(const GemmRoute& r, F f) {
     return by_flag(r.akc, [&](auto ak) { return by_flag(r.bkc, [&](auto bk) { return f(ak, bk); }); });

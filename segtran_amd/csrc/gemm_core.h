@@ -436,4 +436,7 @@ static bool splitk_vec_ok(const void* ws, const void* C, const void* bias, const
                                 bias_mode, bias_b1, bias_b0, total, resid);                                                                                         \
     } while (0)
 
+// a run-time flag as a template argument: f(std::true_type) or f(std::false_type) (the kernel routers of gemm.hip and conv3d.hip)
+template <class F> static auto by_flag(bool flag, F f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }
+
 }  // namespace segx

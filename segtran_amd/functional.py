@@ -1601,6 +1601,70 @@ def _same_pads(size, k, s):
     return out
 
 
+def _conv3d_fwd_shaped(L, x, w, y, B, Cout, geom, mode, x_bs=0, y_bs=0, halo=True):
+    """y = the convolution of geometry `geom` over x with the layer's filters w as they are (mode 0: the forward pass) or transposed and flipped (mode 1: the stride-1
+    data gradient, Cout = the layer's Cin).  The LDS-resident-halo kernel where it serves (3 x 3 x 3 stride-1 'same', conv3d_halo.hip; filters pre-split once per call),
+    else the implicit GEMM: split-K workspace, filters packed where the contracted channels come in eights (one tap decode per eight gathers, conv3d.hip).
+    x_bs / y_bs: sample strides of channel slices (0 = dense)."""
+    C, KV = geom[0], geom[7] * geom[8] * geom[9]
+    if halo and L.conv3d_halo_ok(B, Cout, geom):
+        L.conv3d_halo_fwd(x, L.conv3d_halo_pack(w, Cout, C, mode), y, B, Cout, geom, x_bs=x_bs, y_bs=y_bs)
+        return
+    sk = L.conv3d_splitk(B, Cout, geom, False)
+    ws = _empty(x, sk * B * Cout * geom[4] * geom[5] * geom[6]) if sk > 1 else None
+    packed = C % 8 == 0
+    if packed or mode:
+        wp = torch.empty_like(w)
+        if packed:
+            L.conv3d_pack_weights(w, wp, Cout, C, KV, mode)
+        else:
+            L.conv3d_flip_weights(w, wp, C, Cout, KV)
+        w = wp
+    L.conv3d_fwd(x, w, y, B, Cout, geom, sk, ws, packed=packed, x_bs=x_bs, y_bs=y_bs)
+
+
+def _conv3d_dgrad_strided(L, dy, w, dx, B, geom):
+    """dx of a strided convolution of geometry `geom`."""
+    Cin, ID, IH, IW, OD, OH, OW, KD, KH, KW, sd, sh, sw, pd, ph, pw = geom
+    Cout = w.shape[0]
+    if Cin <= 4:
+        # strided transposed convolution onto <= 4 channels (the 7x7x7 stride-2 I3D stem): direct gather kernel
+        L.conv3d_bwd_data_direct(dy, w, dx, B, Cout, geom)
+        return
+    # general strided case (the 4x4 stride-2 convolutions of the domain discriminator): dY with stride-1 zeros inserted, then the stride-1 transposed
+    # convolution on the tile engine (positions beyond the dilated extent read the zero padding); always the implicit GEMM
+    DD, DH, DW = (OD - 1) * sd + 1, (OH - 1) * sh + 1, (OW - 1) * sw + 1
+    dyd = dy.new_zeros(B, Cout, DD, DH, DW)
+    dyd[:, :, ::sd, ::sh, ::sw] = dy
+    g2 = (Cout, DD, DH, DW, ID, IH, IW, KD, KH, KW, 1, 1, 1, KD - 1 - pd, KH - 1 - ph, KW - 1 - pw)
+    _conv3d_fwd_shaped(L, dyd, w, dx, B, Cin, g2, 1, halo=False)
+
+
+def _conv3d_wgrad(L, dy, x, w, B, geom, x_bs=0):
+    """dw of the convolution of geometry `geom` (x: possibly a channel slice with sample stride x_bs): the halo kernel where it serves, else per-sample rows on the
+    implicit GEMM (packed row order where Cin comes in eights), their sum over the batch, and the layer's [Cout][Cin][KV] order restored."""
+    Cout, Cin = w.shape[:2]
+    KV = geom[7] * geom[8] * geom[9]
+    N = Cin * KV
+    if L.conv3d_halo_wgrad_ok(B, Cout, geom):
+        dw = torch.empty_like(w)
+        L.conv3d_halo_wgrad(dy, x, dw, B, Cout, geom, x_bs=x_bs)
+        return dw
+    sk = L.conv3d_splitk(B, Cout, geom, True)
+    ws = _empty(dy, sk * B * Cout * N) if sk > 1 else None
+    dwb = _empty(dy, B, Cout * N)
+    packed = Cin % 8 == 0
+    L.conv3d_bwd_weight(dy, x, dwb, B, Cout, geom, sk, ws, packed=packed, x_bs=x_bs)
+    dw = dwb
+    if B > 1:
+        dw = _empty(dy, Cout * N)
+        L.colsum(dwb, dw, _empty(dy, L.colreduce_ws(B, Cout * N, 1)), B, Cout * N)
+    if packed:
+        dwp, dw = dw, _empty(dy, Cout * N)
+        L.conv3d_unpack_wgrad(dwp, dw, Cout, Cin, KV)
+    return dw.view_as(w)
+
+
 class _Conv3d(_Fn):
     @staticmethod
     def forward(ctx, x, w, stride, pads):
@@ -1613,21 +1677,8 @@ class _Conv3d(_Fn):
         OH = (IH + ph + phb - KH) // stride[1] + 1
         OW = (IW + pw + pwb - KW) // stride[2] + 1
         y = _empty(x, B, Cout, OD, OH, OW)
-        geom = (Cin, ID, IH, IW, OD, OH, OW, KD, KH, KW) + tuple(stride) + (pd, ph, pw)
-        if L.conv3d_halo_ok(B, Cout, geom):  # r06: 3 x 3 x 3 stride-1 'same' on the LDS-resident-halo kernel (conv3d_halo.hip); filters pre-split once per call
-            L.conv3d_halo_fwd(x, L.conv3d_halo_pack(w, Cout, Cin, 0), y, B, Cout, geom)
-            ctx.geom, ctx.stride, ctx.pads = geom, tuple(stride), pads
-            ctx.save_for_backward(x, w)
-            return y
-        sk = L.conv3d_splitk(B, Cout, geom, False)
-        ws = _empty(x, sk * y.numel()) if sk > 1 else None
-        if Cin % 8 == 0:                    # packed contraction order: one tap decode per eight gathers (see conv3d.hip)
-            wp = torch.empty_like(w)
-            L.conv3d_pack_weights(w, wp, Cout, Cin, KD * KH * KW, 0)
-            L.conv3d_fwd(x, wp, y, B, Cout, geom, sk, ws, packed=True)
-        else:
-            L.conv3d_fwd(x, w, y, B, Cout, geom, sk, ws)
-        ctx.geom, ctx.stride, ctx.pads = geom, tuple(stride), pads
+        ctx.geom = (Cin, ID, IH, IW, OD, OH, OW, KD, KH, KW) + tuple(stride) + (pd, ph, pw)
+        _conv3d_fwd_shaped(L, x, w, y, B, Cout, ctx.geom, 0)
         ctx.save_for_backward(x, w)
         return y
 
@@ -1636,71 +1687,18 @@ class _Conv3d(_Fn):
         L = segx.lib()
         x, w = ctx.saved_tensors
         dy = _c(dy)
-        B, Cin, ID, IH, IW = x.shape
-        Cout, _, KD, KH, KW = w.shape
-        KV = KD * KH * KW
-        geom = ctx.geom
-        OD, OH, OW = geom[4:7]
+        Cin, ID, IH, IW, OD, OH, OW, KD, KH, KW, sd, sh, sw, pd, ph, pw = geom = ctx.geom
+        B, Cout = x.shape[0], w.shape[0]
         dx = dw = None
         if ctx.needs_input_grad[0]:
-            if ctx.stride == (1, 1, 1):
-                wt = _empty(x, Cin, Cout, KD, KH, KW)
-                (pd, _), (ph, _), (pw, _) = ctx.pads
+            dx = torch.empty_like(x)
+            if (sd, sh, sw) == (1, 1, 1):
                 g2 = (Cout, OD, OH, OW, ID, IH, IW, KD, KH, KW, 1, 1, 1, KD - 1 - pd, KH - 1 - ph, KW - 1 - pw)
-                dx = torch.empty_like(x)
-                if L.conv3d_halo_ok(B, Cin, g2):
-                    L.conv3d_halo_fwd(dy, L.conv3d_halo_pack(w, Cin, Cout, 1), dx, B, Cin, g2)
-                else:
-                    sk = L.conv3d_splitk(B, Cin, g2, False)
-                    ws = _empty(x, sk * dx.numel()) if sk > 1 else None
-                    if Cout % 8 == 0:
-                        L.conv3d_pack_weights(w, wt, Cin, Cout, KV, 1)
-                        L.conv3d_fwd(dy, wt, dx, B, Cin, g2, sk, ws, packed=True)
-                    else:
-                        L.conv3d_flip_weights(w, wt, Cout, Cin, KV)
-                        L.conv3d_fwd(dy, wt, dx, B, Cin, g2, sk, ws)
-            elif Cin <= 4:
-                # strided transposed convolution onto <= 4 channels (the 7x7x7 stride-2 I3D stem): direct gather kernel
-                dx = torch.empty_like(x)
-                L.conv3d_bwd_data_direct(dy, w, dx, B, Cout, geom)
+                _conv3d_fwd_shaped(L, dy, w, dx, B, Cin, g2, 1)
             else:
-                # general strided case (the 4x4 stride-2 convolutions of the domain discriminator): dY with stride-1 zeros inserted, then the
-                # stride-1 transposed convolution on the tile engine (positions beyond the dilated extent read the zero padding)
-                sd, sh, sw = ctx.stride
-                DD, DH, DW = (OD - 1) * sd + 1, (OH - 1) * sh + 1, (OW - 1) * sw + 1
-                dyd = dy.new_zeros(B, Cout, DD, DH, DW)
-                dyd[:, :, ::sd, ::sh, ::sw] = dy
-                wt = _empty(x, Cin, Cout, KD, KH, KW)
-                (pd, _), (ph, _), (pw, _) = ctx.pads
-                g2 = (Cout, DD, DH, DW, ID, IH, IW, KD, KH, KW, 1, 1, 1, KD - 1 - pd, KH - 1 - ph, KW - 1 - pw)
-                dx = torch.empty_like(x)
-                sk = L.conv3d_splitk(B, Cin, g2, False)
-                ws = _empty(x, sk * dx.numel()) if sk > 1 else None
-                if Cout % 8 == 0:
-                    L.conv3d_pack_weights(w, wt, Cin, Cout, KV, 1)
-                    L.conv3d_fwd(dyd, wt, dx, B, Cin, g2, sk, ws, packed=True)
-                else:
-                    L.conv3d_flip_weights(w, wt, Cout, Cin, KV)
-                    L.conv3d_fwd(dyd, wt, dx, B, Cin, g2, sk, ws)
-        if ctx.needs_input_grad[1] and L.conv3d_halo_wgrad_ok(B, Cout, geom):
-            dw = torch.empty_like(w)
-            L.conv3d_halo_wgrad(dy, x, dw, B, Cout, geom)
-        elif ctx.needs_input_grad[1]:
-            P, N = OD * OH * OW, Cin * KV
-            sk = L.conv3d_splitk(B, Cout, geom, True)
-            ws = _empty(x, sk * B * Cout * N) if sk > 1 else None
-            dwb = _empty(x, B, Cout * N)
-            packed = Cin % 8 == 0               # packed row order: one tap lookup per eight gathers (see conv3d.hip)
-            L.conv3d_bwd_weight(dy, x, dwb, B, Cout, geom, sk, ws, packed=packed)
-            if B > 1:
-                dw = _empty(x, Cout * N)
-                L.colsum(dwb, dw, _empty(x, L.colreduce_ws(B, Cout * N, 1)), B, Cout * N)
-            else:
-                dw = dwb
-            if packed:
-                dwp, dw = dw, _empty(x, Cout * N)
-                L.conv3d_unpack_wgrad(dwp, dw, Cout, Cin, KV)
-            dw = dw.view_as(w)
+                _conv3d_dgrad_strided(L, dy, w, dx, B, geom)
+        if ctx.needs_input_grad[1]:
+            dw = _conv3d_wgrad(L, dy, x, w, B, geom)
         return dx, dw, None, None
 
 
@@ -1716,7 +1714,6 @@ class _Conv3dSlices(_Fn):
         t = _c(t)
         ctx.with_tail = bool(with_tail)
         B, Ct, D, H, W = t.shape
-        vol = D * H * W
         ys, geoms, c0 = [], [], 0
         for w in ws:
             w = _c(w)
@@ -1724,13 +1721,7 @@ class _Conv3dSlices(_Fn):
             assert Cin % 8 == 0 and Cout % 8 == 0 and KD % 2 == KH % 2 == KW % 2 == 1, 'slice convolutions: channel counts in multiples of 8, odd windows'
             geom = (Cin, D, H, W, D, H, W, KD, KH, KW, 1, 1, 1, KD // 2, KH // 2, KW // 2)
             y = _empty(t, B, Cout, D, H, W)
-            if L.conv3d_halo_ok(B, Cout, geom):
-                L.conv3d_halo_fwd(t[:, c0:], L.conv3d_halo_pack(w, Cout, Cin, 0), y, B, Cout, geom, x_bs=Ct * vol)
-            else:
-                sk = L.conv3d_splitk(B, Cout, geom, False)
-                wp = torch.empty_like(w)
-                L.conv3d_pack_weights(w, wp, Cout, Cin, KD * KH * KW, 0)
-                L.conv3d_fwd(t[:, c0:], wp, y, B, Cout, geom, sk, _empty(t, sk * y.numel()) if sk > 1 else None, packed=True, x_bs=Ct * vol)
+            _conv3d_fwd_shaped(L, t[:, c0:], w, y, B, Cout, geom, 0, x_bs=Ct * D * H * W)
             ys.append(y); geoms.append(geom); c0 += Cin
         assert c0 <= Ct, 'the slices exceed the tensor'      # channels beyond the last slice (another consumer's, e.g. Inception branch 0)
         ctx.geoms = geoms
@@ -1747,7 +1738,7 @@ class _Conv3dSlices(_Fn):
         L = segx.lib()
         t, ws = ctx.saved_tensors[0], ctx.saved_tensors[1:]
         B, Ct, D, H, W = t.shape
-        vol = D * H * W
+        t_bs = Ct * D * H * W
         dt = torch.empty_like(t) if ctx.needs_input_grad[0] else None
         covered = sum(int(w.shape[1]) for w in ws)
         d_tail = dys[len(ws)] if ctx.with_tail else None
@@ -1758,36 +1749,11 @@ class _Conv3dSlices(_Fn):
                 dt[:, covered:].zero_()
         dws, c0 = [], 0
         for i, (w, dy, geom) in enumerate(zip(ws, dys, ctx.geoms)):
-            Cout, Cin, KD, KH, KW = w.shape
-            KV = KD * KH * KW
+            Cout, Cin = w.shape[:2]
             dy = _c(dy) if dy is not None else torch.zeros(B, Cout, D, H, W, dtype=torch.float32, device=t.device)
             if dt is not None:
-                g2 = (Cout, D, H, W, D, H, W, KD, KH, KW, 1, 1, 1, KD // 2, KH // 2, KW // 2)
-                if L.conv3d_halo_ok(B, Cin, g2):
-                    L.conv3d_halo_fwd(dy, L.conv3d_halo_pack(w, Cin, Cout, 1), dt[:, c0:], B, Cin, g2, y_bs=Ct * vol)
-                else:
-                    wt = torch.empty_like(w)
-                    sk = L.conv3d_splitk(B, Cin, g2, False)
-                    L.conv3d_pack_weights(w, wt, Cin, Cout, KV, 1)
-                    L.conv3d_fwd(dy, wt, dt[:, c0:], B, Cin, g2, sk, _empty(t, sk * B * Cin * vol) if sk > 1 else None, packed=True, y_bs=Ct * vol)
-            dw = None
-            if ctx.needs_input_grad[2 + i] and L.conv3d_halo_wgrad_ok(B, Cout, geom):
-                dw = torch.empty_like(w)
-                L.conv3d_halo_wgrad(dy, t[:, c0:], dw, B, Cout, geom, x_bs=Ct * vol)
-            elif ctx.needs_input_grad[2 + i]:
-                N = Cin * KV
-                sk = L.conv3d_splitk(B, Cout, geom, True)
-                dwb = _empty(t, B, Cout * N)
-                L.conv3d_bwd_weight(dy, t[:, c0:], dwb, B, Cout, geom, sk, _empty(t, sk * B * Cout * N) if sk > 1 else None, packed=True, x_bs=Ct * vol)
-                if B > 1:
-                    dwp = _empty(t, Cout * N)
-                    L.colsum(dwb, dwp, _empty(t, L.colreduce_ws(B, Cout * N, 1)), B, Cout * N)
-                else:
-                    dwp = dwb
-                dw = _empty(t, Cout * N)
-                L.conv3d_unpack_wgrad(dwp, dw, Cout, Cin, KV)
-                dw = dw.view_as(w)
-            dws.append(dw)
+                _conv3d_fwd_shaped(L, dy, w, dt[:, c0:], B, Cin, (Cout,) + geom[1:], 1, y_bs=t_bs)
+            dws.append(_conv3d_wgrad(L, dy, t[:, c0:], w, B, geom, x_bs=t_bs) if ctx.needs_input_grad[2 + i] else None)
             c0 += Cin
         return (dt, None) + tuple(dws)
 

@@ -383,6 +383,28 @@ def test_conv3d_same_takes_the_halo_kernel_where_it_applies(backend):
     assert L.c.segx_tune_get(Knob.CONV_HALO) == held == 1            # the default, and what the test leaves behind
 
 
+def test_conv3d_route_table(backend):
+    """conv_route() of conv3d.hip against the recorded table tests/golden/conv3d_routes.json: B, Cout, geom, wgrad and the knobs held -> (splitk, engine, tile rows,
+    FASTW, 16-byte loads), recorded from the library as it was BEFORE conv_route() existed (segx_conv3d_splitk; engine, tile and loader form from its launch
+    conditions).  Rows: every 3-D convolution of Inception-I3D at the cfg4 (96 x 112 x 112) and cfg5 (128^3) sizes, batch 4 -- the stem in its raw, composed and
+    space-to-depth forms; forward, stride-1 data gradient and weight gradient as SF._Conv3d forms them -- on either engine, and the 13 geometries of
+    test_conv3d_on_the_bf16x6_engine with conv_x6_wgrad_all = 0 / 1 / 2.  Host logic only: nothing is launched."""
+    import json, os
+    L = backend.L
+    rows = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'conv3d_routes.json')))
+    assert len(rows) == 345
+    seen = set()
+    for r in rows:
+        with L.tuned(**r['knobs']):
+            sk = L.conv3d_splitk(r['B'], r['Cout'], r['geom'], r['wgrad'])
+            engine, tile_rows, vec, fastw, slabs, grid = L.conv3d_route(r['B'], r['Cout'], r['geom'], r['wgrad'], sk)
+        assert (sk, engine, tile_rows, fastw, vec) == (r['splitk'], r['engine'], r['tile_rows'], r['fastw'], r['vec']), r
+        assert slabs == sk and grid[1:] == (r['B'], sk) and grid[0] % -(-r['Cout'] // tile_rows) == 0, r
+        seen |= {(engine, 'vec' if vec else 'scalar') if engine == 'f32' else (engine, tile_rows), ('fastw', fastw) if engine == 'x6' and r['wgrad'] else None,
+                 'splitk' if sk > 1 else None}
+    assert seen >= {('f32', 'vec'), ('f32', 'scalar'), ('x6', 64), ('x6', 128), ('fastw', 0), ('fastw', 1), ('fastw', 2), 'splitk'}
+
+
 @pytest.mark.parametrize('engine', ['f32', 'x6'])
 @pytest.mark.parametrize('B,H,W,D', [(2, 8, 12, 6), (1, 6, 16, 8)])
 def test_stem_and_bridge_as_one_space_to_depth_convolution(backend, engine, B, H, W, D):
