@@ -418,15 +418,18 @@ enum {
                                          * tiles --, 0 = N fastest always (rounds 1-5) */
 };
 /* One more id of segx_tune / segx_tune_get, kept OUT of the enum above because it is no tuning knob -- its settings do not give identical results, it selects a
- * precision: bf16 products per block of segx_gemm_f32's bf16 tile engine.  6 (default) = fp32-equivalent; 3 = hi.mid + mid.hi + hi.hi on two bf16 planes per operand --
+ * precision: bf16 products per block of the bf16 tile engine in segx_gemm_f32 and the forward 3-D convolutions.  6 (default) = fp32-equivalent; 3 = hi.mid + mid.hi + hi.hi on two bf16 planes per operand --
  * accurate to (2^-15 + 2^-16) |A|.|B| per element, an INFERENCE opt-in -- on the routes that have a three-term kernel; every other route runs six-term
- * (segx_x3_launches tells).  Only 6 and 3 are accepted.  The implicit-GEMM convolutions, the skinny kernel and the fp32 engine do not read it. */
+ * (segx_x3_launches tells).  Only 6 and 3 are accepted.  3-D convolutions: the forward-shaped launches on the bf16 engine follow it -- segx_conv3d_fwd*
+ * with packed filters and segx_conv3d_halo_fwd, hence also the BACKWARD-DATA pass, which is such a launch on the flipped filter bank: at this ABI a data gradient
+ * computed under 3 is three-term.  What keeps the mode out of training is the Python interface (inference_precision refuses to be entered with gradients enabled).
+ * The weight gradients (segx_conv3d_bwd_weight*, segx_conv3d_halo_wgrad), the fp32-MFMA convolution kernels, the skinny kernel and the fp32 engine do not read it. */
 #define SEGX_KNOB_X6_TERMS 20
 int segx_tune(int knob, int value);
 /* r06: the value a knob holds now (-1 for an unknown knob and for the counter SEGX_KNOB_X6_LAUNCHES): a caller that changes a process-wide default for its own
  * lifetime (dist.GradReducer: SEGX_KNOB_BN_PATH) reads it first and puts it back instead of assuming the default */
 int segx_tune_get(int knob);
-/* Launches of segx_gemm_f32 that ran the three-term product (SEGX_KNOB_X6_TERMS = 3) since the last call; resets the count.  SEGX_KNOB_X6_LAUNCHES keeps counting
+/* Launches of segx_gemm_f32, segx_conv3d_fwd* and segx_conv3d_halo_fwd that ran the three-term product (SEGX_KNOB_X6_TERMS = 3) since the last call; resets the count.  SEGX_KNOB_X6_LAUNCHES keeps counting
  * every launch on the bf16 tile engine, so "asked for three terms, ran six" is the difference of the two. */
 int segx_x3_launches(void);
 /* r04: TWO adjacent outer axes of a linear resampling in one streaming pass over [outer, n1, n2, inner] (inner % 4 == 0: the contiguous extent, read
@@ -497,6 +500,10 @@ int64_t segx_conv3d_splitk(int B, int Cout, const int* geom, int wgrad);
  * 1 bf16x6), [1] = output channels per tile (64 / 128), [2] = 16-byte loads of the dense operand, [3] = packed, [4] = the bf16x6 weight gradient's loader form
  * (0 per-position decode, 1 rows of eight floats / two quads, 2 contiguous octet), [5] = k slabs, [6..8] = grid x, y, z */
 int segx_conv3d_route(int B, int Cout, const int* geom, int wgrad, int splitk, int aligned, int packed, int32_t* out);
+/* bf16 products per block (6 or 3, SEGX_KNOB_X6_TERMS) the forward convolution of this geometry would run under the knobs as they are now; nothing is launched.  Where
+ * segx_conv3d_halo_ok accepts the call -- the callers then use segx_conv3d_halo_fwd -- the halo kernel's count, otherwise that of the route segx_conv3d_fwd* would take
+ * (arguments as for segx_conv3d_route).  0 off the bf16 tile engine (and for arguments segx_conv3d_route refuses). */
+int segx_conv3d_fwd_terms(int B, int Cout, const int* geom, int splitk, int aligned, int packed);
 int segx_conv3d_fwd(const float* X, const float* W /* [Cout][Cin][KD][KH][KW] */, float* Y, int B, int Cout, const int* geom, int splitk,
                     float* workspace, void* stream);
 /* Packed contraction order for Cin % 8 == 0: k runs (channel block of 8, tap, channel in block), so eight consecutive k share one tap and

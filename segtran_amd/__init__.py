@@ -10,7 +10,7 @@ def sliding_windows(H, W, orig_input_size, stride):
 
 
 def inference_precision(name):
-    """Context manager: the precision of the bf16 tile engine's GEMMs inside the block (infer2d.inference_precision).  'fp32' (the default behaviour): six bf16
+    """Context manager: the precision of the bf16 tile engine's GEMMs and forward 3-D convolutions inside the block (infer2d.inference_precision).  'fp32' (the default behaviour): six bf16
     products per block, fp32-equivalent; 'bf16x3': three, ~2^-15 relative per product sum -- inference only: entering with gradients enabled raises RuntimeError."""
     from .infer2d import inference_precision as f
     return f(name)

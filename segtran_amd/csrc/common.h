@@ -301,16 +301,18 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
     X(17, conv_halo_min_tiles, 256, 1, 1 << 24)      /* fewest 128-output spatial tiles (x batch) for which the halo kernels are used (below: split-K im2col) */   \
     X(18, skinny_nt, 1, 0, 1)                        /* batch-reduced skinny weight gradients on the streaming kernel (gemm_skinny.hip); 0 = the tile kernels' split-K slabs */ \
     X(19, tile_walk, 1, 0, 1)                        /* 1 = the GEMM kernels walk M fastest where the A operand fits an XCD's L2 and B is the big one (gemm_core.h tile_walk), 0 = N fastest always (rounds 1-5) */ \
-    X(20, x6_terms, 6, 3, 6)                         /* products per block of the bf16 tile engine in segx_gemm_f32: 6 = fp32-equivalent, 3 = hi.mid + mid.hi + hi.hi (~2^-15 relative; inference opt-in) where a three-term kernel is built */
+    X(20, x6_terms, 6, 3, 6)                         /* products per block of the bf16 tile engine in segx_gemm_f32 and the forward 3-D convolutions: 6 = fp32-equivalent, 3 = hi.mid + mid.hi + hi.hi (~2^-15 relative; inference opt-in) where a three-term kernel is built */
 struct Knobs {
 #define SEGX_KNOB_FIELD(id, field, def, lo, hi) std::atomic<int> field{def};
     SEGX_KNOB_TABLE(SEGX_KNOB_FIELD)
 #undef SEGX_KNOB_FIELD
     std::atomic<int> x6_launches{0};                // knob 5: launches that ran on the bf16x6 engine since the last query
-    std::atomic<int> x3_launches{0};                // segx_x3_launches: those of them (segx_gemm_f32 only) that ran the three-term product
+    std::atomic<int> x3_launches{0};                // segx_x3_launches: those of them (segx_gemm_f32, forward 3-D convolutions) that ran the three-term product
 };
 inline Knobs& knobs() { static Knobs k; return k; }
 inline int kget(const std::atomic<int>& a) { return a.load(std::memory_order_relaxed); }
+// bf16 products per block segx_conv3d_halo_fwd runs under knob x6_terms as it is now (conv3d_halo.hip; segx_conv3d_fwd_terms of conv3d.hip reports it)
+int halo_fwd_terms();
 
 // host-side: device pointer every dropout launch hands to its kernel (segx_set_rng_base); one instance for the whole library
 inline const uint64_t*& rng_base() { static const uint64_t* p = nullptr; return p; }

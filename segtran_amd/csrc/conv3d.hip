@@ -206,6 +206,7 @@ struct ConvFwdLoaderB6 {
         for (int i = 0; i < NP; ++i) { r[4 * i] = t4[i].x; r[4 * i + 1] = t4[i].y; r[4 * i + 2] = t4[i].z; r[4 * i + 3] = t4[i].w; }
         return ok;
     }
+    template <int TERMS = 6>                                           // 3: the hi and mid planes only (the three-term product of gemm_mainloop_x6)
     __device__ __forceinline__ void store6(float (&r)[NREG], unsigned okmask, unsigned char* __restrict__ P, int tid) const {
         const int n = tid & 127, c0 = (tid >> 7) * 2;
 #pragma unroll
@@ -214,7 +215,7 @@ struct ConvFwdLoaderB6 {
             const bool ok = ((okmask >> (8 * sub)) & 1u) != 0u;        // the eight k of a (channel block, tap) pair are inside or outside together
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = ok ? r[8 * sub + j] : 0.f;
-            x6_store8<X6Plane<128>::bytes>(P, x6_off(n, c0 + sub), v);
+            x6_store8<X6Plane<128>::bytes, TERMS>(P, x6_off(n, c0 + sub), v);
         }
     }
 };
@@ -412,15 +413,17 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_kernel(GemmArgs g, ConvGe
 }
 
 // the packed convolutions on the bf16x6 engine (float4-legal weights / dY: the host checks)
-template <class Cfg, int WPE>
+// TERMS = 3 (forward / backward-data only, knob x6_terms through conv_route()): the three-term product -- two planes per operand (32 / 24 KB per workgroup), three
+// matrix instructions per block; tile walk, split-K slabs and epilogue are the six-term ones
+template <class Cfg, int WPE, int TERMS = 6>
 __global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(WPE) void conv3d_fwd_x6_kernel(GemmArgs g, ConvGeom q) {
     static_assert(Cfg::BN == 128, "conv loaders fill 128 columns");
-    __shared__ __attribute__((aligned(16))) unsigned char lds[X6Lds<Cfg>::BYTES];
+    __shared__ __attribute__((aligned(16))) unsigned char lds[X6Lds<Cfg, TERMS>::BYTES];
     const TileCoord t = tile_coord<Cfg>(g);
     const DenseLoader6<true, Cfg::BM> la{g.A, g.a_m, 1, t.m0, g.M};                  // packed weights [Cout][Cin*KV]
     const ConvFwdLoaderB6 lb(g.B + (int64_t)t.zb * g.b_b0, q, t.n0, g.N);            // X[b]
     f32x16 acc[Cfg::MI][Cfg::NJ];
-    gemm_mainloop_x6<Cfg>(acc, la, lb, t.kbeg, t.kend, lds);
+    gemm_mainloop_x6<Cfg, DenseLoader6<true, Cfg::BM>, ConvFwdLoaderB6, 0, TERMS>(acc, la, lb, t.kbeg, t.kend, lds);
     gemm_epilogue<SEGX_EPI_NONE, Cfg>(acc, g, t);
 }
 template <class Cfg, int WPE, int FASTW>
@@ -1242,6 +1245,7 @@ struct ConvRoute {
     int engine, rows;    // ConvEngine; output channels per tile: 64 (CfgCout64) or 128 (Cfg128)
     bool wgrad, vec, packed;             // vec: 16-byte loads of the dense operand (filters / dY); packed: the order of segx_conv3d_pack_weights / ..._bwd_weight_packed
     int fastw;           // FASTW of conv3d_wgrad_x6_kernel: 0 = per-position decode, 1 = rows of eight / two quads, 2 = contiguous octet (0 off that kernel)
+    int terms;           // bf16 products per block: 3 = the three-term forward kernel (knob x6_terms = 3, bf16 engine, not a weight gradient), else 6 (also off the bf16 engine)
     int splitk, k_chunk, tiles_m, tiles_n;
     dim3 grid;
 };
@@ -1286,6 +1290,8 @@ static ConvRoute conv_route(const ConvGeom& q, int B, int Cout, bool wgrad, int 
         if (!x6) r.fastw = 0;
     }
     r.engine = x6 ? CONV_X6 : CONV_F32;
+    // the precision selector: forward-shaped launches (forward, backward-data) of the bf16 engine only -- the weight gradients stay six-term whatever it says
+    r.terms = !wgrad && x6 && kget(knobs().x6_terms) == 3 ? 3 : 6;
     r.tiles_m = ceil_div(Cout, r.rows); r.tiles_n = ceil_div(N, BN);
     r.grid = dim3(r.tiles_m * r.tiles_n, B, r.splitk);
     return r;
@@ -1295,7 +1301,7 @@ static ConvRoute conv_route(const ConvGeom& q, int B, int Cout, bool wgrad, int 
 using ConvKernel = void (*)(GemmArgs, ConvGeom);
 template <class Cfg, int WPE> static ConvKernel conv_tile_kernel(const ConvRoute& r) {
     if (r.engine == CONV_X6) {
-        if (!r.wgrad) return conv3d_fwd_x6_kernel<Cfg, WPE>;
+        if (!r.wgrad) return r.terms == 3 ? conv3d_fwd_x6_kernel<Cfg, WPE, 3> : conv3d_fwd_x6_kernel<Cfg, WPE>;
         return r.fastw == 2 ? conv3d_wgrad_x6_kernel<Cfg, WPE, 2> : r.fastw == 1 ? conv3d_wgrad_x6_kernel<Cfg, WPE, 1> : conv3d_wgrad_x6_kernel<Cfg, WPE, 0>;
     }
     return by_flag(r.vec, [&](auto v) { return by_flag(r.packed, [&](auto p) -> ConvKernel {
@@ -1344,6 +1350,16 @@ extern "C" int segx_conv3d_route(int B, int Cout, const int* geom, int wgrad, in
     out[6] = (int32_t)r.grid.x; out[7] = (int32_t)r.grid.y; out[8] = (int32_t)r.grid.z;
     return 0;
 }
+// the bf16 products per block a forward convolution would run under the knobs as they are now (include/segx.h); launches nothing
+extern "C" int segx_conv3d_fwd_terms(int B, int Cout, const int* geom, int splitk, int aligned, int packed) {
+    if (!geom || B <= 0 || Cout <= 0 || B > 65535) return 0;
+    const ConvGeom q = make_geom(geom);
+    const int64_t P = (int64_t)q.OD * q.OH * q.OW, CK = (int64_t)q.Cin * q.KD * q.KH * q.KW;
+    if (P <= 0 || P >= 2147483647LL || CK <= 0 || CK >= 2147483647LL || (packed && q.Cin % 8 != 0)) return 0;
+    if (segx_conv3d_halo_ok(B, Cout, geom)) return halo_fwd_terms();          // the call goes to the halo kernel (SF.conv3d_same asks the same question)
+    const ConvRoute r = conv_route(q, B, Cout, false, splitk < 1 ? 1 : splitk, aligned != 0, packed != 0);
+    return r.engine == CONV_X6 ? r.terms : 0;
+}
 /* One host path for both passes -- validate, route, fill the arguments, launch, sum the k slabs -- as the GEMM  out = dense x im2col(X):
  *   forward:          dense = the filters [Cout][Cin*KV], out = Y [B][Cout][P];
  *   weight gradient:  dense = dY [B][Cout][P], out = dWb [B][Cout][Cin*KV], per-sample rows (sum over b with segx_colsum).
@@ -1372,6 +1388,7 @@ static int conv3d_impl(bool wgrad, const float* dense, const float* X, float* ou
     g.dropout_p = 0.f; g.seed = g.offset = 0; g.rbase = nullptr; g.splitk = splitk; g.slab = 0; g.resid = nullptr;
     g.k_chunk = r.k_chunk; g.c_split = (int64_t)B * Cout * N;
     if (r.engine == CONV_X6) knobs().x6_launches.fetch_add(1, std::memory_order_relaxed);
+    if (r.terms == 3) knobs().x3_launches.fetch_add(1, std::memory_order_relaxed);
     hipLaunchKernelGGL(conv_kernel(r), r.grid, dim3(256), 0, stream, g, q);
     int rc = check_launch(who);
     if (rc || splitk == 1) return rc;

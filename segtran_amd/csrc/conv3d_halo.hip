@@ -75,12 +75,17 @@ template <int TW> __device__ __forceinline__ void halo_row_of(int r, int& q, int
     }
 }
 
-template <class Cfg, int WPE>
+// TERMS = 3 (knob x6_terms, read by segx_conv3d_halo_fwd): the three-term product hi.mid + mid.hi + hi.hi of gemm_x6.h -- the halo is split into the hi and mid planes only
+// (split2_pair), only those two planes of the filter bank are loaded and staged (the bank keeps its three-plane format), LDS is 2 PH + 2 PA, a step reads two fragments
+// per operand and issues three matrix instructions per block.  Everything else -- tile walk, staging maps, prefetches, epilogue -- is shared with TERMS = 6.
+template <class Cfg, int WPE, int TERMS = 6>
 __global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(WPE) void conv3d_halo_fwd_x6_kernel(HaloArgs g) {
-    constexpr int MI = Cfg::MI, NJ = Cfg::NJ, PA = Cfg::PA, PH = Cfg::PH, TW = Cfg::TW, TH = Cfg::TH, TD = Cfg::TD;
-    __shared__ __attribute__((aligned(16))) unsigned char lds[Cfg::LDS_BYTES];
+    static_assert(TERMS == 6 || TERMS == 3, "six or three bf16 products per block");
+    constexpr int MI = Cfg::MI, NJ = Cfg::NJ, PA = Cfg::PA, PH = Cfg::PH, TW = Cfg::TW, TH = Cfg::TH, TD = Cfg::TD, NPL = x6_planes(TERMS);
+    static_assert(NPL * (PH + PA) <= Cfg::LDS_BYTES, "the planes of this term count fit the configuration's LDS figure");
+    __shared__ __attribute__((aligned(16))) unsigned char lds[NPL * (PH + PA)];
     unsigned char* const LH = lds;                                   // halo: [plane][slot][8 channels] bf16
-    unsigned char* const LA_ = lds + 3 * PH;                         // weights: [plane][row][32 k] bf16, chunk-swizzled (x6_off)
+    unsigned char* const LA_ = lds + NPL * PH;                       // weights: [plane][row][32 k] bf16, chunk-swizzled (x6_off)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1, kh = lane >> 5;
     // ---- which tile: consecutive logical blocks share an XCD (L2): output-channel tiles of one spatial block first, then neighbours along W, H, D
     unsigned l = xcd_block(blockIdx.x, gridDim.x);
@@ -134,7 +139,7 @@ __global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(WPE) void conv3d_halo_
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
     float hreg[Cfg::H_ITEMS][8];
-    uvec4 wreg[3][Cfg::A_CHUNKS];                                   // (a native vector type: an array of HIP's uint4 structs stayed in scratch memory)
+    uvec4 wreg[NPL][Cfg::A_CHUNKS];                                  // (a native vector type: an array of HIP's uint4 structs stayed in scratch memory)
     auto load_halo = [&](int cb) {
         const float* const Xc = Xb + (int64_t)cb * 8 * chan;
 #pragma unroll
@@ -151,20 +156,20 @@ __global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(WPE) void conv3d_halo_
                 float v[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) v[j] = hoff[i] >= 0 ? hreg[i][j] : 0.f;
-                x6_store8<PH>(LH, hslot[i], v);
+                x6_store8<PH, TERMS>(LH, hslot[i], v);
             }
         }
     };
     auto load_w = [&](int tile) {                                    // tile = cb * 7 + tap quad
-        const int64_t base = (int64_t)tile * wtile;
+        const int64_t base = (int64_t)tile * wtile;                  // (the bank holds three planes per tile whatever TERMS is: hi, mid, lo)
 #pragma unroll
-        for (int p = 0; p < 3; ++p)
+        for (int p = 0; p < NPL; ++p)
 #pragma unroll
             for (int i = 0; i < Cfg::A_CHUNKS; ++i) wreg[p][i] = *reinterpret_cast<const uvec4*>(wsrc[i] + base + p * wplane);
     };
     auto store_w = [&]() {
 #pragma unroll
-        for (int p = 0; p < 3; ++p)
+        for (int p = 0; p < NPL; ++p)
 #pragma unroll
             for (int i = 0; i < Cfg::A_CHUNKS; ++i) *reinterpret_cast<uvec4*>(LA_ + p * PA + wdst[i]) = wreg[p][i];
     };
@@ -189,22 +194,24 @@ __global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(WPE) void conv3d_halo_
                 const int chunk = 2 * s + kh;
                 const int so0 = halo_tap_slot<Cfg>(halo_tap(pair, 0)) * 16, so1 = halo_tap_slot<Cfg>(halo_tap(pair, 1)) * 16;
                 const int so = so0 + kh * (so1 - so0);               // this lane's tap of the pair
-                bf16x8 a[MI][3];
+                bf16x8 a[MI][NPL];
 #pragma unroll
                 for (int i = 0; i < MI; ++i)
 #pragma unroll
-                    for (int p = 0; p < 3; ++p) a[i][p] = *reinterpret_cast<const bf16x8*>(LA_ + p * PA + x6_off(arow + 32 * i, chunk));
+                    for (int p = 0; p < NPL; ++p) a[i][p] = *reinterpret_cast<const bf16x8*>(LA_ + p * PA + x6_off(arow + 32 * i, chunk));
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) {
-                    bf16x8 bb[3];
+                    bf16x8 bb[NPL];
 #pragma unroll
-                    for (int p = 0; p < 3; ++p) bb[p] = *reinterpret_cast<const bf16x8*>(LH + p * PH + bslot[j] + so);
+                    for (int p = 0; p < NPL; ++p) bb[p] = *reinterpret_cast<const bf16x8*>(LH + p * PH + bslot[j] + so);
 #pragma unroll
                     for (int i = 0; i < MI; ++i) {
                         f32x16 c = acc[i][j];
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], bb[2], c, 0, 0, 0);     // hi . lo
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][2], bb[0], c, 0, 0, 0);     // lo . hi
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], bb[1], c, 0, 0, 0);     // mid . mid
+                        if constexpr (TERMS == 6) {
+                            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], bb[2], c, 0, 0, 0); // hi . lo
+                            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][2], bb[0], c, 0, 0, 0); // lo . hi
+                            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], bb[1], c, 0, 0, 0); // mid . mid
+                        }
                         c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], bb[1], c, 0, 0, 0);     // hi . mid
                         c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], bb[0], c, 0, 0, 0);     // mid . hi
                         c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], bb[0], c, 0, 0, 0);     // hi . hi
@@ -535,6 +542,8 @@ __global__ __launch_bounds__(256) void conv3d_halo_wgrad_reduce_kernel(const flo
 using namespace segx;
 #define SEGX_STREAM hipStream_t stream = (hipStream_t)stream_
 
+int segx::halo_fwd_terms() { return kget(knobs().x6_terms) == 3 ? 3 : 6; }
+
 static bool halo_geom_ok(const int* geom) {
     if (!geom) return false;
     const int Cin = geom[0], ID = geom[1], IH = geom[2], IW = geom[3];
@@ -601,15 +610,21 @@ extern "C" int segx_conv3d_halo_fwd(const float* X, const void* Wq, float* Y, in
     g.ntd = ceil_div(D, twd == 8 ? 4 : 8); g.nth = ceil_div(H, 4); g.ntw = ceil_div(W, twd); g.nmt = ceil_div(Cout, mtile); g.ncb = Cin / 8;
     const int64_t wgs = (int64_t)B * g.ntd * g.nth * g.ntw * g.nmt;
     SEGX_REQUIRE(wgs < 2147483647LL, "segx_conv3d_halo_fwd: grid too large");
+    // the precision selector: this function reads knob x6_terms itself (the data gradient is this launch on the other filter bank and follows it too; the Python
+    // interface sets 3 only without gradients, segx.h)
+    const int terms = halo_fwd_terms();
     knobs().x6_launches.fetch_add(1, std::memory_order_relaxed);
+    if (terms == 3) knobs().x3_launches.fetch_add(1, std::memory_order_relaxed);
     const dim3 grid((unsigned)wgs);
-#define SEGX_HALO_LAUNCH(MI, WPE) do { \
-        if (twd == 8) hipLaunchKernelGGL((conv3d_halo_fwd_x6_kernel<HaloCfg<MI, 4, 4, 8>, WPE>), grid, dim3(256), 0, stream, g); \
-        else hipLaunchKernelGGL((conv3d_halo_fwd_x6_kernel<HaloCfg<MI, 8, 4, 4>, WPE>), grid, dim3(256), 0, stream, g); } while (0)
+#define SEGX_HALO_LAUNCH_T(MI, WPE, TERMS) do { \
+        if (twd == 8) hipLaunchKernelGGL((conv3d_halo_fwd_x6_kernel<HaloCfg<MI, 4, 4, 8>, WPE, TERMS>), grid, dim3(256), 0, stream, g); \
+        else hipLaunchKernelGGL((conv3d_halo_fwd_x6_kernel<HaloCfg<MI, 8, 4, 4>, WPE, TERMS>), grid, dim3(256), 0, stream, g); } while (0)
+#define SEGX_HALO_LAUNCH(MI, WPE) do { if (terms == 3) SEGX_HALO_LAUNCH_T(MI, WPE, 3); else SEGX_HALO_LAUNCH_T(MI, WPE, 6); } while (0)
     if (mtile == 64) SEGX_HALO_LAUNCH(1, 4);
     else if (mtile == 128) SEGX_HALO_LAUNCH(2, 3);
     else SEGX_HALO_LAUNCH(3, 2);
 #undef SEGX_HALO_LAUNCH
+#undef SEGX_HALO_LAUNCH_T
     return check_launch("segx_conv3d_halo_fwd");
 }
 

@@ -269,7 +269,8 @@ static bool ws_tile_id(int tile) { return tile >= SEGX_TILE_256x128 && tile <= S
 // and the product shapes, folded and unfolded), all on the product schedule:
 //   wave-specialised, plain, A k-contiguous: 256 x 128, 128 x 128, 128 x 256 and 96 x 256 with B in either layout, 64 x 256 with B row-contiguous, 256 x 96;
 //   four-wave, dense loaders (K no multiple of 32): A k-contiguous, B row-contiguous -- a pointwise convolution -- plain and fused swish, the three tiles;
-//   four-wave, lean loaders: the same; the plain products with a k-contiguous B: NT (nn.Linear, Q.K^T) on 128 x 128 and 64 x 64, A row-contiguous on all three tiles;
+//   four-wave, lean loaders: the same; the plain products with a k-contiguous B, A in either layout (NT: nn.Linear, Q.K^T), on all three tiles -- NT on 64 x 128 is
+//   the one route the eval forward of the 3-D model added;
 //   the fused GELU (128 x 128, A k-contiguous) with B in either layout.
 // Every other route runs six-term whatever knob 20 says, and the counters show it (segx_x3_launches).
 static bool x3_built(const GemmRoute& r) {
@@ -280,7 +281,7 @@ static bool x3_built(const GemmRoute& r) {
         case GEMM_X6: return conv && r.epi != SEGX_EPI_GELU;
         case GEMM_X6_LEAN:
             if (!plain) return r.akc;                        // swish: A k-contiguous, B row-contiguous by the entry point's contract; GELU: A k-contiguous
-            return conv || (r.bkc && (r.tile != SEGX_TILE_64x128 || !r.akc));
+            return conv || r.bkc;                            // (NT on 64 x 128: the [2352 x 1024 x 256] x 16 attention product of the 3-D forward at cfg4's size)
         default: return false;
     }
 }
@@ -418,8 +419,7 @@ template <bool LEAN> static GemmLaunch x6_kernel(const GemmRoute& r) {
 template <bool LEAN, class Cfg, int W> static GemmLaunch x3_tile(const GemmRoute& r) {
     if (r.epi == SEGX_EPI_SWISH) return built_for<Cfg>(x6_form<LEAN, Cfg, true, false, SEGX_EPI_SWISH, W, 3>());
     if constexpr (LEAN) {
-        if constexpr (std::is_same<Cfg, Cfg64x128>::value) { if (r.bkc) return built_for<Cfg>(x6_form<true, Cfg, false, true, SEGX_EPI_NONE, W, 3>()); }
-        else if (r.bkc) return built_for<Cfg>(by_flag(r.akc, [](auto ak) { return x6_form<true, Cfg, decltype(ak)::value, true, SEGX_EPI_NONE, W, 3>(); }));
+        if (r.bkc) return built_for<Cfg>(by_flag(r.akc, [](auto ak) { return x6_form<true, Cfg, decltype(ak)::value, true, SEGX_EPI_NONE, W, 3>(); }));
     }
     return built_for<Cfg>(x6_form<LEAN, Cfg, true, false, SEGX_EPI_NONE, W, 3>());
 }

@@ -30,8 +30,8 @@ PRECISIONS = {'fp32': 6, 'bf16x3': 3}           # name -> Knob.X6_TERMS: bf16 pr
 
 @contextlib.contextmanager
 def inference_precision(name):
-    """with inference_precision('bf16x3'): the GEMMs of the bf16 tile engine run the three-term product (hi.mid + mid.hi + hi.hi on two bf16 planes per operand) on
-    the routes that have such a kernel -- accurate to (2^-15 + 2^-16) |A|.|B| per element instead of fp32-equivalent; 'fp32' is the default behaviour.
+    """with inference_precision('bf16x3'): the GEMMs and the forward 3-D convolutions of the bf16 tile engine run the three-term product (hi.mid + mid.hi + hi.hi on
+    two bf16 planes per operand) on the routes that have such a kernel -- accurate to (2^-15 + 2^-16) |A|.|B| per element instead of fp32-equivalent; 'fp32' is the default behaviour.
     The setting is process-wide for the duration of the block (segx_tune knob X6_TERMS) and the value it held comes back at the end, also after an exception.
     Inference only: the training parity bar rules the mode out, so entering with gradients enabled raises RuntimeError; an unknown name raises ValueError."""
     if name not in PRECISIONS:

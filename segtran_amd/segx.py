@@ -150,7 +150,7 @@ class SegxLib:
         return int(self.c.segx_tune(Knob.X6_LAUNCHES, 0))
 
     def x3_launches(self):
-        """launches of gemm() that ran the three-term bf16 product (Knob.X6_TERMS = 3) since the last call; x6_launches() - x3_launches() of the same span
+        """launches of gemm(), conv3d_fwd() and conv3d_halo_fwd() that ran the three-term bf16 product (Knob.X6_TERMS = 3) since the last call; x6_launches() - x3_launches() of the same span
         asked for three terms and ran six"""
         return int(self.c.segx_x3_launches())
 
@@ -608,6 +608,16 @@ class SegxLib:
         self.check(self.c.segx_conv3d_route(B, Cout, self._geom(geom), int(bool(wgrad)), splitk, int(bool(aligned)), int(bool(packed)), out), 'segx_conv3d_route')
         return ('f32', 'x6')[out[0]], out[1], bool(out[2]), out[4], out[5], tuple(out[6:9])
 
+    def conv3d_fwd_terms(self, B, Cout, geom, splitk=1, aligned=True, packed=None):
+        """bf16 products per block (6 or 3) the forward convolution would run under the knobs as they are now: the halo kernel's where conv3d_halo_ok() accepts the
+        call, else the implicit GEMM's route; 0 off the bf16 tile engine (segx_conv3d_fwd_terms); packed=None as for conv3d_route"""
+        packed = geom[0] % 8 == 0 if packed is None else packed
+        return int(self.c.segx_conv3d_fwd_terms(B, Cout, self._geom(geom), splitk, int(bool(aligned)), int(bool(packed))))
+
+    def conv3d_fwd_packed(self, X, Wp, Y, B, Cout, geom, splitk=1, ws=None, x_bs=0, y_bs=0):
+        """conv3d_fwd with the filters in the packed contraction order of conv3d_pack_weights (Cin % 8 == 0)"""
+        self.conv3d_fwd(X, Wp, Y, B, Cout, geom, splitk, ws, packed=True, x_bs=x_bs, y_bs=y_bs)
+
     def conv3d_fwd(self, X, W, Y, B, Cout, geom, splitk=1, ws=None, packed=False, x_bs=0, y_bs=0):
         """x_bs / y_bs (packed only): X / Y are channel slices of wider tensors whose samples lie that many floats apart (0 = dense)."""
         self._chk_t(X, W, Y, ws)
@@ -762,7 +772,7 @@ _SIGS = {
     'segx_gray_mean_ws_floats': 'il', 'segx_gray_mean': 'pppilip', 'segx_normalize': 'ppiilfppp',
     'segx_x6_presplit_elems': 'iiii', 'segx_x6_presplit': 'piilliillpp',
     'segx_tune': 'ii', 'segx_tune_get': 'i', 'segx_x3_launches': '', 'segx_gemm_route': 'pppp', 'segx_set_rng_base': 'p', 'segx_rng_advance': 'pup', 'segx_resized_crop3d': 'pplpp', 'segx_stem_compose_fwd': 'ppppiiiiip', 'segx_stem_compose_bwd': 'pppppppiiiiip', 'segx_bridge_input': 'ppiiiiiip', 'segx_stem_s2d_input': 'ppiiiiiip', 'segx_conv2d_stem_fwd': 'pppiiiiiiiiiiip', 'segx_conv2d_stem_im2col': 'ppiiiiiiiiiiip', 'segx_dropout': 'pplfuup', 'segx_avgpool2_fwd': 'ppliip', 'segx_avgpool2_bwd': 'ppliip', 'segx_transpose': 'ppliip', 'segx_interp_linear_fwd_axis': 'pppliilfp', 'segx_window_accum': 'pppiipp', 'segx_harden_segmap': 'ppppiilifp', 'segx_window_gather': 'ppppiiipp', 'segx_window_merge': 'pppppiiipifp', 'segx_dice_ws_floats': 'll', 'segx_dice_sums': 'pppllp',
-    'segx_conv3d_fwd': 'pppiipipp', 'segx_conv3d_fwd_packed': 'pppiipipp', 'segx_conv3d_fwd_packed_bs': 'pppiipipllp', 'segx_conv3d_bwd_weight_packed_bs': 'pppiipipllp', 'segx_conv3d_pack_weights': 'ppiiiip', 'segx_conv3d_splitk': 'iipi', 'segx_conv3d_route': 'iipiiiip', 'segx_conv3d_flip_weights': 'ppiiip', 'segx_conv3d_bwd_weight': 'pppiipipp', 'segx_conv3d_bwd_weight_packed': 'pppiipipp', 'segx_conv3d_unpack_wgrad': 'ppiiip',
+    'segx_conv3d_fwd': 'pppiipipp', 'segx_conv3d_fwd_packed': 'pppiipipp', 'segx_conv3d_fwd_packed_bs': 'pppiipipllp', 'segx_conv3d_bwd_weight_packed_bs': 'pppiipipllp', 'segx_conv3d_pack_weights': 'ppiiiip', 'segx_conv3d_splitk': 'iipi', 'segx_conv3d_route': 'iipiiiip', 'segx_conv3d_fwd_terms': 'iipiii', 'segx_conv3d_flip_weights': 'ppiiip', 'segx_conv3d_bwd_weight': 'pppiipipp', 'segx_conv3d_bwd_weight_packed': 'pppiipipp', 'segx_conv3d_unpack_wgrad': 'ppiiip',
     'segx_conv3d_halo_ok': 'iip', 'segx_conv3d_halo_wq_floats': 'ii', 'segx_conv3d_halo_pack': 'ppiiip', 'segx_conv3d_halo_fwd': 'pppiipllip', 'segx_conv3d_halo_wgrad_ok': 'iip', 'segx_conv3d_halo_wgrad_ws_floats': 'iip', 'segx_conv3d_halo_wgrad': 'ppppiipllp',
     'segx_conv3d_bwd_data_direct': 'ppppiipp', 'segx_nonzero_mask': 'ppiiiiiiiip', 'segx_label_nhot': 'ppiilip',
     'segx_maxpool3d_fwd': 'ppplpp', 'segx_maxpool3d_bwd': 'ppplppp',
