@@ -628,6 +628,34 @@ int segx_window_merge(const float* scores, const int* origins, const int* origin
 int64_t segx_dice_ws_floats(int64_t planes, int64_t S);
 int segx_dice_sums(const float* pred, const float* gt, float* part, int64_t planes, int64_t S, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Surface-distance metrics of the 3-D evaluation (metrics.hip): medpy.metric.binary.asd(pred, gt) of calculate_metric_percase (test_util3d.py:203-206) and the
+ * hd95 of its commented-out line, for unit voxel spacing and connectivity 1, in integers: a border map, an exact squared distance field, a histogram of the
+ * squared distances on the other mask's border.  The caller finishes in float64: asd = sum hist[k] sqrt(k) / sum hist[k]; hd95 = the 95th percentile of the
+ * two directions' distances, read from the cumulative counts.  Tensors are [planes][D][H][W], W contiguous; a 2-D image has D = 1.
+ * ------------------------------------------------------------------------------------------- */
+/* Distance of a line / plane without a border voxel.  No real squared distance reaches it (they stay below 3 * SEGX_EDT_MAX_EXTENT^2 = 196 608), and
+ * SEGX_EDT_INF + SEGX_EDT_MAX_EXTENT^2 stays inside int32, so a pass may add an offset to it before clamping back.  A plane with no border voxel ends as all
+ * SEGX_EDT_INF. */
+#define SEGX_EDT_INF 0x40000000
+/* Largest D, H or W of segx_edt_sq / segx_surface_hist: a workgroup of an H or D pass stages whole lines of 32 columns in LDS -- SEGX_EDT_MAX_EXTENT * 32 * 4 bytes
+ * = 32 KiB, four workgroups per compute unit by LDS (160 KiB) -- and a lane of the W pass holds four cells of its row.  240 x 240 x 155 (BraTS) fits; a larger
+ * extent is refused. */
+#define SEGX_EDT_MAX_EXTENT 256
+/* border = mask XOR binary_erosion(mask) with the face neighbourhood (medpy __surface_distances, connectivity 1; test_util3d.py:203-206 through
+ * metric.binary.asd): a voxel is set iff mask != 0; a neighbour outside the array counts as unset, so a set voxel on a face of the volume is a border voxel.
+ * nd = 3: six neighbours (D = 1 erodes to nothing, as medpy's rank-3 erosion does); nd = 2: the four in-plane neighbours (every z slice on its own).
+ * mask: floats, border: bytes (0 / 1). */
+int segx_surface_border(const float* mask, uint8_t* border, int64_t planes, int D, int H, int W, int nd, void* stream);
+/* d2[v] = the squared Euclidean distance from v to the nearest set voxel of border[plane], for EVERY voxel (scipy's distance_transform_edt(~border) squared, the
+ * `dt` of medpy's __surface_distances; test_util3d.py:203-206), exact in int32; SEGX_EDT_INF throughout a plane without a set voxel.  Separable: a W pass, then an
+ * H and a D pass in place, each the full minimum over its line.  No workspace.  D, H, W <= SEGX_EDT_MAX_EXTENT. */
+int segx_edt_sq(const uint8_t* border, int32_t* d2, int64_t planes, int D, int H, int W, void* stream);
+/* hist[plane][k] += the number of voxels v with border_from[plane][v] set and d2_to[plane][v] == k (medpy's sds = dt[border(result)], test_util3d.py:203-206, as
+ * counts): hist is int32 [planes][nbins], zeroed by the caller, nbins >= (D-1)^2 + (H-1)^2 + (W-1)^2 + 1; a voxel with k >= nbins (the sentinel) is not counted.
+ * Integer atomic adds: the result does not depend on their order.  planes <= 65535. */
+int segx_surface_hist(const uint8_t* border_from, const int32_t* d2_to, int32_t* hist, int64_t planes, int D, int H, int W, int nbins, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

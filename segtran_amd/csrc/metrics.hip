@@ -1,0 +1,158 @@
+// metrics.hip -- surface-distance metrics of the 3-D evaluation: what medpy.metric.binary.asd / hd95 compute for
+// calculate_metric_percase (test_util3d.py:203-206), with unit voxel spacing and connectivity 1, as three image-sized integer kernels:
+//   surface_border   border(m) = m XOR erode(m), face neighbourhood, out-of-array neighbours unset (medpy __surface_distances: binary_erosion, border_value 0)
+//   edt_sq           the exact squared Euclidean distance to the nearest border voxel (scipy distance_transform_edt of the complement, squared), separable:
+//                    one pass per axis, out[y] = min over y' of (f[y'] + (y - y')^2) over the WHOLE line -- O(extent) per voxel, no envelope bookkeeping, int32
+//   surface_hist     hist[plane][k] = number of border voxels of the other mask at squared distance k (integer atomic adds: order-independent, bit-reproducible)
+// The float64 finish (mean of sqrt(k) weighted by the counts, the 95th percentile from the cumulative counts) is a few lines on the host (infer3d.py).
+#include "common.h"
+
+namespace segx {
+
+constexpr int EDT_INF = SEGX_EDT_INF, EDT_MAX = SEGX_EDT_MAX_EXTENT;
+constexpr int EDT_SLAB = 32;                 // consecutive cells of the contiguous axis a workgroup of an H / D pass owns: 128-byte global rows, one bank each in LDS
+constexpr int HIST_LOW = 1024;               // bins a workgroup of surface_hist keeps in LDS (distances below 32 voxels: where surfaces that nearly agree pile up)
+
+// border[p][z][y][x] = set && !(every face neighbour set); a neighbour outside the array is unset.  nd == 2: the z neighbours do not exist (a stack of images).
+// One thread per voxel.
+__global__ __launch_bounds__(256) void surface_border_kernel(const float* __restrict__ mask, uint8_t* __restrict__ border, int64_t planes, int D, int H, int W,
+                                                             int nd) {
+    const int64_t HW = (int64_t)H * W, total = planes * D * HW;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        int64_t r = idx % ((int64_t)D * HW);
+        const int z = (int)(r / HW); r -= (int64_t)z * HW;
+        const int y = (int)(r / W), x = (int)(r - (int64_t)y * W);
+        bool b = false;
+        if (mask[idx] != 0.0f) {
+            bool in = x > 0 && x < W - 1 && y > 0 && y < H - 1 && (nd == 2 || (z > 0 && z < D - 1));
+            if (in) {
+                in = mask[idx - 1] != 0.0f && mask[idx + 1] != 0.0f && mask[idx - W] != 0.0f && mask[idx + W] != 0.0f;
+                if (in && nd == 3) in = mask[idx - HW] != 0.0f && mask[idx + HW] != 0.0f;
+            }
+            b = !in;
+        }
+        border[idx] = b ? 1 : 0;
+    }
+}
+
+// W pass: d2[row][x] = min over x' with border[row][x'] set of (x - x')^2, EDT_INF for a row without one.  A wave owns a row (staged in LDS as 0 / EDT_INF; every
+// lane reads the same x': a broadcast) and a lane up to four cells of it, 64 apart: W <= 256.
+__global__ __launch_bounds__(256) void edt_row_kernel(const uint8_t* __restrict__ border, int* __restrict__ d2, int64_t rows, int W) {
+    __shared__ int f[4 * EDT_MAX];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int* fr = f + wave * EDT_MAX;
+    for (int64_t row0 = (int64_t)blockIdx.x * 4; row0 < rows; row0 += (int64_t)gridDim.x * 4) {
+        const int64_t row = row0 + wave;
+        if (row < rows)
+            for (int x = lane; x < W; x += 64) fr[x] = border[row * W + x] ? 0 : EDT_INF;
+        __syncthreads();
+        if (row < rows) {
+            int o0 = EDT_INF, o1 = EDT_INF, o2 = EDT_INF, o3 = EDT_INF;
+            for (int xp = 0; xp < W; ++xp) {
+                const int v = fr[xp], t = lane - xp;
+                o0 = min(o0, v + t * t); o1 = min(o1, v + (t + 64) * (t + 64)); o2 = min(o2, v + (t + 128) * (t + 128)); o3 = min(o3, v + (t + 192) * (t + 192));
+            }
+            int* o = d2 + row * W;
+            if (lane < W) o[lane] = min(o0, EDT_INF);
+            if (lane + 64 < W) o[lane + 64] = min(o1, EDT_INF);
+            if (lane + 128 < W) o[lane + 128] = min(o2, EDT_INF);
+            if (lane + 192 < W) o[lane + 192] = min(o3, EDT_INF);
+        }
+        __syncthreads();
+    }
+}
+
+// H / D pass, in place, on g viewed as [outer][n][inner] (inner contiguous): g[o][y][x] = min(EDT_INF, min over y' of (g[o][y'][x] + (y - y')^2)).  A workgroup owns
+// the n lines of EDT_SLAB consecutive x of one o, staged in LDS as [n][EDT_SLAB]: global rows of 128 bytes, LDS reads across lanes in x (32 banks, the two halves of a
+// wave read the same addresses).  A thread computes four consecutive outputs of its column per sweep over the line, so one LDS read feeds four add / min pairs.
+// It reads the LDS copy and writes only global memory: in place is safe, the slab is this workgroup's alone.
+__global__ __launch_bounds__(256) void edt_axis_kernel(int* __restrict__ g, int64_t outer, int n, int64_t inner) {
+    __shared__ int f[EDT_MAX * EDT_SLAB];
+    const int64_t slabs = (inner + EDT_SLAB - 1) / EDT_SLAB, items = outer * slabs;
+    const int tx = threadIdx.x & (EDT_SLAB - 1), ty = threadIdx.x / EDT_SLAB;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t o = item / slabs, x = (item - o * slabs) * EDT_SLAB + tx;
+        int* col = g + o * n * inner + x;
+        for (int y = ty; y < n; y += 256 / EDT_SLAB) f[y * EDT_SLAB + tx] = x < inner ? col[(int64_t)y * inner] : EDT_INF;
+        __syncthreads();
+        for (int y0 = ty * 4; y0 < n; y0 += 4 * (256 / EDT_SLAB)) {
+            int o0 = EDT_INF, o1 = EDT_INF, o2 = EDT_INF, o3 = EDT_INF;
+            for (int yp = 0; yp < n; ++yp) {
+                const int v = f[yp * EDT_SLAB + tx], t = y0 - yp;
+                o0 = min(o0, v + t * t); o1 = min(o1, v + (t + 1) * (t + 1)); o2 = min(o2, v + (t + 2) * (t + 2)); o3 = min(o3, v + (t + 3) * (t + 3));
+            }
+            if (x < inner) {
+                col[(int64_t)y0 * inner] = min(o0, EDT_INF);
+                if (y0 + 1 < n) col[(int64_t)(y0 + 1) * inner] = min(o1, EDT_INF);
+                if (y0 + 2 < n) col[(int64_t)(y0 + 2) * inner] = min(o2, EDT_INF);
+                if (y0 + 3 < n) col[(int64_t)(y0 + 3) * inner] = min(o3, EDT_INF);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// hist[plane][k] += 1 for every voxel of border[plane] whose d2[plane] is k < nbins.  blockIdx.y = plane; the low bins are counted in LDS and added to global
+// memory once per workgroup, the rest go to global memory directly.
+__global__ __launch_bounds__(256) void surface_hist_kernel(const uint8_t* __restrict__ border, const int* __restrict__ d2, int* __restrict__ hist, int64_t S,
+                                                           int nbins) {
+    __shared__ int low[HIST_LOW];
+    const int plane = blockIdx.y;
+    const uint8_t* b = border + (int64_t)plane * S; const int* d = d2 + (int64_t)plane * S; int* h = hist + (int64_t)plane * nbins;
+    for (int i = threadIdx.x; i < HIST_LOW; i += 256) low[i] = 0;
+    __syncthreads();
+    for (int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x; s < S; s += (int64_t)gridDim.x * 256) {
+        if (!b[s]) continue;
+        const unsigned k = (unsigned)d[s];
+        if (k >= (unsigned)nbins) continue;
+        if (k < (unsigned)HIST_LOW) atomicAdd(&low[k], 1);
+        else atomicAdd(&h[k], 1);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < HIST_LOW && i < nbins; i += 256)
+        if (low[i]) atomicAdd(&h[i], low[i]);
+}
+
+}  // namespace segx
+
+using namespace segx;
+#define SEGX_STREAM hipStream_t stream = (hipStream_t)stream_
+
+static inline int64_t edt_bins(int D, int H, int W) { return (int64_t)(D - 1) * (D - 1) + (int64_t)(H - 1) * (H - 1) + (int64_t)(W - 1) * (W - 1) + 1; }
+
+extern "C" int segx_surface_border(const float* mask, uint8_t* border, int64_t planes, int D, int H, int W, int nd, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(mask && border, "segx_surface_border: null pointer");
+    SEGX_REQUIRE(planes > 0 && D > 0 && H > 0 && W > 0, "segx_surface_border: planes, D, H and W must be positive");
+    SEGX_REQUIRE(nd == 2 || nd == 3, "segx_surface_border: nd is 2 or 3, not %d", nd);
+    const int64_t total = planes * D * H * W;
+    hipLaunchKernelGGL(surface_border_kernel, dim3((unsigned)i64min(65536, (total + 255) / 256)), dim3(256), 0, stream, mask, border, planes, D, H, W, nd);
+    return check_launch("segx_surface_border");
+}
+
+extern "C" int segx_edt_sq(const uint8_t* border, int32_t* d2, int64_t planes, int D, int H, int W, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(border && d2, "segx_edt_sq: null pointer");
+    SEGX_REQUIRE(planes > 0 && D > 0 && H > 0 && W > 0, "segx_edt_sq: planes, D, H and W must be positive");
+    SEGX_REQUIRE(D <= EDT_MAX && H <= EDT_MAX && W <= EDT_MAX, "segx_edt_sq: extents %d x %d x %d above the cap of %d per axis", D, H, W, EDT_MAX);
+    const int64_t rows = planes * D * H;
+    hipLaunchKernelGGL(edt_row_kernel, dim3((unsigned)i64min(65536, (rows + 3) / 4)), dim3(256), 0, stream, border, d2, rows, W);
+    if (H > 1) {
+        const int64_t items = planes * D * ((W + EDT_SLAB - 1) / EDT_SLAB);
+        hipLaunchKernelGGL(edt_axis_kernel, dim3((unsigned)i64min(1 << 20, items)), dim3(256), 0, stream, d2, planes * D, H, (int64_t)W);
+    }
+    if (D > 1) {
+        const int64_t inner = (int64_t)H * W, items = planes * ((inner + EDT_SLAB - 1) / EDT_SLAB);
+        hipLaunchKernelGGL(edt_axis_kernel, dim3((unsigned)i64min(1 << 20, items)), dim3(256), 0, stream, d2, planes, D, inner);
+    }
+    return check_launch("segx_edt_sq");
+}
+
+extern "C" int segx_surface_hist(const uint8_t* border_from, const int32_t* d2_to, int32_t* hist, int64_t planes, int D, int H, int W, int nbins, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(border_from && d2_to && hist, "segx_surface_hist: null pointer");
+    SEGX_REQUIRE(planes > 0 && planes <= 65535 && D > 0 && H > 0 && W > 0, "segx_surface_hist: 1 <= planes <= 65535, D, H and W positive");
+    SEGX_REQUIRE(D <= EDT_MAX && H <= EDT_MAX && W <= EDT_MAX, "segx_surface_hist: extents %d x %d x %d above the cap of %d per axis", D, H, W, EDT_MAX);
+    SEGX_REQUIRE(nbins >= edt_bins(D, H, W), "segx_surface_hist: nbins %d below (D-1)^2 + (H-1)^2 + (W-1)^2 + 1 = %lld", nbins, (long long)edt_bins(D, H, W));
+    const int64_t S = (int64_t)D * H * W;
+    hipLaunchKernelGGL(surface_hist_kernel, dim3((unsigned)i64max(1, i64min(1024, (S + 4095) / 4096)), (unsigned)planes), dim3(256), 0, stream, border_from, d2_to,
+                       hist, S, nbins);
+    return check_launch("segx_surface_hist");
+}

@@ -2313,3 +2313,51 @@ def dice_scores(pred, gt, smooth=1e-5):
     S = pred.numel() // P
     sums = L.dice_sums(pred, gt, P, S)
     return (2 * sums[:, 0] + smooth) / (sums[:, 1] + sums[:, 2] + smooth)
+
+
+# -------------------------------------------------------------------------------------------------
+# Surface-distance metrics (metrics.hip): border map, exact squared distance field, histogram of squared surface distances.  Planes-first tensors:
+# [P, H, W] is a stack of images (nd = 2), [P, D, H, W] a stack of volumes (nd = 3).  Forward only.
+# -------------------------------------------------------------------------------------------------
+def _surface_operand(what, t, dtype=None):
+    if torch.is_grad_enabled() and t.requires_grad:
+        raise RuntimeError(what + ' is forward-only: call it under torch.no_grad() or on tensors without gradient')
+    if t.dim() not in (3, 4):
+        raise ValueError('%s: [P, H, W] or [P, D, H, W] tensors, not rank %d' % (what, t.dim()))
+    if dtype is not None and t.dtype != dtype:
+        raise TypeError('%s: a %s tensor, not %s' % (what, dtype, t.dtype))
+    P = t.shape[0]
+    D, H, W = (1,) * (4 - t.dim()) + tuple(t.shape[1:])
+    return _c(t.detach()), P, D, H, W
+
+
+def surface_border(masks):
+    """border = mask XOR erode(mask) with the face neighbourhood (4 neighbours for [P, H, W], 6 for [P, D, H, W]); a voxel is set iff it is not 0, neighbours
+    outside the array are unset.  What medpy's surface distances call the surface (connectivity 1).  Returns uint8 0 / 1 of the same shape."""
+    m, P, D, H, W = _surface_operand('surface_border', masks)
+    m = m.float()
+    border = torch.empty(m.shape, dtype=torch.uint8, device=m.device)
+    segx.lib().surface_border(m, border, P, D, H, W, m.dim() - 1)
+    return border
+
+
+def edt_sq(border):
+    """int32 squared Euclidean distance (unit spacing) of EVERY voxel to the nearest set voxel of its plane of `border` (uint8), exact; a plane without a set voxel
+    is segx.SegxLib.EDT_INF throughout.  Extents above segx.SegxLib.EDT_MAX_EXTENT are refused."""
+    b, P, D, H, W = _surface_operand('edt_sq', border, torch.uint8)
+    d2 = torch.empty(b.shape, dtype=torch.int32, device=b.device)
+    segx.lib().edt_sq(b, d2, P, D, H, W)
+    return d2
+
+
+def surface_hist(border_from, d2_to):
+    """int32 [P, nbins], nbins = (D-1)^2 + (H-1)^2 + (W-1)^2 + 1: hist[p, k] = number of set voxels of border_from[p] (uint8) whose d2_to[p] (int32, from edt_sq) is
+    k -- the squared surface distances from one mask's border to the other's as counts.  Voxels at the sentinel (an empty other mask) are not counted."""
+    b, P, D, H, W = _surface_operand('surface_hist', border_from, torch.uint8)
+    d, *_ = _surface_operand('surface_hist', d2_to, torch.int32)
+    if b.shape != d.shape:
+        raise ValueError('surface_hist: border_from %s and d2_to %s differ in shape' % (tuple(b.shape), tuple(d.shape)))
+    nbins = (D - 1) ** 2 + (H - 1) ** 2 + (W - 1) ** 2 + 1
+    hist = torch.zeros(P, nbins, dtype=torch.int32, device=b.device)
+    segx.lib().surface_hist(b, d, hist, P, D, H, W, nbins)
+    return hist

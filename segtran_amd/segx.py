@@ -597,6 +597,18 @@ class SegxLib:
         self.colsum(part, out, ws, chunks, planes * 3)
         return out.view(planes, 3)
 
+    # ---- surface-distance metrics (metrics.hip) -------------------------------------------------------
+    EDT_INF, EDT_MAX_EXTENT = 0x40000000, 256            # SEGX_EDT_INF, SEGX_EDT_MAX_EXTENT of include/segx.h
+
+    def surface_border(self, mask, border, planes, D, H, W, nd):
+        self._call('segx_surface_border', mask, mask, border, planes, D, H, W, nd)
+
+    def edt_sq(self, border, d2, planes, D, H, W):
+        self._call('segx_edt_sq', border, border, d2, planes, D, H, W)
+
+    def surface_hist(self, border_from, d2_to, hist, planes, D, H, W, nbins):
+        self._call('segx_surface_hist', hist, border_from, d2_to, hist, planes, D, H, W, nbins)
+
     def conv3d_splitk(self, B, Cout, geom, wgrad):
         return int(self.c.segx_conv3d_splitk(B, Cout, self._geom(geom), 1 if wgrad else 0))
 
@@ -772,6 +784,7 @@ _SIGS = {
     'segx_gray_mean_ws_floats': 'il', 'segx_gray_mean': 'pppilip', 'segx_normalize': 'ppiilfppp',
     'segx_x6_presplit_elems': 'iiii', 'segx_x6_presplit': 'piilliillpp',
     'segx_tune': 'ii', 'segx_tune_get': 'i', 'segx_x3_launches': '', 'segx_gemm_route': 'pppp', 'segx_set_rng_base': 'p', 'segx_rng_advance': 'pup', 'segx_resized_crop3d': 'pplpp', 'segx_stem_compose_fwd': 'ppppiiiiip', 'segx_stem_compose_bwd': 'pppppppiiiiip', 'segx_bridge_input': 'ppiiiiiip', 'segx_stem_s2d_input': 'ppiiiiiip', 'segx_conv2d_stem_fwd': 'pppiiiiiiiiiiip', 'segx_conv2d_stem_im2col': 'ppiiiiiiiiiiip', 'segx_dropout': 'pplfuup', 'segx_avgpool2_fwd': 'ppliip', 'segx_avgpool2_bwd': 'ppliip', 'segx_transpose': 'ppliip', 'segx_interp_linear_fwd_axis': 'pppliilfp', 'segx_window_accum': 'pppiipp', 'segx_harden_segmap': 'ppppiilifp', 'segx_window_gather': 'ppppiiipp', 'segx_window_merge': 'pppppiiipifp', 'segx_dice_ws_floats': 'll', 'segx_dice_sums': 'pppllp',
+    'segx_surface_border': 'ppliiiip', 'segx_edt_sq': 'ppliiip', 'segx_surface_hist': 'pppliiiip',
     'segx_conv3d_fwd': 'pppiipipp', 'segx_conv3d_fwd_packed': 'pppiipipp', 'segx_conv3d_fwd_packed_bs': 'pppiipipllp', 'segx_conv3d_bwd_weight_packed_bs': 'pppiipipllp', 'segx_conv3d_pack_weights': 'ppiiiip', 'segx_conv3d_splitk': 'iipi', 'segx_conv3d_route': 'iipiiiip', 'segx_conv3d_fwd_terms': 'iipiii', 'segx_conv3d_flip_weights': 'ppiiip', 'segx_conv3d_bwd_weight': 'pppiipipp', 'segx_conv3d_bwd_weight_packed': 'pppiipipp', 'segx_conv3d_unpack_wgrad': 'ppiiip',
     'segx_conv3d_halo_ok': 'iip', 'segx_conv3d_halo_wq_floats': 'ii', 'segx_conv3d_halo_pack': 'ppiiip', 'segx_conv3d_halo_fwd': 'pppiipllip', 'segx_conv3d_halo_wgrad_ok': 'iip', 'segx_conv3d_halo_wgrad_ws_floats': 'iip', 'segx_conv3d_halo_wgrad': 'ppppiipllp',
     'segx_conv3d_bwd_data_direct': 'ppppiipp', 'segx_nonzero_mask': 'ppiiiiiiiip', 'segx_label_nhot': 'ppiilip',
