@@ -656,6 +656,29 @@ int segx_edt_sq(const uint8_t* border, int32_t* d2, int64_t planes, int D, int H
  * Integer atomic adds: the result does not depend on their order.  planes <= 65535. */
 int segx_surface_hist(const uint8_t* border_from, const int32_t* d2_to, int32_t* hist, int64_t planes, int D, int H, int W, int nbins, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Tail of the 2-D evaluation (components.hip): connected components, fragment removal (test_util2d.py:267-289), row extents for the vertical cup/disc ratio
+ * (utils/losses.py:76-127) and the n-hot -> pixel-value maps (datasets2d.py:144-171).  Stacks of planes [P][H][W], W contiguous, H * W < SEGX_CCL_MAX_PLANE.
+ * Integer results, exact and independent of the order of execution.  No call copies to the host or synchronises the stream.
+ * ------------------------------------------------------------------------------------------- */
+#define SEGX_CCL_TILE_H 32              /* the tile one workgroup labels in LDS; tests place their seams by these */
+#define SEGX_CCL_TILE_W 64
+#define SEGX_CCL_MAX_PLANE 0x40000000   /* H * W must stay below 2^30: plane indices and 1 + index are held in int32 */
+/* 8-connected components (cv2.connectedComponents' default connectivity) of every plane of fg: a pixel is background iff fg == bg_value (0 for a 0 / 1 mask).
+ * labels: 0 on the background, else 1 + the raster index inside the plane of the component's first pixel.  sizes: the component's pixel count at the cell of its
+ * first pixel, 0 everywhere else.  Both are written in full; no workspace.  One workgroup per tile in one grid: planes * tiles per plane < 2^24. */
+int segx_ccl2d(const uint8_t* fg, int bg_value, int32_t* labels, int32_t* sizes, int64_t planes, int H, int W, void* stream);
+/* keep[plane][0..1] = the two candidates with the largest counts, largest first: every component (its label, count from sizes) and, when it has at least one pixel,
+ * the background (label 0, count H * W - sum of sizes).  Ties go to the background, then to the lower label.  -1 where fewer than two candidates exist.  One workgroup of
+ * 1024 threads per plane in one grid: planes < 2^22. */
+int segx_frag_keep2(const int32_t* sizes, int32_t* keep, int64_t planes, int H, int W, void* stream);
+/* out = (label == 0 || label is one of keep[plane]) ? seg : bg_value */
+int segx_frag_apply(const uint8_t* seg, const int32_t* labels, const int32_t* keep, uint8_t* out, int64_t planes, int H, int W, int bg_value, void* stream);
+/* ext[plane] = (lowest, highest) row index that holds a value >= thres, (H, -1) where none does (a NaN is below every threshold).  ext is initialised here. */
+int segx_row_extent(const float* mask, int32_t* ext, int64_t planes, int H, int W, float thres, void* stream);
+/* out[b][s] = values[c] of the LAST class c with nhot[b][c][s] == 1, 0 where no class is on (the reference assigns class by class, ascending). */
+int segx_nhot_to_values(const float* nhot, const int32_t* values, uint8_t* out, int64_t B, int C, int64_t S, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

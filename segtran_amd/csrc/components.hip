@@ -1,0 +1,331 @@
+// components.hip -- the tail of the 2-D (fundus / polyp) evaluation on the device: 8-connected component labelling, removal of fragmentary segments
+// (test_util2d.py:267-289), the row extents behind the vertical cup/disc ratio (utils/losses.py:76-127) and the n-hot -> pixel-value maps
+// (datasets2d.py:144-171, 225-...).  Integer kernels with exact, order-independent results; no host round trip, no stream synchronisation.
+//
+// Labelling of uint8 planes [P][H][W] in three launches.  A label is 1 + the raster index (inside its plane) of another pixel of the same component that is
+// NOT LATER in raster order -- a parent pointer -- and 0 on the background; a pixel whose label is 1 + its own index is a root.
+//   (a) ccl_tile_kernel     one workgroup labels a CCL_TH x CCL_TW tile in LDS by label equivalence to a fixed point (Kalentev et al. 2011): every component of the
+//                           tile ends on its first pixel; the pixels of each are counted with LDS integer adds; the tile writes global parent pointers and, at
+//                           each tile-local root, the local count (0 everywhere else).
+//   (b) ccl_seam_kernel     one thread per pixel on the right column / bottom row of a tile unites it with its set neighbours across the seam (right, below and
+//                           both diagonals) by the union that needs only atomicMin (Komura 2015; Playne & Hawick 2018).
+//   (c) ccl_flatten_kernel  every pixel is pointed at its root, and every tile-local root hands its count to the final root: ONE integer atomicAdd per
+//                           tile-local component, not one per pixel (a 10^6-pixel disc adding into one word would run at the single-address atomic rate).
+//
+// Why (b) is right without locks, and ends.  Labels only ever DECREASE, and a cell only ever points to a member of its own set, because the only writes are
+// atomicMin(&L[a], b + 1) with b < a and a, b being united.  So whatever a thread reads -- also a stale value out of a cache that another XCD's atomic has since
+// lowered -- is 1 + an ancestor-or-former-ancestor: following such values walks down a strictly decreasing sequence of non-negative indices inside the plane and
+// stops at a cell that WAS a root when it was read.  Two walks that meet prove the sets are already one.  Otherwise the larger root a takes atomicMin with the
+// smaller one; the returned old value is the arbiter: if it is a + 1, a was still a root and is now linked -- done; else some other thread linked a to old - 1 < a
+// in between (that link may just have been replaced by ours, so it must be re-established): continue uniting old - 1 with b.  Every iteration therefore either
+// ends or strictly lowers one of the two positive integers (a, b): it terminates.  Cells that other workgroups may change in the same launch are read through
+// SEGX_TEAM_LOAD (agent scope: not out of this CU's L1); nothing here waits for another workgroup.
+#include "common.h"
+
+namespace segx {
+
+constexpr int CCL_TH = SEGX_CCL_TILE_H, CCL_TW = SEGX_CCL_TILE_W;      // 32 x 64: label rows of 256 bytes
+constexpr int CCL_PW = CCL_TW + 2, CCL_PN = (CCL_TH + 2) * CCL_PW;      // the LDS tile carries a one-pixel unset rim: no neighbour test at its edges
+constexpr int CCL_PER = CCL_TH * CCL_TW / 256;                          // pixels a thread owns: rows 4k + wave, column lane
+static_assert(CCL_TW == 64 && CCL_TH % 4 == 0, "a wave owns a tile row");
+
+__global__ __launch_bounds__(256) void ccl_tile_kernel(const uint8_t* __restrict__ fg, int bg, int* __restrict__ labels, int* __restrict__ sizes, int H, int W,
+                                                       int tiles_x, int tiles_y) {
+    __shared__ int lab[CCL_PN], cnt[CCL_PN];
+    __shared__ int changed[2];
+    const int tid = threadIdx.x, lx = tid & 63, lw = tid >> 6;
+    const int64_t blk = blockIdx.x, per_plane = (int64_t)tiles_x * tiles_y;
+    const int64_t plane = blk / per_plane;
+    const int t = (int)(blk - plane * per_plane), x0 = (t % tiles_x) * CCL_TW, y0 = (t / tiles_x) * CCL_TH;
+    const int64_t base = plane * H * W;
+    const int gx = x0 + lx;
+    for (int i = tid; i < CCL_PN; i += 256) { lab[i] = -1; cnt[i] = 0; }
+    if (tid < 2) changed[tid] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < CCL_PER; ++k) {
+        const int ly = 4 * k + lw, gy = y0 + ly, c = (ly + 1) * CCL_PW + lx + 1;
+        if (gx < W && gy < H && fg[base + (int64_t)gy * W + gx] != bg) lab[c] = c;
+    }
+    __syncthreads();
+    // label equivalence: (scan) a pixel whose neighbourhood holds a smaller label lowers the label cell of ITS root; (analysis) every pixel follows the cells down to
+    // a root.  Labels never rise, an iteration without a change is the fixed point: all pixels of a component carry its smallest (= first, raster order) cell.
+    for (int it = 0;; ++it) {
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < CCL_PER; ++k) {
+            const int c = (4 * k + lw + 1) * CCL_PW + lx + 1, r = lab[c];
+            if (r < 0) continue;
+            int m = r;
+#pragma unroll
+            for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+                for (int dx = -1; dx <= 1; ++dx) {
+                    const int v = lab[c + dy * CCL_PW + dx];
+                    if (v >= 0 && v < m) m = v;
+                }
+            if (m < r) { atomicMin(&lab[r], m); any = true; }
+        }
+        if (any) changed[it & 1] = 1;
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < CCL_PER; ++k) {
+            const int c = (4 * k + lw + 1) * CCL_PW + lx + 1;
+            int r = lab[c];
+            if (r < 0) continue;
+            for (int v = lab[r]; v < r; v = lab[r]) r = v;       // cells hold values <= their own index: strictly down to a root
+            lab[c] = r;
+        }
+        if (tid == 0) changed[(it + 1) & 1] = 0;                  // the other flag: nobody reads or sets it before the next barrier
+        const int again = changed[it & 1];
+        __syncthreads();
+        if (!again) break;
+    }
+#pragma unroll
+    for (int k = 0; k < CCL_PER; ++k) {
+        const int r = lab[(4 * k + lw + 1) * CCL_PW + lx + 1];
+        if (r >= 0) atomicAdd(&cnt[r], 1);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < CCL_PER; ++k) {
+        const int ly = 4 * k + lw, gy = y0 + ly, c = (ly + 1) * CCL_PW + lx + 1;
+        if (gx >= W || gy >= H) continue;
+        const int r = lab[c];
+        const int64_t g = base + (int64_t)gy * W + gx;
+        labels[g] = r < 0 ? 0 : 1 + (y0 + r / CCL_PW - 1) * W + x0 + r % CCL_PW - 1;
+        sizes[g] = r == c ? cnt[c] : 0;
+    }
+}
+
+// the root below cell x of the plane L (x is set).  Values are 1 + an index <= the cell's own; anything else ends the walk, so it stays inside the plane whatever it reads.
+__device__ __forceinline__ int ccl_find(const int* L, int x) {
+    for (;;) {
+        const int v = SEGX_TEAM_LOAD(L + x) - 1;
+        if ((unsigned)v >= (unsigned)x) return x;
+        x = v;
+    }
+}
+
+// unite the sets of the set cells a and b (the argument for correctness and termination: head of this file)
+__device__ __forceinline__ void ccl_union(int* L, int a, int b) {
+    for (;;) {
+        a = ccl_find(L, a); b = ccl_find(L, b);
+        if (a == b) return;
+        if (a < b) { const int s = a; a = b; b = s; }
+        const int old = atomicMin(L + a, b + 1);
+        if (old == a + 1 || old <= 0 || old > a) return;          // linked a root; (the other two: not a label of this plane -- never written by these kernels)
+        a = old - 1;
+    }
+}
+
+__device__ __forceinline__ bool ccl_set(const int* L, int i) { return SEGX_TEAM_LOAD(L + i) != 0; }
+
+// One thread per seam pixel: the last column of every tile column but the last (all rows), then the last row of every tile row but the last (all columns).  A pixel whose
+// straight neighbour across the seam is set unites with it alone: the diagonal ones touch that neighbour inside their tile or across a seam another thread handles.
+__global__ __launch_bounds__(256) void ccl_seam_kernel(int* __restrict__ labels, int64_t planes, int H, int W) {
+    const int nvs = (W - 1) / CCL_TW, nhs = (H - 1) / CCL_TH;
+    const int64_t nv = (int64_t)nvs * H, per = nv + (int64_t)nhs * W, total = planes * per, HW = (int64_t)H * W;
+    for (int64_t it = (int64_t)blockIdx.x * 256 + threadIdx.x; it < total; it += (int64_t)gridDim.x * 256) {
+        const int64_t plane = it / per;
+        int64_t r = it - plane * per;
+        int* L = labels + plane * HW;
+        if (r < nv) {
+            const int k = (int)(r / H), y = (int)(r - (int64_t)k * H), a = y * W + (k + 1) * CCL_TW - 1;
+            if (!ccl_set(L, a)) continue;
+            if (ccl_set(L, a + 1)) ccl_union(L, a, a + 1);
+            else {
+                if (y > 0 && ccl_set(L, a + 1 - W)) ccl_union(L, a, a + 1 - W);
+                if (y + 1 < H && ccl_set(L, a + 1 + W)) ccl_union(L, a, a + 1 + W);
+            }
+        } else {
+            r -= nv;
+            const int k = (int)(r / W), x = (int)(r - (int64_t)k * W), a = ((k + 1) * CCL_TH - 1) * W + x;
+            if (!ccl_set(L, a)) continue;
+            if (ccl_set(L, a + W)) ccl_union(L, a, a + W);
+            else {
+                if (x > 0 && ccl_set(L, a + W - 1)) ccl_union(L, a, a + W - 1);
+                if (x + 1 < W && ccl_set(L, a + W + 1)) ccl_union(L, a, a + W + 1);
+            }
+        }
+    }
+}
+
+// The union is complete (launch boundary): roots no longer change.  A store here may race with another thread's walk through the same cell; it too writes 1 + a member
+// of the set that is not later, so the walk still ends on the root.  A count moves from a tile-local root that is not the final one; final roots are only added to.
+__global__ __launch_bounds__(256) void ccl_flatten_kernel(int* __restrict__ labels, int* __restrict__ sizes, int64_t planes, int HW) {
+    const int64_t total = planes * HW;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        const int64_t plane = idx / HW;
+        const int i = (int)(idx - plane * HW);
+        int* L = labels + plane * HW;
+        if (!ccl_set(L, i)) continue;
+        const int root = ccl_find(L, i);
+        if (root == i) continue;
+        L[i] = root + 1;
+        const int s = sizes[idx];
+        if (s) { atomicAdd(sizes + plane * HW + root, s); sizes[idx] = 0; }
+    }
+}
+
+// ---- which labels stay ---------------------------------------------------------------------------------------------------------------------------------------
+struct Top2 { int c1, l1, c2, l2; };                         // the best and the second candidate (count, label); count -1 = none
+__device__ __forceinline__ bool frag_better(int ca, int la, int cb, int lb) { return ca > cb || (ca == cb && la < lb); }     // ties: the lower label (background = 0) first
+__device__ __forceinline__ void frag_insert(Top2& t, int c, int l) {
+    if (frag_better(c, l, t.c1, t.l1)) { t.c2 = t.c1; t.l2 = t.l1; t.c1 = c; t.l1 = l; }
+    else if (frag_better(c, l, t.c2, t.l2)) { t.c2 = c; t.l2 = l; }
+}
+
+constexpr int KEEP_THREADS = 1024;
+// One workgroup per plane: a thread folds its strided share of sizes[plane] into (sum, top two), then a fixed-order tree over LDS.  (count, label) is a total order,
+// so the result does not depend on the order anyway.
+__global__ __launch_bounds__(KEEP_THREADS) void frag_keep2_kernel(const int* __restrict__ sizes, int* __restrict__ keep, int HW) {
+    __shared__ int sc1[KEEP_THREADS], sl1[KEEP_THREADS], sc2[KEEP_THREADS], sl2[KEEP_THREADS], ssum[KEEP_THREADS];
+    const int tid = threadIdx.x;
+    const int* s = sizes + (int64_t)blockIdx.x * HW;
+    Top2 t{-1, 0x7fffffff, -1, 0x7fffffff};
+    int sum = 0;
+    int i = tid;
+    for (; i + 3 * KEEP_THREADS < HW; i += 4 * KEEP_THREADS) {                      // four loads in flight per thread
+        const int v0 = s[i], v1 = s[i + KEEP_THREADS], v2 = s[i + 2 * KEEP_THREADS], v3 = s[i + 3 * KEEP_THREADS];
+        if (v0 | v1 | v2 | v3) {
+            if (v0) { sum += v0; frag_insert(t, v0, i + 1); }
+            if (v1) { sum += v1; frag_insert(t, v1, i + KEEP_THREADS + 1); }
+            if (v2) { sum += v2; frag_insert(t, v2, i + 2 * KEEP_THREADS + 1); }
+            if (v3) { sum += v3; frag_insert(t, v3, i + 3 * KEEP_THREADS + 1); }
+        }
+    }
+    for (; i < HW; i += KEEP_THREADS) {
+        const int v = s[i];
+        if (v) { sum += v; frag_insert(t, v, i + 1); }
+    }
+    sc1[tid] = t.c1; sl1[tid] = t.l1; sc2[tid] = t.c2; sl2[tid] = t.l2; ssum[tid] = sum;
+    __syncthreads();
+    for (int h = KEEP_THREADS / 2; h > 0; h >>= 1) {
+        if (tid < h) {
+            frag_insert(t, sc1[tid + h], sl1[tid + h]); frag_insert(t, sc2[tid + h], sl2[tid + h]);
+            sum += ssum[tid + h];
+            sc1[tid] = t.c1; sl1[tid] = t.l1; sc2[tid] = t.c2; sl2[tid] = t.l2; ssum[tid] = sum;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        if (HW - sum > 0) frag_insert(t, HW - sum, 0);
+        keep[2 * (int64_t)blockIdx.x] = t.c1 < 0 ? -1 : t.l1;
+        keep[2 * (int64_t)blockIdx.x + 1] = t.c2 < 0 ? -1 : t.l2;
+    }
+}
+
+__global__ __launch_bounds__(256) void frag_apply_kernel(const uint8_t* __restrict__ seg, const int* __restrict__ labels, const int* __restrict__ keep,
+                                                         uint8_t* __restrict__ out, int64_t planes, int HW, int bg) {
+    const int64_t total = planes * HW;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        const int64_t plane = idx / HW;
+        const int l = labels[idx];
+        out[idx] = (l == 0 || l == keep[2 * plane] || l == keep[2 * plane + 1]) ? seg[idx] : (uint8_t)bg;
+    }
+}
+
+// ---- row extents ---------------------------------------------------------------------------------------------------------------------------------------------
+constexpr int EXT_ROWS = 32;                 // rows of one plane a workgroup covers: a wave takes every fourth
+__global__ __launch_bounds__(256) void row_extent_init_kernel(int* __restrict__ ext, int64_t planes, int H) {
+    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < planes; p += (int64_t)gridDim.x * 256) { ext[2 * p] = H; ext[2 * p + 1] = -1; }
+}
+
+__global__ __launch_bounds__(256) void row_extent_kernel(const float* __restrict__ mask, int* __restrict__ ext, int64_t planes, int H, int W, float thres) {
+    __shared__ int lo_s, hi_s;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t groups = (H + EXT_ROWS - 1) / EXT_ROWS, items = planes * groups;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t plane = item / groups;
+        const int y0 = (int)(item - plane * groups) * EXT_ROWS, y1 = min(y0 + EXT_ROWS, H);
+        if (threadIdx.x == 0) { lo_s = H; hi_s = -1; }
+        __syncthreads();
+        int lo = H, hi = -1;
+        for (int y = y0 + wave; y < y1; y += 4) {                                  // wave-uniform bounds: every lane takes part in the shuffles
+            const float* row = mask + (plane * H + y) * W;
+            int any = 0;
+            for (int x = lane; x < W; x += 64) any |= row[x] >= thres ? 1 : 0;
+            for (int m = 32; m > 0; m >>= 1) any |= __shfl_xor(any, m);
+            if (any) { lo = min(lo, y); hi = max(hi, y); }
+        }
+        if (lane == 0 && hi >= 0) { atomicMin(&lo_s, lo); atomicMax(&hi_s, hi); }
+        __syncthreads();
+        if (threadIdx.x == 0 && hi_s >= 0) { atomicMin(ext + 2 * plane, lo_s); atomicMax(ext + 2 * plane + 1, hi_s); }
+        __syncthreads();
+    }
+}
+
+// ---- n-hot -> pixel values -----------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void nhot_to_values_kernel(const float* __restrict__ nhot, const int* __restrict__ values, uint8_t* __restrict__ out, int64_t B,
+                                                             int C, int64_t S) {
+    const int64_t total = B * S;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        const int64_t b = idx / S, s = idx - b * S;
+        const float* src = nhot + b * C * S + s;
+        int v = 0;
+        for (int c = 0; c < C; ++c)
+            if (src[c * S] == 1.0f) v = values[c];                                 // ascending: a later class wins, as the reference's assignment order
+        out[idx] = (uint8_t)v;
+    }
+}
+
+}  // namespace segx
+
+using namespace segx;
+#define SEGX_STREAM hipStream_t stream = (hipStream_t)stream_
+
+static inline unsigned grid_for(int64_t work) { return (unsigned)i64max(1, i64min(1 << 20, (work + 255) / 256)); }
+
+extern "C" int segx_ccl2d(const uint8_t* fg, int bg_value, int32_t* labels, int32_t* sizes, int64_t planes, int H, int W, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(fg && labels && sizes, "segx_ccl2d: null pointer");
+    SEGX_REQUIRE(planes > 0 && H > 0 && W > 0, "segx_ccl2d: planes, H and W must be positive");
+    SEGX_REQUIRE((int64_t)H * W < SEGX_CCL_MAX_PLANE, "segx_ccl2d: H * W = %lld is not below the limit of 2^30 pixels per plane", (long long)H * W);
+    SEGX_REQUIRE(bg_value >= 0 && bg_value <= 255, "segx_ccl2d: bg_value %d is no uint8 value", bg_value);
+    const int tiles_x = (W + CCL_TW - 1) / CCL_TW, tiles_y = (H + CCL_TH - 1) / CCL_TH;
+    const int64_t tiles = planes * tiles_x * tiles_y;
+    SEGX_REQUIRE(tiles < ((int64_t)1 << 24), "segx_ccl2d: %lld tiles exceed one grid (2^24 workgroups of 256 threads)", (long long)tiles);
+    hipLaunchKernelGGL(ccl_tile_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, fg, bg_value, labels, sizes, H, W, tiles_x, tiles_y);
+    const int64_t seam = planes * ((int64_t)((W - 1) / CCL_TW) * H + (int64_t)((H - 1) / CCL_TH) * W);
+    if (seam > 0) {
+        hipLaunchKernelGGL(ccl_seam_kernel, dim3(grid_for(seam)), dim3(256), 0, stream, labels, planes, H, W);
+        hipLaunchKernelGGL(ccl_flatten_kernel, dim3(grid_for(planes * H * W)), dim3(256), 0, stream, labels, sizes, planes, H * W);
+    }
+    return check_launch("segx_ccl2d");
+}
+
+extern "C" int segx_frag_keep2(const int32_t* sizes, int32_t* keep, int64_t planes, int H, int W, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(sizes && keep, "segx_frag_keep2: null pointer");
+    SEGX_REQUIRE(planes > 0 && H > 0 && W > 0, "segx_frag_keep2: planes, H and W must be positive");
+    SEGX_REQUIRE(planes < ((int64_t)1 << 22), "segx_frag_keep2: %lld planes exceed one grid (2^22 workgroups of 1024 threads)", (long long)planes);
+    SEGX_REQUIRE((int64_t)H * W < SEGX_CCL_MAX_PLANE, "segx_frag_keep2: H * W = %lld is not below the limit of 2^30 pixels per plane", (long long)H * W);
+    hipLaunchKernelGGL(frag_keep2_kernel, dim3((unsigned)planes), dim3(KEEP_THREADS), 0, stream, sizes, keep, H * W);
+    return check_launch("segx_frag_keep2");
+}
+
+extern "C" int segx_frag_apply(const uint8_t* seg, const int32_t* labels, const int32_t* keep, uint8_t* out, int64_t planes, int H, int W, int bg_value,
+                               void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(seg && labels && keep && out, "segx_frag_apply: null pointer");
+    SEGX_REQUIRE(planes > 0 && H > 0 && W > 0, "segx_frag_apply: planes, H and W must be positive");
+    SEGX_REQUIRE((int64_t)H * W < SEGX_CCL_MAX_PLANE, "segx_frag_apply: H * W = %lld is not below the limit of 2^30 pixels per plane", (long long)H * W);
+    SEGX_REQUIRE(bg_value >= 0 && bg_value <= 255, "segx_frag_apply: bg_value %d is no uint8 value", bg_value);
+    hipLaunchKernelGGL(frag_apply_kernel, dim3(grid_for(planes * H * W)), dim3(256), 0, stream, seg, labels, keep, out, planes, H * W, bg_value);
+    return check_launch("segx_frag_apply");
+}
+
+extern "C" int segx_row_extent(const float* mask, int32_t* ext, int64_t planes, int H, int W, float thres, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(mask && ext, "segx_row_extent: null pointer");
+    SEGX_REQUIRE(planes > 0 && H > 0 && W > 0, "segx_row_extent: planes, H and W must be positive");
+    SEGX_REQUIRE((int64_t)H * W < SEGX_CCL_MAX_PLANE, "segx_row_extent: H * W = %lld is not below the limit of 2^30 pixels per plane", (long long)H * W);
+    hipLaunchKernelGGL(row_extent_init_kernel, dim3(grid_for(planes)), dim3(256), 0, stream, ext, planes, H);
+    const int64_t items = planes * ((H + EXT_ROWS - 1) / EXT_ROWS);
+    hipLaunchKernelGGL(row_extent_kernel, dim3((unsigned)i64min(1 << 20, items)), dim3(256), 0, stream, mask, ext, planes, H, W, thres);
+    return check_launch("segx_row_extent");
+}
+
+extern "C" int segx_nhot_to_values(const float* nhot, const int32_t* values, uint8_t* out, int64_t B, int C, int64_t S, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(nhot && values && out, "segx_nhot_to_values: null pointer");
+    SEGX_REQUIRE(B > 0 && C > 0 && S > 0, "segx_nhot_to_values: B, C and S must be positive");
+    hipLaunchKernelGGL(nhot_to_values_kernel, dim3(grid_for(B * S)), dim3(256), 0, stream, nhot, values, out, B, C, S);
+    return check_launch("segx_nhot_to_values");
+}

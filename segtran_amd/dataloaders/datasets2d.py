@@ -1,5 +1,5 @@
-"""On-device label maps of the 2D train step (mirror of reference code/dataloaders/datasets2d.py:90-139, 200-223).
-Only the in-step label -> n-hot maps are on the hot path; file I/O and imgaug pipelines are out of scope."""
+"""On-device label maps of the 2D train step and of the evaluation's export (mirror of reference code/dataloaders/datasets2d.py:90-171, 200-250).
+Only the in-step label -> n-hot maps and the n-hot -> pixel-value maps are built; file I/O and imgaug pipelines are out of scope."""
 import torch
 
 
@@ -31,3 +31,24 @@ def harden_segmap2d(mask_soft, T=0.5):
     _, hard = SF.harden_segmap(x.float().contiguous(), None, mode=0, T=T, want_soft=False)
     hard = hard.to(torch.int32)
     return hard if batched else hard[0]
+
+
+def _inv_map(what, mask_nhot, values):
+    from .. import functional as SF
+    if mask_nhot.dim() not in (3, 4) or mask_nhot.shape[-3] < len(values):
+        raise ValueError('%s: n-hot maps [C, H, W] or [B, C, H, W] with C >= %d, not %s' % (what, len(values), tuple(mask_nhot.shape)))
+    batched = mask_nhot.dim() == 4
+    x = mask_nhot if batched else mask_nhot.unsqueeze(0)
+    out = SF.nhot_to_values(x[:, :len(values)], values)
+    return out if batched else out[0]
+
+
+def fundus_inv_map_mask(mask_nhot):
+    """reference datasets2d.py:144-171: n-hot (bg, disc, cup) [C, H, W] or [B, C, H, W] -> the REFUGE annotation format, uint8: 255 background, 128 optic disc,
+    0 optic cup; assigned in that order, so a pixel with several classes on takes the last one's value, and one with none stays 0 (segx_nhot_to_values)."""
+    return _inv_map('fundus_inv_map_mask', mask_nhot, (255, 128, 0))
+
+
+def polyp_inv_map_mask(mask_nhot):
+    """reference datasets2d.py:225-250: n-hot (bg, polyp) [C, H, W] or [B, C, H, W] -> uint8 0 background / 255 polyp (segx_nhot_to_values)."""
+    return _inv_map('polyp_inv_map_mask', mask_nhot, (0, 255))

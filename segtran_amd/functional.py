@@ -2361,3 +2361,92 @@ def surface_hist(border_from, d2_to):
     hist = torch.zeros(P, nbins, dtype=torch.int32, device=b.device)
     segx.lib().surface_hist(b, d, hist, P, D, H, W, nbins)
     return hist
+
+
+# -------------------------------------------------------------------------------------------------
+# Tail of the 2-D evaluation (components.hip): connected components, fragment removal, row extents, n-hot -> pixel values.  Stacks of planes [P, H, W] (or one
+# [H, W] plane); integer kernels with exact results; no copy to the host and no synchronisation, so the calls can be captured into a graph.  Forward only.
+# -------------------------------------------------------------------------------------------------
+def _planes_operand(what, t, dtypes):
+    if torch.is_grad_enabled() and t.requires_grad:
+        raise RuntimeError(what + ' is forward-only: call it under torch.no_grad() or on tensors without gradient')
+    if t.dim() not in (2, 3):
+        raise ValueError('%s: an [H, W] or [P, H, W] tensor, not rank %d' % (what, t.dim()))
+    if t.dtype not in dtypes:
+        raise TypeError('%s: a %s tensor, not %s' % (what, ' / '.join(str(d) for d in dtypes), t.dtype))
+    P, H, W = (1,) * (3 - t.dim()) + tuple(t.shape)
+    if P < 1 or H < 1 or W < 1:
+        raise ValueError('%s: empty tensor %s' % (what, tuple(t.shape)))
+    if H * W >= segx.SegxLib.CCL_MAX_PLANE:
+        raise ValueError('%s: H * W = %d is not below the limit of 2^30 pixels per plane' % (what, H * W))
+    t = _c(t.detach())
+    return (t.view(torch.uint8) if t.dtype == torch.bool else t), P, H, W
+
+
+def _uint8_value(what, v):
+    if int(v) != v or not 0 <= int(v) <= 255:
+        raise ValueError('%s: %r is no uint8 value' % (what, v))
+    return int(v)
+
+
+def label_components(mask, bg_value=0):
+    """8-connected components (cv2.connectedComponents' default connectivity) of every plane of a uint8 / bool mask [P, H, W] or [H, W]; a pixel is background
+    iff it equals bg_value.  Returns (labels, sizes), int32 of the mask's shape: labels = 0 on the background, else 1 + the raster index inside the plane of the
+    component's first pixel; sizes = the component's pixel count at that first pixel, 0 everywhere else."""
+    m, P, H, W = _planes_operand('label_components', mask, (torch.uint8, torch.bool))
+    labels = torch.empty(m.shape, dtype=torch.int32, device=m.device)
+    sizes = torch.empty(m.shape, dtype=torch.int32, device=m.device)
+    segx.lib().ccl2d(m, _uint8_value('label_components: bg_value', bg_value), labels, sizes, P, H, W)
+    return labels, sizes
+
+
+def remove_fragments(seg_u8, bg_value):
+    """Per plane of the uint8 label image(s) [P, H, W] / [H, W]: label the 8-connected components of seg != bg_value, keep the two most frequent of {background,
+    components} (ties: the background, then the component that starts first) and paint the rest bg_value.  Returns a new tensor; three kernels' worth of launches
+    (segx_ccl2d, segx_frag_keep2, segx_frag_apply), nothing on the host."""
+    s, P, H, W = _planes_operand('remove_fragments', seg_u8, (torch.uint8,))
+    bg = _uint8_value('remove_fragments: bg_value', bg_value)
+    L = segx.lib()
+    labels = torch.empty(s.shape, dtype=torch.int32, device=s.device)
+    sizes = torch.empty(s.shape, dtype=torch.int32, device=s.device)
+    keep = torch.empty(P, 2, dtype=torch.int32, device=s.device)
+    out = torch.empty_like(s)
+    L.ccl2d(s, bg, labels, sizes, P, H, W)
+    L.frag_keep2(sizes, keep, P, H, W)
+    L.frag_apply(s, labels, keep, out, P, H, W, bg)
+    return out
+
+
+def row_extent(mask, thres):
+    """int32 [P, 2] (or [2] for one [H, W] plane): the lowest and the highest row index of each plane of the float mask that holds a value >= thres; (H, -1) where
+    none does."""
+    m, P, H, W = _planes_operand('row_extent', mask, (torch.float32,))
+    ext = torch.empty(P, 2, dtype=torch.int32, device=m.device)
+    segx.lib().row_extent(m, ext, P, H, W, thres)
+    return ext if mask.dim() == 3 else ext[0]
+
+
+_VALUE_TABLES = {}
+
+
+def nhot_to_values(nhot, values):
+    """uint8 [B, *spatial] from n-hot floats [B, C, *spatial]: 0, then for c ascending values[c] where nhot[:, c] == 1 -- a later class wins, as in the reference's
+    inverse maps.  values: C ints in 0..255 (their device table is built once per device and kept: no host copy on later calls)."""
+    if torch.is_grad_enabled() and nhot.requires_grad:
+        raise RuntimeError('nhot_to_values is forward-only: call it under torch.no_grad() or on tensors without gradient')
+    if nhot.dim() < 3:
+        raise ValueError('nhot_to_values: [B, C, *spatial] floats, not rank %d' % nhot.dim())
+    values = tuple(_uint8_value('nhot_to_values: values', v) for v in values)
+    B, C = nhot.shape[:2]
+    if len(values) != C:
+        raise ValueError('nhot_to_values: %d values for %d classes' % (len(values), C))
+    x = _c(nhot.detach().float())
+    out = torch.empty((B,) + tuple(x.shape[2:]), dtype=torch.uint8, device=x.device)
+    if out.numel() == 0:
+        raise ValueError('nhot_to_values: empty tensor %s' % (tuple(nhot.shape),))
+    key = (values, x.device)
+    table = _VALUE_TABLES.get(key)
+    if table is None:
+        table = _VALUE_TABLES[key] = torch.tensor(values, dtype=torch.int32, device=x.device)
+    segx.lib().nhot_to_values(x, table, out, B, C, out.numel() // B)
+    return out

@@ -1,7 +1,8 @@
 """2-D evaluation with BatchNorm folded into the backbone's kernels: test_util2d's sliding-window inference with a `fold_bn` switch, a `fused` form
 (one gather launch, the network on stacked windows, one merge launch) and that form captured as one replayable hipGraph (GraphedSlidingWindow).
 
-test_util2d.py mirrors the reference's file of that name and keeps the reference's signatures; the switch lives here.  fold_bn=True folds the (eval-mode) net for
+test_util2d.py mirrors the reference's file of that name and keeps the reference's signatures; the switch lives here.  So does the tail of the evaluation after
+preds_soft: calc_vcdr, calc_batch_metric with the vCDR-error column, remove_fragmentary_segs, export_masks.  fold_bn=True folds the (eval-mode) net for
 the call if it is not folded already (Segtran2d.fold_batchnorm) and unfolds it afterwards; a net the caller folded stays folded."""
 import contextlib
 import math
@@ -10,7 +11,8 @@ import torch
 
 from . import functional as SF
 from . import test_util2d as _T2
-from .test_util2d import calc_dice, calc_batch_metric          # noqa: F401  (same module surface)
+from .test_util2d import calc_dice          # noqa: F401  (same module surface)
+from .dataloaders.datasets2d import harden_segmap2d
 
 
 @contextlib.contextmanager
@@ -133,19 +135,98 @@ def test_single_batch(net, image_batch, orig_input_size, patch_size, stride, tas
             return plan.run(net, image_batch)
 
 
+def calc_vcdr(mask_nhot_soft, thres=0.5, delta=1):
+    """reference utils/losses.py:76-127, the vertical cup/disc ratio of n-hot maps (0 background, 1 disc, 2 cup), soft or hard: the vertical extent of the
+    thresholded cup over that of the disc.  The extents come from SF.row_extent; the few scalar operations keep the reference's dtypes (int64 lengths, float32
+    quotient), so the values are the reference's bit for bit.  No branch on device data, no copy to the host: the call can be captured into a graph.
+
+    [C, H, W] (one image): (max_idx - min_idx - delta) of the cup over that of the disc + 0.0001; -1. without a disc, 0. without a cup; a 0-dim float32 tensor.
+    [B, C, H, W]: the reference's batch form as it is -- no delta, and the minimum runs over occupied * index, so it is 0 whenever any row is unoccupied
+    (the length is then the highest occupied row + 1); a float32 [B] tensor."""
+    m = mask_nhot_soft.detach().float()
+    if m.dim() == 4:
+        B, _, H, W = m.shape
+        vert_indices = torch.arange(1, H + 1, device=m.device).repeat(B, 1)
+
+        def vert_len(c):                                     # a row is a plane of height 1: its extent is (0, 0) when occupied, (1, -1) when not
+            occupied = SF.row_extent(m[:, c].reshape(B * H, 1, W), thres)[:, 1].view(B, H) == 0
+            indexed = occupied * vert_indices
+            return indexed.max(dim=1)[0] - indexed.min(dim=1)[0]
+        return vert_len(2) / (vert_len(1) + 0.0001)
+    if m.dim() != 3:
+        raise ValueError('calc_vcdr: [C, H, W] or [B, C, H, W] n-hot maps, not rank %d' % m.dim())
+    ext = SF.row_extent(m[1:3], thres).long()               # [2, 2]: (lowest, highest) row of disc and cup; (H, -1) where empty
+    length = ext[:, 1] - ext[:, 0] - delta
+    vcdr = length[1] / (length[0] + 0.0001)
+    vcdr = torch.where(ext[1, 1] < 0, 0., vcdr)              # no cup
+    return torch.where(ext[0, 1] < 0, -1., vcdr)            # no disc (tested first in the reference)
+
+
+def calc_batch_metric(BC_pred_soft, BC_gt, num_classes, do_calc_vcdr_error=False):
+    """reference test_util2d.py:241-265.  The default is test_util2d.calc_batch_metric, unchanged (that function still refuses the flag); with do_calc_vcdr_error
+    the table has one more column, |calc_vcdr(gt) - calc_vcdr(pred)| (:259-263, the fundus task's own metric): that function's loop -- resample, harden, Dice,
+    the same calls, so the Dice columns are the default's bit for bit -- with the column computed from the same hardened maps."""
+    if not do_calc_vcdr_error:
+        return _T2.calc_batch_metric(BC_pred_soft, BC_gt, num_classes)
+    out = _T2.np.zeros((len(BC_pred_soft), num_classes))
+    for ins, (C_pred_soft, C_gt) in enumerate(zip(BC_pred_soft, BC_gt)):
+        if tuple(C_pred_soft.shape[1:]) != tuple(C_gt.shape[1:]):
+            C_pred_soft = SF.interp_linear(C_pred_soft.unsqueeze(0).contiguous(), tuple(C_gt.shape[1:]))[0]
+        C_pred = harden_segmap2d(C_pred_soft)
+        d = SF.dice_scores(C_pred[1:].float().reshape(num_classes - 1, -1), C_gt[1:].float().reshape(num_classes - 1, -1))
+        out[ins, :num_classes - 1] = d.cpu().numpy()
+        out[ins, num_classes - 1] = _T2.np.abs((calc_vcdr(C_gt) - calc_vcdr(C_pred)).cpu().numpy())
+    return out
+
+
+def remove_fragmentary_segs(segmap, bg_value):
+    """reference test_util2d.py:267-289 on the device: segmap is a uint8 label image [H, W] or a stack [P, H, W] (each plane on its own) on the device.  The
+    8-connected components of segmap != bg_value are labelled, the two most frequent of {background, components} stay, every other component is painted bg_value.
+    Returns a NEW tensor of the same shape, dtype and device; the input is not modified (the reference writes into its host copy).
+
+    It gives the reference's result wherever the reference is defined: at least one background pixel, at least one foreground component, and no tie at the
+    cut (the second and third largest counts differ).  Outside that domain the reference drops into pdb (fewer than two labels) or depends on argpartition's
+    unspecified order among equals; here ties go to the background first, then to the component whose first pixel comes first in raster order, and a plane that
+    is all background or all foreground comes back unchanged."""
+    if not isinstance(segmap, torch.Tensor) or segmap.dtype != torch.uint8:
+        raise TypeError('remove_fragmentary_segs: a uint8 device tensor, not %s' % (segmap.dtype if isinstance(segmap, torch.Tensor) else type(segmap).__name__))
+    return SF.remove_fragments(segmap, bg_value)
+
+
 def test_all_cases(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, mask_prepred_mapping_func=None, fold_bn=False, fused=False,
-                   window_batch=None, precision='fp32'):
-    """test_util2d.test_all_cases; fold_bn: ONE fold for all the batches; fused / window_batch / precision: as test_single_batch."""
+                   window_batch=None, precision='fp32', do_calc_vcdr_error=False):
+    """test_util2d.test_all_cases; fold_bn: ONE fold for all the batches; fused / window_batch / precision: as test_single_batch; do_calc_vcdr_error: the vCDR
+    error as one more entry (both returned vectors then have num_classes entries, as in the reference)."""
     with _precision(precision), _folded(net, fold_bn):
-        if not fused:
+        if not fused and not do_calc_vcdr_error:
             return _T2.test_all_cases(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, mask_prepred_mapping_func)
-        total, count = _T2.np.zeros(num_classes - 1), 0
+        np = _T2.np
+        total, count = (np.zeros(num_classes), np.zeros(num_classes)) if do_calc_vcdr_error else (np.zeros(num_classes - 1), 0)
         for image_batch, mask_batch in batches:
             gt = mask_prepred_mapping_func(mask_batch) if mask_prepred_mapping_func else mask_batch
-            _, preds_soft = test_single_batch(net, image_batch, orig_input_size, patch_size, stride, task_name, num_classes, fused=True, window_batch=window_batch)
-            m = calc_batch_metric(preds_soft, gt, num_classes)
+            _, preds_soft = test_single_batch(net, image_batch, orig_input_size, patch_size, stride, task_name, num_classes, fused=fused, window_batch=window_batch)
+            m = calc_batch_metric(preds_soft, gt, num_classes, do_calc_vcdr_error=do_calc_vcdr_error)
             total += m.sum(axis=0); count += len(m)
-        return total / max(count, 1), count
+        return total / np.maximum(count, 1), count
+
+
+def export_masks(preds_soft, unscaled_sizes, inv_map, remove_frag=False, bg_value=255):
+    """The arithmetic of the reference's save loop (test_util2d.py:93-106, and test2d.py's --removefrag) without the files: per image i, preds_soft[i] [C, H, W] is
+    resampled to unscaled_sizes[i] = (H0, W0) (interp_linear), hardened (harden_segmap2d), mapped to pixel values by inv_map (fundus_inv_map_mask /
+    polyp_inv_map_mask of dataloaders.datasets2d) and, with remove_frag, cleaned by remove_fragmentary_segs(., bg_value).  Returns the list of uint8 [H0, W0]
+    device tensors; writing them in an image format is the caller's."""
+    if len(unscaled_sizes) != len(preds_soft):
+        raise ValueError('export_masks: %d sizes for %d predictions' % (len(unscaled_sizes), len(preds_soft)))
+    out = []
+    with torch.no_grad():
+        for soft, size in zip(preds_soft, unscaled_sizes):
+            H0, W0 = (int(v) for v in size)
+            soft = soft.unsqueeze(0).contiguous()
+            if (H0, W0) != tuple(soft.shape[2:]):
+                soft = SF.interp_linear(soft, (H0, W0))
+            mask = inv_map(harden_segmap2d(soft[0]))
+            out.append(remove_fragmentary_segs(mask, bg_value) if remove_frag else mask)
+    return out
 
 
 class GraphedSlidingWindow:

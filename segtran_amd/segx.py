@@ -609,6 +609,24 @@ class SegxLib:
     def surface_hist(self, border_from, d2_to, hist, planes, D, H, W, nbins):
         self._call('segx_surface_hist', hist, border_from, d2_to, hist, planes, D, H, W, nbins)
 
+    # ---- components, fragment removal, row extents, n-hot -> values (components.hip) --------------------
+    CCL_TILE, CCL_MAX_PLANE = (32, 64), 1 << 30          # SEGX_CCL_TILE_H / _W, SEGX_CCL_MAX_PLANE of include/segx.h
+
+    def ccl2d(self, fg, bg_value, labels, sizes, planes, H, W):
+        self._call('segx_ccl2d', labels, fg, int(bg_value), labels, sizes, planes, H, W)
+
+    def frag_keep2(self, sizes, keep, planes, H, W):
+        self._call('segx_frag_keep2', keep, sizes, keep, planes, H, W)
+
+    def frag_apply(self, seg, labels, keep, out, planes, H, W, bg_value):
+        self._call('segx_frag_apply', out, seg, labels, keep, out, planes, H, W, int(bg_value))
+
+    def row_extent(self, mask, ext, planes, H, W, thres):
+        self._call('segx_row_extent', ext, mask, ext, planes, H, W, float(thres))
+
+    def nhot_to_values(self, nhot, values, out, B, C, S):
+        self._call('segx_nhot_to_values', out, nhot, values, out, B, C, S)
+
     def conv3d_splitk(self, B, Cout, geom, wgrad):
         return int(self.c.segx_conv3d_splitk(B, Cout, self._geom(geom), 1 if wgrad else 0))
 
@@ -785,6 +803,7 @@ _SIGS = {
     'segx_x6_presplit_elems': 'iiii', 'segx_x6_presplit': 'piilliillpp',
     'segx_tune': 'ii', 'segx_tune_get': 'i', 'segx_x3_launches': '', 'segx_gemm_route': 'pppp', 'segx_set_rng_base': 'p', 'segx_rng_advance': 'pup', 'segx_resized_crop3d': 'pplpp', 'segx_stem_compose_fwd': 'ppppiiiiip', 'segx_stem_compose_bwd': 'pppppppiiiiip', 'segx_bridge_input': 'ppiiiiiip', 'segx_stem_s2d_input': 'ppiiiiiip', 'segx_conv2d_stem_fwd': 'pppiiiiiiiiiiip', 'segx_conv2d_stem_im2col': 'ppiiiiiiiiiiip', 'segx_dropout': 'pplfuup', 'segx_avgpool2_fwd': 'ppliip', 'segx_avgpool2_bwd': 'ppliip', 'segx_transpose': 'ppliip', 'segx_interp_linear_fwd_axis': 'pppliilfp', 'segx_window_accum': 'pppiipp', 'segx_harden_segmap': 'ppppiilifp', 'segx_window_gather': 'ppppiiipp', 'segx_window_merge': 'pppppiiipifp', 'segx_dice_ws_floats': 'll', 'segx_dice_sums': 'pppllp',
     'segx_surface_border': 'ppliiiip', 'segx_edt_sq': 'ppliiip', 'segx_surface_hist': 'pppliiiip',
+    'segx_ccl2d': 'pippliip', 'segx_frag_keep2': 'ppliip', 'segx_frag_apply': 'ppppliiip', 'segx_row_extent': 'ppliifp', 'segx_nhot_to_values': 'ppplilp',
     'segx_conv3d_fwd': 'pppiipipp', 'segx_conv3d_fwd_packed': 'pppiipipp', 'segx_conv3d_fwd_packed_bs': 'pppiipipllp', 'segx_conv3d_bwd_weight_packed_bs': 'pppiipipllp', 'segx_conv3d_pack_weights': 'ppiiiip', 'segx_conv3d_splitk': 'iipi', 'segx_conv3d_route': 'iipiiiip', 'segx_conv3d_fwd_terms': 'iipiii', 'segx_conv3d_flip_weights': 'ppiiip', 'segx_conv3d_bwd_weight': 'pppiipipp', 'segx_conv3d_bwd_weight_packed': 'pppiipipp', 'segx_conv3d_unpack_wgrad': 'ppiiip',
     'segx_conv3d_halo_ok': 'iip', 'segx_conv3d_halo_wq_floats': 'ii', 'segx_conv3d_halo_pack': 'ppiiip', 'segx_conv3d_halo_fwd': 'pppiipllip', 'segx_conv3d_halo_wgrad_ok': 'iip', 'segx_conv3d_halo_wgrad_ws_floats': 'iip', 'segx_conv3d_halo_wgrad': 'ppppiipllp',
     'segx_conv3d_bwd_data_direct': 'ppppiipp', 'segx_nonzero_mask': 'ppiiiiiiiip', 'segx_label_nhot': 'ppiilip',
