@@ -37,7 +37,9 @@ int segx_last_error(char* buf, int buflen);
 enum { SEGX_EPI_NONE = 0, SEGX_EPI_GELU = 1 /* aux = pre-activation, C = dropout(gelu(.)), :244-245 */,
        SEGX_EPI_SWISH = 2 /* C = swish(alpha * A B^T + bias): a pointwise convolution whose BatchNorm was folded into its weights and bias (inference,
                              efficientnet/model.py:96-98, 280-282).  No aux, no dropout, no resid / gmax / split-K / batch_reduce; built for the operand layout of a
-                             pointwise convolution's forward (A k-contiguous, B row-contiguous) on the 128x128, 64x128 and 64x64 tiles of both engines */ };
+                             pointwise convolution's forward (A k-contiguous, B row-contiguous) on the 128x128, 64x128 and 64x64 tiles of both engines */,
+       SEGX_EPI_RELU = 3 /* C = max(alpha * A B^T + bias, 0): the same for the ReLU layers of Inception-I3D (aj_i3d.py:75-97 with the BatchNorm folded in) -- same
+                            refusals, operand layout and tiles as SEGX_EPI_SWISH.  C may be a channel slice of a wider NCDHW tensor: c_b0 = that tensor's sample stride */ };
 enum { SEGX_BIAS_NONE = 0, SEGX_BIAS_N = 1 /* bias[n] */, SEGX_BIAS_M = 2 /* bias[m] */ };
 /* tile engines (segx_tune knob 4): SEGX_ENGINE_F32 = v_mfma_f32_32x32x2_f32 on fp32 operands (bit-for-bit a k-ordered fmaf chain);
  * SEGX_ENGINE_BF16X6 = fp32 operands split in registers into three bf16 planes, six v_mfma_f32_32x32x16_bf16 per block (fp32-equivalent:
@@ -530,6 +532,13 @@ int segx_conv3d_unpack_wgrad(const float* dWp, float* dW, int Cout, int Cin, int
  * the slice; *_bstride = distance between samples in floats (0 = dense); pointers 16-byte aligned */
 int segx_conv3d_fwd_packed_bs(const float* X, const float* Wp, float* Y, int B, int Cout, const int* geom, int splitk, float* workspace,
                               int64_t x_bstride, int64_t y_bstride, void* stream);
+/* Y = act(conv3d(X, W) + bias[co]) -- a convolution whose BatchNorm was folded into filters and bias (inference).  act: 0 none, 2 ReLU.  packed != 0: W in
+ * the order of segx_conv3d_pack_weights; x_bstride / y_bstride as in segx_conv3d_fwd_packed_bs.  Route, split factor and counters are those of segx_conv3d_fwd*; with
+ * splitk > 1 bias and ReLU are applied by the slab reduction (bias after the slab sum).  Where the route is the plain call's, the result is max(plain + bias, 0) in fp32. */
+int segx_conv3d_fwd_bias_act(const float* X, const float* W, const float* bias, float* Y, int B, int Cout, const int* geom, int splitk, float* workspace,
+                             int packed, int64_t x_bstride, int64_t y_bstride, int act, void* stream);
+/* Y[b][i] = max(Y[b][i] + map[i], 0), i < n, in place: the folded space-to-depth stem's bias map [O, OD, OH, OW] + ReLU in one pass */
+int segx_bias_map_relu(float* Y, const float* map, int B, int64_t n, void* stream);
 int segx_conv3d_bwd_weight_packed_bs(const float* dY, const float* X, float* dWb, int B, int Cout, const int* geom, int splitk, float* workspace,
                                      int64_t dy_bstride, int64_t x_bstride, void* stream);
 /* r06 -- the 3 x 3 x 3, stride-1, 'same' convolutions (Unit3D, aj_i3d.py:75-97; every spatial convolution of the Inception modules, :198-273) with an LDS-RESIDENT
@@ -547,6 +556,9 @@ int segx_conv3d_halo_ok(int B, int Cout, const int* geom);
 int64_t segx_conv3d_halo_wq_floats(int O, int C);
 int segx_conv3d_halo_pack(const float* W, void* Wq, int O, int C, int mode, void* stream);
 int segx_conv3d_halo_fwd(const float* X, const void* Wq, float* Y, int B, int Cout, const int* geom, int64_t x_bstride, int64_t y_bstride, int mtile, void* stream);
+/* the same with bias[co] added and ReLU applied in the store loop (act = 2; fp32 add, then max, on the value the plain kernel stores): folded BatchNorm, inference */
+int segx_conv3d_halo_bias_act_fwd(const float* X, const void* Wq, const float* bias, float* Y, int B, int Cout, const int* geom, int64_t x_bstride, int64_t y_bstride,
+                                  int mtile, int act, void* stream);
 /* weight gradient of the same convolutions with the halo resident (three x-shifted windows per halo row, so that a lane's eight consecutive output positions are 16 aligned
  * bytes for every tap): dW [Cout][Cin][27], summed over the batch, from dY [B][Cout][D][H][W] and X [B][Cin][D][H][W].  A workgroup owns 128 / 192 output channels x
  * (8 input channels x 27 taps) and streams over its share of the 4 x 4 x 8 spatial blocks; the K-split slabs (ws: segx_conv3d_halo_wgrad_ws_floats floats) are reduced

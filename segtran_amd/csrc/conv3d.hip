@@ -426,6 +426,31 @@ __global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(WPE) void conv3d_fwd_x
     gemm_mainloop_x6<Cfg, DenseLoader6<true, Cfg::BM>, ConvFwdLoaderB6, 0, TERMS>(acc, la, lb, t.kbeg, t.kend, lds);
     gemm_epilogue<SEGX_EPI_NONE, Cfg>(acc, g, t);
 }
+// The forward kernels with a fused epilogue (EPI = SEGX_EPI_RELU: y = max(conv + bias[co], 0), the bias through GemmArgs.bias / SEGX_BIAS_M as in the plain epilogue): a
+// convolution whose BatchNorm was folded into filters and bias (inference, segx_conv3d_fwd_bias_act).  Loaders, main loop and tile walk are those of
+// conv3d_fwd_kernel / conv3d_fwd_x6_kernel; split-K launches keep the plain kernels (raw slabs) and clamp in the slab reduction.
+template <bool VEC, class Cfg, bool PACK8, int EPI>
+__global__ __launch_bounds__(256, 2) void conv3d_fwd_act_kernel(GemmArgs g, ConvGeom q) {
+    static_assert(Cfg::BN == 128, "conv loaders fill 128 columns");
+    __shared__ __attribute__((aligned(16))) TileLdsT<Cfg> lds;
+    const TileCoord t = tile_coord<Cfg>(g);
+    const DenseLoader<true, VEC, Cfg::BM> la{g.A, g.a_m, 1, t.m0, g.M};
+    const ConvFwdLoaderB<PACK8> lb(g.B + (int64_t)t.zb * g.b_b0, q, t.n0, g.N);
+    f32x16 acc[Cfg::MI][Cfg::NJ];
+    gemm_mainloop<Cfg>(acc, la, lb, t.kbeg, t.kend, lds);
+    gemm_epilogue<EPI, Cfg>(acc, g, t);
+}
+template <class Cfg, int WPE, int TERMS, int EPI>
+__global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(WPE) void conv3d_fwd_x6_act_kernel(GemmArgs g, ConvGeom q) {
+    static_assert(Cfg::BN == 128, "conv loaders fill 128 columns");
+    __shared__ __attribute__((aligned(16))) unsigned char lds[X6Lds<Cfg, TERMS>::BYTES];
+    const TileCoord t = tile_coord<Cfg>(g);
+    const DenseLoader6<true, Cfg::BM> la{g.A, g.a_m, 1, t.m0, g.M};
+    const ConvFwdLoaderB6 lb(g.B + (int64_t)t.zb * g.b_b0, q, t.n0, g.N);
+    f32x16 acc[Cfg::MI][Cfg::NJ];
+    gemm_mainloop_x6<Cfg, DenseLoader6<true, Cfg::BM>, ConvFwdLoaderB6, 0, TERMS>(acc, la, lb, t.kbeg, t.kend, lds);
+    gemm_epilogue<EPI, Cfg>(acc, g, t);
+}
 template <class Cfg, int WPE, int FASTW>
 __global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(WPE) void conv3d_wgrad_x6_kernel(GemmArgs g, ConvGeom q) {
     static_assert(Cfg::BN == 128, "conv loaders fill 128 columns");
@@ -1310,6 +1335,14 @@ template <class Cfg, int WPE> static ConvKernel conv_tile_kernel(const ConvRoute
     }); });
 }
 static ConvKernel conv_kernel(const ConvRoute& r) { return r.rows == CfgCout64::BM ? conv_tile_kernel<CfgCout64, 4>(r) : conv_tile_kernel<Cfg128, 3>(r); }
+// the forward kernels with the fused ReLU epilogue (un-split forward launches of segx_conv3d_fwd_bias_act): the same route -> the same tile, engine and term count
+template <class Cfg, int WPE> static ConvKernel conv_tile_relu_kernel(const ConvRoute& r) {
+    if (r.engine == CONV_X6) return r.terms == 3 ? conv3d_fwd_x6_act_kernel<Cfg, WPE, 3, SEGX_EPI_RELU> : conv3d_fwd_x6_act_kernel<Cfg, WPE, 6, SEGX_EPI_RELU>;
+    return by_flag(r.vec, [&](auto v) { return by_flag(r.packed, [&](auto p) -> ConvKernel {
+        return conv3d_fwd_act_kernel<decltype(v)::value, Cfg, decltype(p)::value, SEGX_EPI_RELU>;
+    }); });
+}
+static ConvKernel conv_relu_kernel(const ConvRoute& r) { return r.rows == CfgCout64::BM ? conv_tile_relu_kernel<CfgCout64, 4>(r) : conv_tile_relu_kernel<Cfg128, 3>(r); }
 
 }  // namespace segx
 
@@ -1367,7 +1400,7 @@ extern "C" int segx_conv3d_fwd_terms(int B, int Cout, const int* geom, int split
  * stages whose position grid alone cannot fill the GPU (192 x 588 x 10368: 40 workgroups un-split).
  * dense_bs / x_bs / out_bs: batch strides (floats) of dY / X / Y when they are channel slices of wider NC... tensors; 0 = dense */
 static int conv3d_impl(bool wgrad, const float* dense, const float* X, float* out, int B, int Cout, const int* geom, int splitk, float* workspace, bool packed,
-                       hipStream_t stream, int64_t dense_bs = 0, int64_t x_bs = 0, int64_t out_bs = 0) {
+                       hipStream_t stream, int64_t dense_bs = 0, int64_t x_bs = 0, int64_t out_bs = 0, const float* bias = nullptr, bool relu = false) {
     const char* who = wgrad ? "segx_conv3d_bwd_weight" : "segx_conv3d_fwd";
     SEGX_REQUIRE(dense && X && out && geom && B > 0 && Cout > 0 && B <= 65535, "%s: bad args", who);
     const ConvGeom q = make_geom(geom);
@@ -1382,17 +1415,30 @@ static int conv3d_impl(bool wgrad, const float* dense, const float* X, float* ou
     const int N = wgrad ? CK : (int)P, K = wgrad ? (int)P : CK;
     GemmArgs g; g.A = dense; g.B = X; g.C = splitk > 1 ? workspace : out;
     g.a_b0 = !wgrad ? 0 : dense_bs ? dense_bs : (int64_t)Cout * P; g.a_m = K; g.b_b0 = x_bs ? x_bs : sample; g.c_b0 = out_bs ? out_bs : (int64_t)Cout * N; g.c_m = N;
-    g.bias = nullptr; g.aux = nullptr; g.gmax = nullptr; g.nb1 = 1; g.bias_b1 = 0; g.bias_b0 = 0; g.alpha = 1.0f; g.epilogue = SEGX_EPI_NONE; g.bias_mode = SEGX_BIAS_NONE;
+    g.bias = bias; g.aux = nullptr; g.gmax = nullptr; g.nb1 = 1; g.bias_b1 = 0; g.bias_b0 = 0; g.alpha = 1.0f; g.epilogue = SEGX_EPI_NONE; g.bias_mode = bias ? SEGX_BIAS_M : SEGX_BIAS_NONE;
     g.a_b1 = g.b_b1 = g.c_b1 = 0; g.b_n = g.b_k = 0; g.a_k = 1; g.vecA = g.vecB = 0;
     g.M = Cout; g.N = N; g.K = K; g.tiles_m = r.tiles_m; g.tiles_n = r.tiles_n;
     g.dropout_p = 0.f; g.seed = g.offset = 0; g.rbase = nullptr; g.splitk = splitk; g.slab = 0; g.resid = nullptr;
     g.k_chunk = r.k_chunk; g.c_split = (int64_t)B * Cout * N;
     if (r.engine == CONV_X6) knobs().x6_launches.fetch_add(1, std::memory_order_relaxed);
     if (r.terms == 3) knobs().x3_launches.fetch_add(1, std::memory_order_relaxed);
-    hipLaunchKernelGGL(conv_kernel(r), r.grid, dim3(256), 0, stream, g, q);
+    // bias (+ ReLU): from the epilogue of an un-split launch (g.bias; the ReLU form of the kernel); a split launch writes raw slabs with the plain kernel (the
+    // epilogue reads no bias there) and the slab reduction below adds the bias after the slab sum and clamps
+    const bool fused_relu = relu && splitk == 1;
+    if (fused_relu) g.epilogue = SEGX_EPI_RELU;
+    const ConvKernel kernel = fused_relu ? conv_relu_kernel(r) : conv_kernel(r);
+    hipLaunchKernelGGL(kernel, r.grid, dim3(256), 0, stream, g, q);
     int rc = check_launch(who);
     if (rc || splitk == 1) return rc;
     const int64_t total = g.c_split;
+    if (bias || relu) {
+        const int bmode = bias ? SEGX_BIAS_M : SEGX_BIAS_NONE;
+        if (relu) SEGX_SPLITK_REDUCE_K(splitk_reduce_relu_kernel, (unsigned)i64min(2048, (total + 255) / 256), stream, (const float*)workspace, out, bias, Cout, N, 1, splitk, g.c_split,
+                                       g.c_b0, (int64_t)0, (int64_t)N, 1.0f, bmode, (int64_t)0, (int64_t)0, total, (const float*)nullptr);
+        else SEGX_SPLITK_REDUCE((unsigned)i64min(2048, (total + 255) / 256), stream, (const float*)workspace, out, bias, Cout, N, 1, splitk, g.c_split,
+                                g.c_b0, (int64_t)0, (int64_t)N, 1.0f, bmode, (int64_t)0, (int64_t)0, total, (const float*)nullptr);
+        return check_launch("segx_conv3d_fwd_bias_act/reduce");
+    }
     SEGX_SPLITK_REDUCE((unsigned)i64min(2048, (total + 255) / 256), stream, (const float*)workspace, out, (const float*)nullptr, Cout, N, 1, splitk, g.c_split,
                        g.c_b0, (int64_t)0, (int64_t)N, 1.0f, (int)SEGX_BIAS_NONE, (int64_t)0, (int64_t)0, total, (const float*)nullptr);
     return check_launch(wgrad ? "segx_conv3d_bwd_weight/reduce" : "segx_conv3d_fwd/reduce");
@@ -1437,6 +1483,39 @@ extern "C" int segx_conv3d_fwd_packed_bs(const float* X, const float* Wp, float*
                                          int64_t x_bstride, int64_t y_bstride, void* stream_) {
     SEGX_REQUIRE(x_bstride >= 0 && y_bstride >= 0 && aligned16c(X) && aligned16c(Y), "segx_conv3d_fwd_packed_bs: bad strides / alignment");
     return conv3d_impl(false, Wp, X, Y, B, Cout, geom, splitk, workspace, true, (hipStream_t)stream_, 0, x_bstride, y_bstride);
+}
+/* Y = act(conv3d(X, W) + bias[co]): a convolution whose BatchNorm was folded into filters and bias (inference).  act: 0 = none, 2 = ReLU (the library's ACT_RELU).
+ * packed: W in the order of segx_conv3d_pack_weights (Cin % 8 == 0); x_bstride / y_bstride: sample strides of channel slices (0 = dense; else packed, X and Y 16-byte aligned).
+ * Routed, counted and priced exactly like segx_conv3d_fwd* (segx_conv3d_route / segx_conv3d_splitk answer for this call too): un-split, bias and ReLU come from the
+ * kernel's epilogue; with splitk > 1 from the slab reduction, the bias added after the slab sum. */
+extern "C" int segx_conv3d_fwd_bias_act(const float* X, const float* W, const float* bias, float* Y, int B, int Cout, const int* geom, int splitk, float* workspace,
+                                        int packed, int64_t x_bstride, int64_t y_bstride, int act, void* stream_) {
+    SEGX_REQUIRE(bias && (act == 0 || act == 2), "segx_conv3d_fwd_bias_act: needs a bias and act = 0 (none) or 2 (ReLU), got act %d", act);
+    SEGX_REQUIRE(x_bstride >= 0 && y_bstride >= 0 && ((!x_bstride && !y_bstride) || (packed && aligned16c(X) && aligned16c(Y))),
+                 "segx_conv3d_fwd_bias_act: bad strides / alignment (channel slices: packed filters, 16-byte aligned X and Y, as segx_conv3d_fwd_packed_bs)");
+    return conv3d_impl(false, W, X, Y, B, Cout, geom, splitk, workspace, packed != 0, (hipStream_t)stream_, 0, x_bstride, y_bstride, bias, act == 2);
+}
+/* Y[b][i] = max(Y[b][i] + map[i], 0) in place, i < n: the one pass after the space-to-depth stem convolution of a folded model -- map [O, OD, OH, OW] is the
+ * bridge's bias seen through the taps the zero padding leaves on, scaled by the BatchNorm factor, plus the folded BatchNorm bias */
+template <bool VEC>
+__global__ __launch_bounds__(256) void bias_map_relu_kernel(float* __restrict__ Y, const float* __restrict__ map, int64_t n, int64_t total) {
+    constexpr int W = VEC ? 4 : 1;
+    for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < total / W; u += (int64_t)gridDim.x * 256) {
+        const int64_t idx = u * W, i = idx % n;
+        if constexpr (VEC) {
+            float4 y = *reinterpret_cast<const float4*>(Y + idx); const float4 m = *reinterpret_cast<const float4*>(map + i);
+            y.x = fmaxf(y.x + m.x, 0.f); y.y = fmaxf(y.y + m.y, 0.f); y.z = fmaxf(y.z + m.z, 0.f); y.w = fmaxf(y.w + m.w, 0.f);
+            *reinterpret_cast<float4*>(Y + idx) = y;
+        } else Y[idx] = fmaxf(Y[idx] + map[i], 0.f);
+    }
+}
+extern "C" int segx_bias_map_relu(float* Y, const float* map, int B, int64_t n, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(Y && map && B > 0 && n > 0, "segx_bias_map_relu: bad args");
+    const int64_t total = (int64_t)B * n;
+    if (n % 4 == 0 && aligned16c(Y) && aligned16c(map))
+        hipLaunchKernelGGL(bias_map_relu_kernel<true>, dim3((unsigned)i64min(4096, (total / 4 + 255) / 256)), dim3(256), 0, stream, Y, map, n, total);
+    else hipLaunchKernelGGL(bias_map_relu_kernel<false>, dim3((unsigned)i64min(4096, (total + 255) / 256)), dim3(256), 0, stream, Y, map, n, total);
+    return check_launch("segx_bias_map_relu");
 }
 extern "C" int segx_conv3d_bwd_weight_packed_bs(const float* dY, const float* X, float* dWb, int B, int Cout, const int* geom, int splitk,
                                                 float* workspace, int64_t dy_bstride, int64_t x_bstride, void* stream_) {

@@ -61,6 +61,7 @@ struct HaloArgs {
     int Cin, Cout, D, H, W;                  // stride 1, 'same': input extent == output extent
     int64_t x_bs, y_bs;                      // sample strides in floats
     int ntd, nth, ntw, nmt, ncb;             // tiles per axis, output-channel tiles, channel blocks of 8
+    const float* bias;                       // [Cout], ACT != 0 only (last: the plain kernels' view of the arguments is what it was)
 };
 
 // lane (fragment row r = lane & 31) -> (x-row q of the block, x): the even-y rows go to the first ds_read_b128 lane group, the odd-y rows to the second
@@ -78,9 +79,12 @@ template <int TW> __device__ __forceinline__ void halo_row_of(int r, int& q, int
 // TERMS = 3 (knob x6_terms, read by segx_conv3d_halo_fwd): the three-term product hi.mid + mid.hi + hi.hi of gemm_x6.h -- the halo is split into the hi and mid planes only
 // (split2_pair), only those two planes of the filter bank are loaded and staged (the bank keeps its three-plane format), LDS is 2 PH + 2 PA, a step reads two fragments
 // per operand and issues three matrix instructions per block.  Everything else -- tile walk, staging maps, prefetches, epilogue -- is shared with TERMS = 6.
-template <class Cfg, int WPE, int TERMS = 6>
+// ACT = 2 (ReLU; segx_conv3d_halo_bias_act_fwd: a layer whose BatchNorm was folded into filters and bias, inference): the store loop adds g.bias[co] and clamps at
+// zero -- fp32 add, then max, on the accumulator the plain kernel stores.  ACT = 0 is the plain kernel: g.bias is not read.
+template <class Cfg, int WPE, int TERMS = 6, int ACT = 0>
 __global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(WPE) void conv3d_halo_fwd_x6_kernel(HaloArgs g) {
     static_assert(TERMS == 6 || TERMS == 3, "six or three bf16 products per block");
+    static_assert(ACT == 0 || ACT == 2, "plain, or bias + ReLU");
     constexpr int MI = Cfg::MI, NJ = Cfg::NJ, PA = Cfg::PA, PH = Cfg::PH, TW = Cfg::TW, TH = Cfg::TH, TD = Cfg::TD, NPL = x6_planes(TERMS);
     static_assert(NPL * (PH + PA) <= Cfg::LDS_BYTES, "the planes of this term count fit the configuration's LDS figure");
     __shared__ __attribute__((aligned(16))) unsigned char lds[NPL * (PH + PA)];
@@ -235,7 +239,11 @@ __global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(WPE) void conv3d_halo_
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int co = m0 + wm * (32 * MI) + 32 * i + 8 * (r >> 2) + 4 * kh + (r & 3);
-                    if (co < g.Cout) Yb[(int64_t)co * chan + pos] = acc[i][j][r];
+                    if constexpr (ACT == 0) {
+                        if (co < g.Cout) Yb[(int64_t)co * chan + pos] = acc[i][j][r];
+                    } else {
+                        if (co < g.Cout) Yb[(int64_t)co * chan + pos] = fmaxf(acc[i][j][r] + g.bias[co], 0.f);
+                    }
                 }
         }
     }
@@ -596,8 +604,9 @@ extern "C" int segx_conv3d_halo_pack(const float* W, void* Wq, int O, int C, int
 }
 /* Y[b][Cout][D][H][W] = conv3d(X[b][Cin][D][H][W], filters) for the geometries segx_conv3d_halo_ok accepts; Wq from segx_conv3d_halo_pack (O = Cout, C = Cin);
  * x_bs / y_bs: sample strides in floats (0 = dense).  mtile: 0 = chosen here, else 64 / 128 / 192 output channels per workgroup (measurements) */
-extern "C" int segx_conv3d_halo_fwd(const float* X, const void* Wq, float* Y, int B, int Cout, const int* geom, int64_t x_bs, int64_t y_bs, int mtile, void* stream_) {
-    SEGX_STREAM; SEGX_REQUIRE(X && Wq && Y && B > 0 && Cout > 0 && halo_geom_ok(geom), "segx_conv3d_halo_fwd: bad args (3 x 3 x 3, stride 1, 'same', Cin %% 8 == 0 only)");
+static int halo_fwd_impl(const float* X, const void* Wq, const float* bias, int act, float* Y, int B, int Cout, const int* geom, int64_t x_bs, int64_t y_bs, int mtile,
+                         hipStream_t stream) {
+    SEGX_REQUIRE(X && Wq && Y && B > 0 && Cout > 0 && halo_geom_ok(geom), "segx_conv3d_halo_fwd: bad args (3 x 3 x 3, stride 1, 'same', Cin %% 8 == 0 only)");
     const int Cin = geom[0], D = geom[1], H = geom[2], W = geom[3];
     int64_t tiles = 0;
     const int twd = halo_tile(D, H, W, &tiles);
@@ -605,7 +614,7 @@ extern "C" int segx_conv3d_halo_fwd(const float* X, const void* Wq, float* Y, in
     SEGX_REQUIRE((reinterpret_cast<uintptr_t>(Wq) & 15) == 0, "segx_conv3d_halo_fwd: unaligned filter bank");
     if (mtile == 0) mtile = halo_mtile(Cout, tiles * B);
     SEGX_REQUIRE(mtile == 64 || mtile == 128 || mtile == 192, "segx_conv3d_halo_fwd: mtile %d", mtile);
-    HaloArgs g; g.X = X; g.Wq = (const unsigned char*)Wq; g.Y = Y; g.Cin = Cin; g.Cout = Cout; g.D = D; g.H = H; g.W = W;
+    HaloArgs g; g.bias = bias; g.X = X; g.Wq = (const unsigned char*)Wq; g.Y = Y; g.Cin = Cin; g.Cout = Cout; g.D = D; g.H = H; g.W = W;
     g.x_bs = x_bs ? x_bs : (int64_t)Cin * D * H * W; g.y_bs = y_bs ? y_bs : (int64_t)Cout * D * H * W;
     g.ntd = ceil_div(D, twd == 8 ? 4 : 8); g.nth = ceil_div(H, 4); g.ntw = ceil_div(W, twd); g.nmt = ceil_div(Cout, mtile); g.ncb = Cin / 8;
     const int64_t wgs = (int64_t)B * g.ntd * g.nth * g.ntw * g.nmt;
@@ -620,12 +629,34 @@ extern "C" int segx_conv3d_halo_fwd(const float* X, const void* Wq, float* Y, in
         if (twd == 8) hipLaunchKernelGGL((conv3d_halo_fwd_x6_kernel<HaloCfg<MI, 4, 4, 8>, WPE, TERMS>), grid, dim3(256), 0, stream, g); \
         else hipLaunchKernelGGL((conv3d_halo_fwd_x6_kernel<HaloCfg<MI, 8, 4, 4>, WPE, TERMS>), grid, dim3(256), 0, stream, g); } while (0)
 #define SEGX_HALO_LAUNCH(MI, WPE) do { if (terms == 3) SEGX_HALO_LAUNCH_T(MI, WPE, 3); else SEGX_HALO_LAUNCH_T(MI, WPE, 6); } while (0)
+#define SEGX_HALO_ACT_LAUNCH_T(MI, WPE, TERMS) do { \
+        if (twd == 8) hipLaunchKernelGGL((conv3d_halo_fwd_x6_kernel<HaloCfg<MI, 4, 4, 8>, WPE, TERMS, 2>), grid, dim3(256), 0, stream, g); \
+        else hipLaunchKernelGGL((conv3d_halo_fwd_x6_kernel<HaloCfg<MI, 8, 4, 4>, WPE, TERMS, 2>), grid, dim3(256), 0, stream, g); } while (0)
+#define SEGX_HALO_ACT_LAUNCH(MI, WPE) do { if (terms == 3) SEGX_HALO_ACT_LAUNCH_T(MI, WPE, 3); else SEGX_HALO_ACT_LAUNCH_T(MI, WPE, 6); } while (0)
+    if (act) {                                               // bias + ReLU in the store loop (twelve forms: MI 1 / 2 / 3 x two tilings x TERMS 6 / 3)
+        if (mtile == 64) SEGX_HALO_ACT_LAUNCH(1, 4);
+        else if (mtile == 128) SEGX_HALO_ACT_LAUNCH(2, 3);
+        else SEGX_HALO_ACT_LAUNCH(3, 2);
+        return check_launch("segx_conv3d_halo_bias_act_fwd");
+    }
     if (mtile == 64) SEGX_HALO_LAUNCH(1, 4);
     else if (mtile == 128) SEGX_HALO_LAUNCH(2, 3);
     else SEGX_HALO_LAUNCH(3, 2);
 #undef SEGX_HALO_LAUNCH
 #undef SEGX_HALO_LAUNCH_T
+#undef SEGX_HALO_ACT_LAUNCH
+#undef SEGX_HALO_ACT_LAUNCH_T
     return check_launch("segx_conv3d_halo_fwd");
+}
+extern "C" int segx_conv3d_halo_fwd(const float* X, const void* Wq, float* Y, int B, int Cout, const int* geom, int64_t x_bs, int64_t y_bs, int mtile, void* stream_) {
+    return halo_fwd_impl(X, Wq, nullptr, 0, Y, B, Cout, geom, x_bs, y_bs, mtile, (hipStream_t)stream_);
+}
+/* segx_conv3d_halo_fwd with bias[co] added to every output and ReLU applied, in the store loop (act = 2, the library's ACT_RELU; nothing else is built): a
+ * 3 x 3 x 3 convolution whose BatchNorm was folded into filters and bias (inference).  Same routing, counters and precision selector as the plain call. */
+extern "C" int segx_conv3d_halo_bias_act_fwd(const float* X, const void* Wq, const float* bias, float* Y, int B, int Cout, const int* geom, int64_t x_bs, int64_t y_bs, int mtile,
+                                             int act, void* stream_) {
+    SEGX_REQUIRE(bias && act == 2, "segx_conv3d_halo_bias_act_fwd: needs a bias and act = 2 (ReLU), got act %d", act);
+    return halo_fwd_impl(X, Wq, bias, act, Y, B, Cout, geom, x_bs, y_bs, mtile, (hipStream_t)stream_);
 }
 
 /* r06 -- weight gradient of the same convolutions with a resident halo: dW [Cout][Cin][27] (summed over the batch) from dY [B][Cout][D][H][W] and X [B][Cin][D][H][W];

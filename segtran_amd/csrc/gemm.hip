@@ -220,7 +220,7 @@ static int skinny_nt_splitk(const float* A, const float* B, const segx_gemm_desc
 
 static int gemm_plan_impl(const float* A, const float* B, const segx_gemm_desc* d, int* tile, int* splitk, bool use_table) {
     SEGX_REQUIRE(A && B && d && tile && splitk && d->M > 0 && d->N > 0 && d->K > 0 && d->nb0 > 0 && d->nb1 > 0, "segx_gemm_plan: bad args");
-    const bool plain = d->epilogue == SEGX_EPI_NONE, swish = d->epilogue == SEGX_EPI_SWISH;
+    const bool plain = d->epilogue == SEGX_EPI_NONE, swish = d->epilogue == SEGX_EPI_SWISH || d->epilogue == SEGX_EPI_RELU;      // (the fused ReLU is planned, routed and built like the fused swish)
     int t = SEGX_TILE_128x128, sk = 1;
     const bool vec = gemm_vec_ok(A, B, d);
     if (const int ssk = skinny_nt_splitk(A, B, d)) { *tile = SEGX_TILE_SKINNY_NT; *splitk = ssk; return 0; }
@@ -294,7 +294,7 @@ static int gemm_route(const float* A, const float* B, const segx_gemm_desc* d, G
     r.ws_grid = kget(knobs().ws_grid); r.walk = kget(knobs().tile_walk) != 0; r.terms = 0;
     const int want_terms = kget(knobs().x6_terms);
     const int nbatch = d->nb0 * d->nb1;
-    const bool gelu = d->epilogue == SEGX_EPI_GELU, swish = d->epilogue == SEGX_EPI_SWISH, ws_forced = ws_tile_id(d->tile);
+    const bool gelu = d->epilogue == SEGX_EPI_GELU, swish = d->epilogue == SEGX_EPI_SWISH || d->epilogue == SEGX_EPI_RELU, ws_forced = ws_tile_id(d->tile);
     const int engine = call_engine(d);
     SEGX_REQUIRE(!ws_forced || engine == SEGX_ENGINE_BF16X6, "segx_gemm_f32: tile %d exists on the bf16x6 engine only", d->tile);
     int tile = d->tile;
@@ -314,7 +314,7 @@ static int gemm_route(const float* A, const float* B, const segx_gemm_desc* d, G
         if (x6) plan6(d->M, d->N, d->K, nbatch, gelu, false, r.splitk, ws_ok && !swish, (!r.akc) + (!r.bkc), &tile, &sk_unused);
         else plan(d->M, d->N, d->K, nbatch, r.vec && !gelu, false, r.splitk, &tile, &sk_unused, !swish);
     }
-    // the fused swish (a folded pointwise convolution's forward) is built for the three four-wave tiles of either engine: any other tile a caller names takes the default one
+    // the fused swish / ReLU (a folded pointwise convolution's forward) is built for the three four-wave tiles of either engine: any other tile a caller names takes the default one
     if (swish && tile != SEGX_TILE_64x128 && tile != SEGX_TILE_64x64) tile = SEGX_TILE_128x128;
     if (ws_forced && !ws_ok) tile = SEGX_TILE_128x128;
     // the 96-row tiles (channel counts 272 / 160 / 192 / 672 / 960 of the backbone: 3 x 96 = 288 rows cover 272 where 3 x 128 compute 384) stage their 96-row
@@ -375,12 +375,15 @@ template <class Cfg> static GemmLaunch f32_tile(const GemmRoute& r) {
     return built_for<Cfg>(by_layout(r, [](auto ak, auto bk) -> GemmKernel { return gemm_f32_kernel<Cfg, decltype(ak)::value, decltype(bk)::value, true, SEGX_EPI_NONE>; }));
 }
 // the fused swish: k-contiguous A, row-contiguous B (segx_gemm_f32 refuses other layouts)
-template <class Cfg> static GemmLaunch f32_swish_tile() { return built_for<Cfg>(gemm_f32_kernel<Cfg, true, false, true, SEGX_EPI_SWISH>); }
+template <class Cfg, int E = SEGX_EPI_SWISH> static GemmLaunch f32_swish_tile() { return built_for<Cfg>(gemm_f32_kernel<Cfg, true, false, true, E>); }
+// ... and the fused ReLU, the same set of forms
+template <int E> static GemmLaunch f32_act_kernel(const GemmRoute& r) {
+    if (!r.vec) return built_for<Cfg128>(gemm_f32_kernel<Cfg128, true, false, false, E>);
+    return r.tile == SEGX_TILE_64x64 ? f32_swish_tile<Cfg64, E>() : r.tile == SEGX_TILE_64x128 ? f32_swish_tile<Cfg64x128, E>() : f32_swish_tile<Cfg128, E>();
+}
 static GemmLaunch f32_kernel(const GemmRoute& r) {
-    if (r.epi == SEGX_EPI_SWISH) {
-        if (!r.vec) return built_for<Cfg128>(gemm_f32_kernel<Cfg128, true, false, false, SEGX_EPI_SWISH>);
-        return r.tile == SEGX_TILE_64x64 ? f32_swish_tile<Cfg64>() : r.tile == SEGX_TILE_64x128 ? f32_swish_tile<Cfg64x128>() : f32_swish_tile<Cfg128>();
-    }
+    if (r.epi == SEGX_EPI_SWISH) return f32_act_kernel<SEGX_EPI_SWISH>(r);
+    if (r.epi == SEGX_EPI_RELU) return f32_act_kernel<SEGX_EPI_RELU>(r);
     if (r.epi == SEGX_EPI_GELU)
         return built_for<Cfg128>(by_flag(r.bkc, [&](auto bk) { return by_flag(r.vec, [](auto v) -> GemmKernel {
             return gemm_f32_kernel<Cfg128, true, decltype(bk)::value, decltype(v)::value, SEGX_EPI_GELU>; }); }));
@@ -401,14 +404,18 @@ template <bool LEAN, class Cfg, bool AK, bool BK, int E, int W, int T = 6> stati
 template <bool LEAN, class Cfg, int W> static GemmLaunch x6_tile(const GemmRoute& r) {
     return built_for<Cfg>(by_layout(r, [](auto ak, auto bk) { return x6_form<LEAN, Cfg, decltype(ak)::value, decltype(bk)::value, SEGX_EPI_NONE, W>(); }));
 }
+// the fused swish / ReLU: k-contiguous A, row-contiguous B, the three four-wave tiles
+template <bool LEAN, int E> static GemmLaunch x6_act_kernel(const GemmRoute& r) {
+    switch (r.tile) {
+        case SEGX_TILE_64x64: return built_for<Cfg64>(x6_form<LEAN, Cfg64, true, false, E, 5>());
+        case SEGX_TILE_64x128: return built_for<Cfg64x128>(x6_form<LEAN, Cfg64x128, true, false, E, 4>());
+        default: return built_for<Cfg128>(x6_form<LEAN, Cfg128, true, false, E, 3>());
+    }
+}
 template <bool LEAN> static GemmLaunch x6_kernel(const GemmRoute& r) {
     if (r.epi == SEGX_EPI_GELU) return built_for<Cfg128>(by_flag(r.bkc, [](auto bk) { return x6_form<LEAN, Cfg128, true, decltype(bk)::value, SEGX_EPI_GELU, 3>(); }));
-    if (r.epi == SEGX_EPI_SWISH)
-        switch (r.tile) {
-            case SEGX_TILE_64x64: return built_for<Cfg64>(x6_form<LEAN, Cfg64, true, false, SEGX_EPI_SWISH, 5>());
-            case SEGX_TILE_64x128: return built_for<Cfg64x128>(x6_form<LEAN, Cfg64x128, true, false, SEGX_EPI_SWISH, 4>());
-            default: return built_for<Cfg128>(x6_form<LEAN, Cfg128, true, false, SEGX_EPI_SWISH, 3>());
-        }
+    if (r.epi == SEGX_EPI_SWISH) return x6_act_kernel<LEAN, SEGX_EPI_SWISH>(r);
+    if (r.epi == SEGX_EPI_RELU) return x6_act_kernel<LEAN, SEGX_EPI_RELU>(r);
     switch (r.tile) {
         case SEGX_TILE_64x64: return x6_tile<LEAN, Cfg64, 5>(r);
         case SEGX_TILE_64x128: return x6_tile<LEAN, Cfg64x128, 4>(r);
@@ -418,6 +425,7 @@ template <bool LEAN> static GemmLaunch x6_kernel(const GemmRoute& r) {
 // the three-term forms of the same kernels (exactly what x3_built() names), at the waves per SIMD of their six-term siblings
 template <bool LEAN, class Cfg, int W> static GemmLaunch x3_tile(const GemmRoute& r) {
     if (r.epi == SEGX_EPI_SWISH) return built_for<Cfg>(x6_form<LEAN, Cfg, true, false, SEGX_EPI_SWISH, W, 3>());
+    if (r.epi == SEGX_EPI_RELU) return built_for<Cfg>(x6_form<LEAN, Cfg, true, false, SEGX_EPI_RELU, W, 3>());
     if constexpr (LEAN) {
         if (r.bkc) return built_for<Cfg>(by_flag(r.akc, [](auto ak) { return x6_form<true, Cfg, decltype(ak)::value, true, SEGX_EPI_NONE, W, 3>(); }));
     }
@@ -557,7 +565,9 @@ extern "C" int segx_gemm_f32(const float* A, const float* B, float* C, const seg
                  d->M, d->N, d->K, d->nb0, d->nb1);
     SEGX_REQUIRE(d->a_m == 1 || d->a_k == 1, "segx_gemm_f32: A needs a unit stride (a_m=%lld a_k=%lld)", (long long)d->a_m, (long long)d->a_k);
     SEGX_REQUIRE(d->b_n == 1 || d->b_k == 1, "segx_gemm_f32: B needs a unit stride (b_n=%lld b_k=%lld)", (long long)d->b_n, (long long)d->b_k);
-    SEGX_REQUIRE(d->epilogue == SEGX_EPI_NONE || d->epilogue == SEGX_EPI_GELU || d->epilogue == SEGX_EPI_SWISH, "segx_gemm_f32: bad epilogue %d", d->epilogue);
+    SEGX_REQUIRE(d->epilogue == SEGX_EPI_NONE || d->epilogue == SEGX_EPI_GELU || d->epilogue == SEGX_EPI_SWISH || d->epilogue == SEGX_EPI_RELU, "segx_gemm_f32: bad epilogue %d", d->epilogue);
+    SEGX_REQUIRE(d->epilogue != SEGX_EPI_RELU || (d->a_k == 1 && d->b_n == 1 && d->b_k != 1 && !d->resid && !d->gmax && d->dropout_p == 0.f),
+                 "segx_gemm_f32: the relu epilogue is built for a pointwise convolution's forward (A k-contiguous, B row-contiguous; no resid, gmax or dropout)");
     SEGX_REQUIRE(d->epilogue != SEGX_EPI_SWISH || (d->a_k == 1 && d->b_n == 1 && d->b_k != 1 && !d->resid && !d->gmax && d->dropout_p == 0.f),
                  "segx_gemm_f32: the swish epilogue is built for a pointwise convolution's forward (A k-contiguous, B row-contiguous; no resid, gmax or dropout)");
     SEGX_REQUIRE(d->epilogue != SEGX_EPI_GELU || d->aux, "segx_gemm_f32: GELU epilogue needs aux");

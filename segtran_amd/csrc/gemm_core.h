@@ -315,6 +315,7 @@ __device__ __forceinline__ void gemm_epilogue(const f32x16 (&acc)[Cfg::MI][Cfg::
                     pre[q] = v;
                     if (EPI == SEGX_EPI_GELU) v = gelu_erf(v) * keep[q];
                     if (EPI == SEGX_EPI_SWISH) v = swish_fwd(v);            // a pointwise convolution with its BatchNorm folded in (inference)
+                    if (EPI == SEGX_EPI_RELU) v = fmaxf(v, 0.f);            // the same for the ReLU layers of Inception-I3D (pointwise and implicit-GEMM convolutions)
                     out[q] = v;
                     if (ok) vmax = fmaxf(vmax, v);
                     if (!vec_st && ok) {
@@ -382,11 +383,12 @@ inline int best_splitk(const TileInfo& ti, int M, int N, int K, int nbatch, doub
 // r04-g: the slabs of an output element are requested four at a time and added in slab order (the loop used to wait for every slab before asking for
 // the next: a 24-slab reduction of a small output took 32 us), and where the layout allows it a thread owns four consecutive columns (16-byte accesses).
 // VEC: N % 4 == 0, every base 16-byte aligned, every stride a multiple of 4 (checked on the host).  The sums are the same numbers in the same order.
-template <bool VEC>
-__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ ws, float* __restrict__ C, const float* __restrict__ bias,
-                                                            int M, int N, int nb1, int splitk, int64_t c_split,
-                                                            int64_t c_b0, int64_t c_b1, int64_t c_m, float alpha,
-                                                            int bias_mode, int64_t bias_b1, int64_t bias_b0, int64_t total, const float* __restrict__ resid) {
+// RELU: the sum, scaled and biased, is clamped at zero -- the second stage of a split-K convolution whose BatchNorm was folded in (splitk_reduce_relu_kernel)
+template <bool VEC, bool RELU>
+__device__ __forceinline__ void splitk_reduce_body(const float* __restrict__ ws, float* __restrict__ C, const float* __restrict__ bias,
+                                                   int M, int N, int nb1, int splitk, int64_t c_split,
+                                                   int64_t c_b0, int64_t c_b1, int64_t c_m, float alpha,
+                                                   int bias_mode, int64_t bias_b1, int64_t bias_b0, int64_t total, const float* __restrict__ resid) {
     constexpr int W = VEC ? 4 : 1;
     using V = typename std::conditional<VEC, f32x4, float>::type;
     const int64_t units = total / W;
@@ -416,8 +418,28 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
         else if (bias_mode == SEGX_BIAS_M) s += V(bp[row]);
         const int64_t o = z0 * c_b0 + z1 * c_b1 + (int64_t)row * c_m + col;
         if (resid) s += *reinterpret_cast<const V*>(resid + o);
+        if constexpr (RELU) {
+            if constexpr (VEC) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) s[q] = fmaxf(s[q], 0.f);
+            } else s = fmaxf(s, 0.f);
+        }
         *reinterpret_cast<V*>(C + o) = s;
     }
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ ws, float* __restrict__ C, const float* __restrict__ bias,
+                                                            int M, int N, int nb1, int splitk, int64_t c_split,
+                                                            int64_t c_b0, int64_t c_b1, int64_t c_m, float alpha,
+                                                            int bias_mode, int64_t bias_b1, int64_t bias_b0, int64_t total, const float* __restrict__ resid) {
+    splitk_reduce_body<VEC, false>(ws, C, bias, M, N, nb1, splitk, c_split, c_b0, c_b1, c_m, alpha, bias_mode, bias_b1, bias_b0, total, resid);
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void splitk_reduce_relu_kernel(const float* __restrict__ ws, float* __restrict__ C, const float* __restrict__ bias,
+                                                                 int M, int N, int nb1, int splitk, int64_t c_split,
+                                                                 int64_t c_b0, int64_t c_b1, int64_t c_m, float alpha,
+                                                                 int bias_mode, int64_t bias_b1, int64_t bias_b0, int64_t total, const float* __restrict__ resid) {
+    splitk_reduce_body<VEC, true>(ws, C, bias, M, N, nb1, splitk, c_split, c_b0, c_b1, c_m, alpha, bias_mode, bias_b1, bias_b0, total, resid);
 }
 // host side: may the reduction use 16-byte accesses?
 static bool splitk_vec_ok(const void* ws, const void* C, const void* bias, const void* resid, int N, int64_t c_split, int64_t c_b0, int64_t c_b1, int64_t c_m,
@@ -427,14 +449,16 @@ static bool splitk_vec_ok(const void* ws, const void* C, const void* bias, const
     if (bias_mode == SEGX_BIAS_N && (!al(bias) || (bias_b1 & 3) || (bias_b0 & 3))) return false;
     return true;
 }
-#define SEGX_SPLITK_REDUCE(blocks, stream, ws, C, bias, M, N, nb1, splitk, c_split, c_b0, c_b1, c_m, alpha, bias_mode, bias_b1, bias_b0, total, resid)               \
+#define SEGX_SPLITK_REDUCE_K(KERNEL, blocks, stream, ws, C, bias, M, N, nb1, splitk, c_split, c_b0, c_b1, c_m, alpha, bias_mode, bias_b1, bias_b0, total, resid)               \
     do {                                                                                                                                                            \
         if (splitk_vec_ok(ws, C, bias, resid, N, c_split, c_b0, c_b1, c_m, bias_mode, bias_b1, bias_b0))                                                            \
-            hipLaunchKernelGGL((splitk_reduce_kernel<true>), dim3((unsigned)i64min(2048, ((total) / 4 + 255) / 256)), dim3(256), 0, stream, ws, C, bias, M, N, nb1,  \
+            hipLaunchKernelGGL((KERNEL<true>), dim3((unsigned)i64min(2048, ((total) / 4 + 255) / 256)), dim3(256), 0, stream, ws, C, bias, M, N, nb1,  \
                                splitk, c_split, c_b0, c_b1, c_m, alpha, bias_mode, bias_b1, bias_b0, total, resid);                                                 \
-        else hipLaunchKernelGGL((splitk_reduce_kernel<false>), dim3(blocks), dim3(256), 0, stream, ws, C, bias, M, N, nb1, splitk, c_split, c_b0, c_b1, c_m, alpha, \
+        else hipLaunchKernelGGL((KERNEL<false>), dim3(blocks), dim3(256), 0, stream, ws, C, bias, M, N, nb1, splitk, c_split, c_b0, c_b1, c_m, alpha, \
                                 bias_mode, bias_b1, bias_b0, total, resid);                                                                                         \
     } while (0)
+#define SEGX_SPLITK_REDUCE(blocks, stream, ws, C, bias, M, N, nb1, splitk, c_split, c_b0, c_b1, c_m, alpha, bias_mode, bias_b1, bias_b0, total, resid) \
+    SEGX_SPLITK_REDUCE_K(splitk_reduce_kernel, blocks, stream, ws, C, bias, M, N, nb1, splitk, c_split, c_b0, c_b1, c_m, alpha, bias_mode, bias_b1, bias_b0, total, resid)
 
 // a run-time flag as a template argument: f(std::true_type) or f(std::false_type) (the kernel routers of gemm.hip and conv3d.hip)
 template <class F> static auto by_flag(bool flag, F f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }

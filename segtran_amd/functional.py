@@ -6,7 +6,7 @@ import math
 import torch
 import torch.nn.functional as F
 from . import segx
-from .segx import EPI_NONE, EPI_GELU, EPI_SWISH, BIAS_NONE, BIAS_N, BIAS_M
+from .segx import EPI_NONE, EPI_GELU, EPI_SWISH, EPI_RELU, BIAS_NONE, BIAS_N, BIAS_M
 
 LN_EPS = 1e-12      # every LayerNorm of the Squeeze-and-Expansion transformer (segtran_shared.py:262,361,889,985)
 
@@ -650,6 +650,38 @@ def conv1x1(x, weight, bias=None, pass_input=False, act=0):
         return _BGemm.apply(weight.reshape(Cout, Cin), x, bias, spec, None, False, 0.0, True)
     y = bgemm(weight.reshape(Cout, Cin), x, spec, bias=bias)
     return (y, x) if pass_input else y
+
+
+def _chan_slice_bs(v):
+    """Sample stride (floats) under which a kernel may address v -- [B, C, *spatial], dense or a channel slice of a wider NC... tensor -- in place: 0 = dense, None =
+    not addressable (samples not contiguous inside, or the slice does not start on 16 bytes / its sample stride is no float4 multiple)."""
+    if v.data_ptr() % 16:
+        return None
+    if v.is_contiguous():
+        return 0
+    if v[0].is_contiguous() and v.stride(0) % 4 == 0:
+        return int(v.stride(0))
+    return None
+
+
+def conv1x1_relu(x, weight, bias, out=None):
+    """relu(conv1x1(x, weight) + bias) from the GEMM's epilogue (SEGX_EPI_RELU) -- forward only: a pointwise convolution of Inception-I3D whose BatchNorm was folded into
+    weight and bias (InceptionI3d.fold_batchnorm).  out: where the result goes -- [B, Cout, *spatial], dense or a channel slice of a wider NC... tensor (the branch's
+    place in the module's concatenation: no copy), 16-byte aligned with a sample stride in multiples of four floats."""
+    _no_grad_operands('conv1x1_relu', x, weight, bias, out)
+    B, Cin = x.shape[0], x.shape[1]
+    S = x.numel() // (B * Cin)
+    Cout = weight.shape[0]
+    L = segx.lib()
+    x, W = _c(x), _c(weight.reshape(Cout, Cin))
+    if out is None:
+        out = _empty(x, B, Cout, *x.shape[2:])
+    bs = _chan_slice_bs(out)
+    if tuple(out.shape) != (B, Cout) + tuple(x.shape[2:]) or bs is None:
+        raise ValueError('conv1x1_relu: out must be [B, Cout, *spatial], dense or a 16-byte aligned channel slice with a sample stride in multiples of 4 floats')
+    _run_gemm(L, W, x, out, Cout, S, Cin, (0, 0, Cin, 1), (Cin * S, 0, 1, S), (bs or Cout * S, 0, S), (B, 1), 1.0, bias=bias,
+              bias_mode=BIAS_M if bias is not None else BIAS_NONE, epilogue=EPI_RELU)
+    return out
 
 
 def conv1x1_tokens(tokens, grid_shape, weight):
@@ -1769,6 +1801,102 @@ def conv3d_same(x, w, stride=(1, 1, 1)):
     """nn.Conv3d(bias=False) with the dynamic TF-'same' zero padding of Unit3D (aj_i3d.py:75-92)."""
     stride = tuple(int(s) for s in stride)
     return _Conv3d.apply(x, w, stride, _same_pads(x.shape[2:], w.shape[2:], stride))
+
+
+def conv3d_bias_relu(x, w, bias, stride=(1, 1, 1), pads=None, out=None, ops=None):
+    """relu(conv3d(x, w) + bias) with the dynamic 'same' padding of conv3d_same (or the given (front, back) pads per axis) -- forward only: a convolution whose BatchNorm
+    was folded into w and bias.  The LDS-resident-halo kernel where it serves (bias and ReLU in its store loop), else the implicit GEMM (epilogue; split-K: the slab
+    reduction).  x / out: dense, or channel slices of wider NCDHW tensors read / written in place (_chan_slice_bs; otherwise through a copy).
+    ops: a dict the caller keeps per layer -- the derived filter banks ('halo': segx_conv3d_halo_pack, 'packed': segx_conv3d_pack_weights) are built on first use and
+    reused while the caller keeps it (the fold's per-layer operand cache): no pack launch after the first call.
+    bias = None: the plain convolution on the cached bank (the folded space-to-depth stem, whose bias is a map: stem_bridge_conv_s2d_folded)."""
+    _no_grad_operands('conv3d_bias_relu', x, w, bias, out)
+    L = segx.lib()
+    stride = tuple(int(v) for v in stride)
+    B, Cin, ID, IH, IW = x.shape
+    Cout, Cw, KD, KH, KW = w.shape
+    assert Cw == Cin and (bias is None or bias.numel() == Cout)
+    (pd, pdb), (ph, phb), (pw, pwb) = pads if pads is not None else _same_pads(x.shape[2:], w.shape[2:], stride)
+    OD, OH, OW = (ID + pd + pdb - KD) // stride[0] + 1, (IH + ph + phb - KH) // stride[1] + 1, (IW + pw + pwb - KW) // stride[2] + 1
+    geom = (Cin, ID, IH, IW, OD, OH, OW, KD, KH, KW) + stride + (pd, ph, pw)
+    x_bs = _chan_slice_bs(x)
+    if x_bs is None:
+        x, x_bs = x.contiguous() if not x.is_contiguous() else x.clone(), 0
+    if out is None:
+        out = _empty(x, B, Cout, OD, OH, OW)
+    assert tuple(out.shape) == (B, Cout, OD, OH, OW)
+    y_bs = _chan_slice_bs(out)
+    y = out if y_bs is not None else _empty(x, B, Cout, OD, OH, OW)
+    y_bs = y_bs or 0
+    ops = ops if ops is not None else {}
+    w = _c(w)
+    if Cin % 8 and (x_bs or y_bs):                              # unpacked filters (no layer of I3D behind its stem): the kernels take dense operands only
+        if x_bs:
+            x, x_bs = x.contiguous(), 0
+        if y_bs:
+            y, y_bs = _empty(x, B, Cout, OD, OH, OW), 0
+    if bias is not None and L.conv3d_halo_ok(B, Cout, geom):
+        wq = ops.get('halo')
+        if wq is None:
+            wq = ops['halo'] = L.conv3d_halo_pack(w, Cout, Cin, 0)
+        L.conv3d_halo_bias_act_fwd(x, wq, bias, y, B, Cout, geom, x_bs=x_bs, y_bs=y_bs, act=ACT_RELU)
+    else:
+        sk = L.conv3d_splitk(B, Cout, geom, False)
+        ws = _empty(x, sk * B * Cout * OD * OH * OW) if sk > 1 else None
+        packed = Cin % 8 == 0
+        if packed:
+            wp = ops.get('packed')
+            if wp is None:
+                wp = torch.empty_like(w)
+                L.conv3d_pack_weights(w, wp, Cout, Cin, KD * KH * KW, 0)
+                ops['packed'] = wp
+            w = wp
+        if bias is None:
+            assert packed or not (x_bs or y_bs)
+            L.conv3d_fwd(x, w, y, B, Cout, geom, sk, ws, packed=packed, x_bs=x_bs, y_bs=y_bs)
+        else:
+            L.conv3d_fwd_bias_act(x, w, bias, y, B, Cout, geom, sk, ws, packed=packed, x_bs=x_bs, y_bs=y_bs, act=ACT_RELU)
+    if y is not out:
+        out.copy_(y)
+    return out
+
+
+def stem_s2d_folded_operands(stem_weight, bridge_weight, bridge_bias, bias):
+    """The constants of stem_bridge_conv_s2d for a stem whose BatchNorm was folded in (stem_weight = w', bias = b'): the space-to-depth filters w2 [O, 8, 7, 7, 4] and
+    the bias seen through each tap v [O, 7, 7, 7] -- the same contractions, over tensors of <= 64 x 343 x 3 x 4 numbers, in fp64 (as the fold itself), rounded once."""
+    O, C3, KD, KH, KW = stem_weight.shape
+    Cb = bridge_weight.shape[1]
+    with torch.no_grad():
+        taps = stem_weight.double().permute(0, 2, 3, 4, 1)                                            # [O, kd, kh, kw, c3]
+        wc = (taps.unsqueeze(-1) * bridge_weight.double().reshape(C3, Cb)).sum(4).permute(0, 4, 1, 2, 3)   # [O, Cb, 7, 7, 7]
+        w2 = F.pad(wc, (0, 1)).view(O, Cb, KD, KH, 4, 2).permute(0, 1, 5, 2, 3, 4).reshape(O, 2 * Cb, KD, KH, 4).float().contiguous()
+        v = (taps * bridge_bias.double()).sum(4)                                                      # [O, 7, 7, 7]
+    return w2, v, bias
+
+
+def stem_s2d_bias_map(v, bias, D, H, W):
+    """[O, OD, OH, OW] (fp32): the bridge's bias through the taps the zero padding leaves on (stem_bridge_conv_s2d's bias map) + bias[o]; depends on the input extent only"""
+    with torch.no_grad():
+        md, mh, mw = (_stem_axis_mask(n, 7, 2, 2, v.device).double() for n in (D, H, W))
+        m = sum(v[:, t, None] * md[:, t].view(1, -1, 1, 1) for t in range(7))                        # [O, OD, kh, kw]
+        m = sum(m[:, :, u, None] * mh[:, u].view(1, 1, -1, 1) for u in range(7))                     # [O, OD, OH, kw]
+        m = sum(m[:, :, :, w, None] * mw[:, w].view(1, 1, 1, -1) for w in range(7))                  # [O, OD, OH, OW]
+        return (m + bias.double().view(-1, 1, 1, 1)).float().contiguous()
+
+
+def stem_bridge_conv_s2d_folded(batch, w2, bias_map, ops=None):
+    """relu(stem_bridge_conv_s2d(...) folded with the stem's BatchNorm): the space-to-depth input, the stride-(2, 2, 1) convolution with the folded filters, and ONE pass
+    y = relu(y + bias_map) (segx_bias_map_relu) -- no linear chain, no ATen add, no BatchNorm launch.  Forward only."""
+    _no_grad_operands('stem_bridge_conv_s2d_folded', batch, w2, bias_map)
+    L = segx.lib()
+    B, Cb, H, W, D = batch.shape
+    U = W // 2 + 3
+    x2 = _empty(batch, B, 2 * Cb, D, H, U)
+    L.stem_s2d_input(_c(batch), x2, B, Cb, H, W, D, U)
+    y = conv3d_bias_relu(x2, w2, None, (2, 2, 1), ((2, 3), (2, 3), (0, 0)), ops=ops)        # (bias = None: the plain convolution on the cached packed bank)
+    assert tuple(y.shape[1:]) == tuple(bias_map.shape)
+    L.bias_map_relu(y, bias_map, B, bias_map.numel())
+    return y
 
 
 class _StemCompose(_Fn):

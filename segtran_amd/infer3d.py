@@ -6,6 +6,8 @@ accumulation and the hardening are test_util3d's own.
 
 It also holds the surface-distance half of calculate_metric_percase (reference test_util3d.py:203-213: medpy's asd, and the hd95 of the commented-out line), computed on
 the device in integers (metrics.hip) and finished here in float64; test_util3d.calculate_metric_percase keeps reporting those columns as invalid."""
+import contextlib
+
 import numpy as np
 import torch
 
@@ -14,11 +16,37 @@ from . import test_util3d as _T3
 from .infer2d import PRECISIONS, _precision, inference_precision          # noqa: F401  (inference_precision: re-exported)
 
 
+def fold_batchnorm(net):
+    """Inference: fold the BatchNorm3d layers of a Segtran3d's I3D backbone into its convolutions (InceptionI3d.fold_batchnorm; eval mode only); returns net.  The 3-D
+    entry point has its own name because Segtran3d.fold_batchnorm() keeps refusing."""
+    net.backbone.fold_batchnorm()
+    return net
+
+
+def unfold_batchnorm(net):
+    net.backbone.unfold_batchnorm()
+    return net
+
+
+@contextlib.contextmanager
+def _folded(net, fold_bn):
+    """infer2d._folded for a Segtran3d: fold for the block if asked and not folded already; a net the caller folded stays folded"""
+    here = bool(fold_bn) and not net.batchnorm_folded
+    if here:
+        fold_batchnorm(net)
+    try:
+        yield
+    finally:
+        if here:
+            unfold_batchnorm(net)
+
+
 def test_single_case(net, image, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, task_name, net_type='segtran', num_classes=4,
-                     precision='fp32'):
-    """test_util3d.test_single_case with one more argument.  precision: 'fp32' (default) -- exactly that function's results -- or 'bf16x3' -- the same loop under
-    torch.no_grad() inside inference_precision('bf16x3'); the setting the process had comes back at the end, also after an exception.  Any other name: ValueError."""
-    with _precision(precision):
+                     precision='fp32', fold_bn=False):
+    """test_util3d.test_single_case with two more arguments.  precision: 'fp32' (default) -- exactly that function's results -- or 'bf16x3' -- the same loop under
+    torch.no_grad() inside inference_precision('bf16x3'); the setting the process had comes back at the end, also after an exception.  Any other name: ValueError.
+    fold_bn: with the backbone's BatchNorm3d layers folded into its convolutions for this call (fold_batchnorm; a net the caller folded stays folded)."""
+    with _precision(precision), _folded(net, fold_bn):
         return _T3.test_single_case(net, image, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, task_name, net_type=net_type,
                                     num_classes=num_classes)
 

@@ -9,6 +9,9 @@ Kernel status: everything runs on libsegx -- the 38 1x1x1 convolutions on the MF
 BatchNorm3d+ReLU as one fused kernel (backbone.hip), the 'same' max-pools in conv3d.hip; the backward-data of the stride-2 stem
 (a transposed convolution onto 3 channels) is the residue-class gather kernel of conv3d.hip -- and is not needed at all when Segtran3d
 composes its input bridge into the stem filters (the default).  No ATen / MIOpen / rocBLAS arithmetic anywhere.
+
+Inference (opt-in): InceptionI3d.fold_batchnorm() folds every BatchNorm3d into the convolution in front of it; the layers then run as ONE launch each -- the GEMM's
+ReLU epilogue, bias + ReLU inside the halo / implicit-GEMM kernels -- and an Inception module assembles its output without BatchNorm launches or torch.cat.
 """
 import torch
 import torch.nn as nn
@@ -48,6 +51,18 @@ class Unit3D(nn.Module):
         if self._activation_fn is not None:
             x = self._activation_fn(x)
         return x
+
+    @property
+    def foldable(self):
+        """a bias-free convolution -> BatchNorm -> ReLU layer: every Unit3D of the feature extractor (not the classification head)"""
+        return self._use_batch_norm and self._activation_fn is F.relu and self.conv3d.bias is None
+
+    def forward_folded(self, x, f, out=None):
+        """f = [w', b', ops] from InceptionI3d.fold_batchnorm: relu(conv(x, w') + b') in ONE launch -- the GEMM's ReLU epilogue for a pointwise layer, else the halo /
+        implicit-GEMM kernel with bias + ReLU (SF.conv3d_bias_relu; ops: its derived filter banks, built at the first call).  No BatchNorm launch, no autograd graph."""
+        if self.pointwise:
+            return SF.conv1x1_relu(x, f[0], f[1], out=out)
+        return SF.conv3d_bias_relu(x, f[0], f[1], self._stride, out=out, ops=f[2])
 
 
 class InceptionModule(nn.Module):
@@ -91,6 +106,35 @@ class InceptionModule(nn.Module):
             return torch.cat([y0, SF.bn_act(y1, self.b1b.bn, SF.ACT_RELU), SF.bn_act(y2, self.b2b.bn, SF.ACT_RELU), self.b3b(self.b3a(x2))], dim=1)
         return torch.cat([self.b0(x), self.b1b(self.b1a(x)), self.b2b(self.b2a(x)), self.b3b(self.b3a(x))], dim=1)
 
+    def folded_operands(self):
+        """[[w', b', ops] of b0, b1a, b1b, b2a, b2b, b3b]: what forward_folded takes (InceptionI3d.fold_batchnorm derives the same per module)"""
+        from ...efficientnet.model import fold_conv_bn
+        return [list(fold_conv_bn(u.conv3d.weight, u.bn)) + [{}] for u in (self.b0, self.b1a, self.b1b, self.b2a, self.b2b, self.b3b)]
+
+    def forward_folded(self, x, layers):
+        """The module with its six BatchNorm layers folded in (layers: [w', b', ops] of b0, b1a, b1b, b2a, b2b, b3b; folded_operands()): ONE ReLU GEMM writes t = the
+        [b1a | b2a | b0] reductions; the two 3 x 3 x 3 convolutions read their slices of t and write their slices of the output (bias + ReLU in their kernels); the
+        pooling branch's ReLU GEMM writes its slice; branch 0's tail of t is copied into its slice (the one copy of the unfolded form).  Channel order [b0, b1, b2, b3].
+        No BatchNorm launch, no torch.cat; the concatenated reduction filters are kept in b1a's operand cache."""
+        f0, f1a, f1b, f2a, f2b, f3b = layers
+        ops = f1a[2]
+        if 'reduce' not in ops:
+            ops['reduce'] = (torch.cat([f1a[0], f2a[0], f0[0]], dim=0).contiguous(), torch.cat([f1a[1], f2a[1], f0[1]]).contiguous())
+        w120, b120 = ops['reduce']
+        t = SF.conv1x1_relu(x, w120, b120)
+        r1, r2 = f1a[0].shape[0], f2a[0].shape[0]
+        c0, c1, c2, c3 = f0[0].shape[0], f1b[0].shape[0], f2b[0].shape[0], f3b[0].shape[0]
+        out = torch.empty((x.shape[0], c0 + c1 + c2 + c3) + tuple(x.shape[2:]), dtype=x.dtype, device=x.device)
+        SF.conv3d_bias_relu(t[:, :r1], f1b[0], f1b[1], out=out[:, c0:c0 + c1], ops=f1b[2])
+        SF.conv3d_bias_relu(t[:, r1:r1 + r2], f2b[0], f2b[1], out=out[:, c0 + c1:c0 + c1 + c2], ops=f2b[2])
+        dst, pooled = out[:, c0 + c1 + c2:], self.b3a(x)
+        if SF._chan_slice_bs(dst) is not None:
+            SF.conv1x1_relu(pooled, f3b[0], f3b[1], out=dst)
+        else:                                                   # (a slice that does not start on 16 bytes: no I3D stage -- its channel counts come in eights)
+            dst.copy_(SF.conv1x1_relu(pooled, f3b[0], f3b[1]))
+        out[:, :c0].copy_(t[:, r1 + r2:])
+        return out
+
 
 class InceptionI3d(nn.Module):
     VALID_ENDPOINTS = ('Conv3d_1a_7x7', 'MaxPool3d_2a_3x3', 'Conv3d_2b_1x1', 'Conv3d_2c_3x3', 'MaxPool3d_3a_3x3',
@@ -123,8 +167,12 @@ class InceptionI3d(nn.Module):
         for k, m in ep.items():
             self.add_module(k, m)
 
-    def extract_features(self, x, stem_conv_out=None):
-        """stem_conv_out: output of the (bias-free) stem convolution computed by the caller; `x` is then not read."""
+    def extract_features(self, x, stem_conv_out=None, stem_out=None):
+        """stem_conv_out: output of the (bias-free) stem convolution computed by the caller; `x` is then not read.
+        stem_out (folded only): the stem layer's output after BatchNorm and ReLU, from folded_stem_bridge."""
+        if self.batchnorm_folded:
+            assert stem_conv_out is None, 'the folded extractor takes the stem output from folded_stem_bridge (Segtran3d), not a raw convolution output'
+            return self._extract_features_folded(x, stem_out)
         feat, prev = {}, None
         for name in self.VALID_ENDPOINTS:
             if name in self.end_points:
@@ -142,3 +190,95 @@ class InceptionI3d(nn.Module):
         return feat
 
     pyramid_endpoints = ('Conv3d_2c_3x3', 'Mixed_3c', 'Mixed_4f')      # feats[1..3] of Segtran3d (each is followed by a strided pool)
+
+    # ---- inference with BatchNorm3d folded into the convolutions (opt-in; DESIGN.md 5q; mirrors EfficientNet.fold_batchnorm) ---------------------------
+    _folded = None             # None, or (layers, sources, versions): layers = {module path of a Unit3D: [w', b', ops]} -- derived tensors, neither Parameters nor buffers
+
+    def _foldable_units(self):
+        """[(module path, Unit3D)]: 'Conv3d_1a_7x7', 'Mixed_3b.b1a', ..."""
+        return [(name + ('.' + sub if sub else ''), m) for name in self.end_points for sub, m in self._modules[name].named_modules() if isinstance(m, Unit3D) and m.foldable]
+
+    def fold_batchnorm(self):
+        """Derive (w', b') = (w gamma / sqrt(var + eps), beta - mean gamma / sqrt(var + eps)) of every convolution -> BatchNorm3d -> ReLU layer of the feature extractor
+        (fp64 on the parameters' device, rounded once).  Eval mode only.  extract_features then issues no BatchNorm launch, no torch.cat and -- after the first call,
+        which fills the per-layer operand cache (concatenated reduction filters, halo / packed filter banks, the stem's constants) -- no pack launch.  train(),
+        load_state_dict(), a device / dtype move and an in-place change of a source tensor (torch's version counters) drop the fold and its cache."""
+        if self.training:
+            raise RuntimeError('fold_batchnorm() is for inference: call .eval() first (in training mode BatchNorm uses batch statistics and cannot be folded)')
+        from ...efficientnet.model import fold_conv_bn
+        units = self._foldable_units()
+        src = [t for _, u in units for t in (u.conv3d.weight, u.bn.weight, u.bn.bias, u.bn.running_mean, u.bn.running_var)]
+        self._folded = ({path: list(fold_conv_bn(u.conv3d.weight, u.bn)) + [{}] for path, u in units}, src, [t._version for t in src])
+        return self
+
+    def unfold_batchnorm(self):
+        self._folded = None
+
+    @property
+    def batchnorm_folded(self):
+        """True while extract_features runs on folded operands; a source tensor changed in place since fold_batchnorm() drops the fold here"""
+        f = self._folded
+        if f is not None and (self.training or any(t._version != v for t, v in zip(f[1], f[2]))):
+            self._folded = f = None
+        return f is not None
+
+    def train(self, mode=True):
+        if mode:
+            self._folded = None
+        return super().train(mode)
+
+    def _apply(self, fn, *args, **kwargs):
+        self._folded = None                # .to() / .cuda() / .float(): the derived tensors would stay behind
+        return super()._apply(fn, *args, **kwargs)
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        self._folded = None                # reached from load_state_dict() of this module and of any module that contains it
+        return super()._load_from_state_dict(*args, **kwargs)
+
+    def folded_operands(self, path):
+        """[w', b', ops] of one Unit3D of the folded extractor by its module path ('Conv3d_1a_7x7', 'Mixed_3b.b1b'; ops: the layer's operand cache)"""
+        return self._folded[0][path]
+
+    def folded_stem_bridge(self, batch, bridge_weight, bridge_bias, space_to_depth):
+        """relu(bn(Conv3d_1a_7x7(in_bridge_to3(batch)))) of the folded model with the 4 -> 3 input bridge composed into the stem (Segtran3d.fuse_input_bridge).
+        space_to_depth: the stride-(2, 2, 1) form -- the folded filters carry the BatchNorm factor, the bridge's bias map carries it too and the BatchNorm's folded
+        bias on top; one convolution and ONE pass y = relu(y + map).  Else the 8-channel stride-2 form with a per-channel bias in the convolution's epilogue.  The
+        composed constants live in the stem's operand cache (the bias map per input extent) and are rebuilt when the bridge's tensors change."""
+        stem = self.Conv3d_1a_7x7
+        w, b, ops = self.folded_operands('Conv3d_1a_7x7')
+        key = (id(bridge_weight), bridge_weight._version, id(bridge_bias), bridge_bias._version)
+        if ops.get('bridge_key') != key:
+            ops.clear()
+            ops['bridge_key'] = key
+        with torch.no_grad():
+            if space_to_depth:
+                if 's2d' not in ops:
+                    ops['s2d'] = SF.stem_s2d_folded_operands(w, bridge_weight.detach(), bridge_bias.detach(), b) + ({}, {})
+                w2, v, bias, conv_ops, maps = ops['s2d']
+                B, Cb, H, W, D = batch.shape
+                if (D, H, W) not in maps:
+                    maps[(D, H, W)] = SF.stem_s2d_bias_map(v, bias, D, H, W)
+                return SF.stem_bridge_conv_s2d_folded(batch, w2, maps[(D, H, W)], ops=conv_ops)
+            if 'composed' not in ops:
+                ops['composed'] = (SF.stem_compose(w, bridge_weight.detach(), bridge_bias.detach(), 8), {})
+            wc, conv_ops = ops['composed']
+            return SF.conv3d_bias_relu(SF.bridge_input(batch, 8), wc, b, stem._stride, ops=conv_ops)
+
+    def _extract_features_folded(self, x, stem_out=None):
+        """stem_out: the stem layer's OUTPUT (after BatchNorm and ReLU) computed by the caller (folded_stem_bridge); `x` is then not read"""
+        feat, L = {}, self._folded[0]
+        with torch.no_grad():
+            for name in self.VALID_ENDPOINTS:
+                if name not in self.end_points:
+                    continue
+                m = self._modules[name]
+                if name == 'Conv3d_1a_7x7' and stem_out is not None:
+                    x = stem_out
+                elif isinstance(m, Unit3D):
+                    x = m.forward_folded(x, L[name])
+                elif isinstance(m, InceptionModule):
+                    x = m.forward_folded(x, [L[name + '.' + b] for b in ('b0', 'b1a', 'b1b', 'b2a', 'b2b', 'b3b')])
+                else:
+                    x = m(x)                                    # the pools (Identity without do_pool1); the pyramid reads feat[prev] as it is
+                feat[name] = x
+        return feat

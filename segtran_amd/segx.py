@@ -33,7 +33,7 @@ class GemmDesc(ctypes.Structure):
                 ('b_planes', c_p), ('bp_b0', c_l), ('bp_b1', c_l), ('resid', c_p)]
 
 
-EPI_NONE, EPI_GELU, EPI_SWISH = 0, 1, 2
+EPI_NONE, EPI_GELU, EPI_SWISH, EPI_RELU = 0, 1, 2, 3
 (TILE_AUTO, TILE_128x128, TILE_64x64, TILE_128x32, TILE_32x128, TILE_64x128, TILE_256x128, TILE_WS128x128, TILE_WS128x256, TILE_WS64x256,
  TILE_WS96x256, TILE_WS256x96, TILE_SKINNY_NT) = range(13)
 BIAS_NONE, BIAS_N, BIAS_M = 0, 1, 2
@@ -661,6 +661,19 @@ class SegxLib:
         rc = self._timed(Y, 2.0 * B * Cout * P * K, ('conv3d_fwd', Cout, P, K, B, splitk), call)
         self.check(rc, 'segx_conv3d_fwd')
 
+    def conv3d_fwd_bias_act(self, X, W, bias, Y, B, Cout, geom, splitk=1, ws=None, packed=False, x_bs=0, y_bs=0, act=2):
+        """Y = act(conv3d_fwd(X, W) + bias[co]) (act 0 none / 2 ReLU): a convolution with its BatchNorm folded in; routed like conv3d_fwd (conv3d_route answers for it)"""
+        self._chk_t(X, W, bias, Y, ws)
+        P = geom[4] * geom[5] * geom[6]; K = geom[0] * geom[7] * geom[8] * geom[9]
+        call = lambda: self.c.segx_conv3d_fwd_bias_act(_ptr(X), _ptr(W), _ptr(bias), _ptr(Y), B, Cout, self._geom(geom), splitk, _ptr(ws), int(bool(packed)), int(x_bs), int(y_bs),
+                                                       int(act), self.stream(Y))
+        rc = self._timed(Y, 2.0 * B * Cout * P * K, ('conv3d_fwd', Cout, P, K, B, splitk), call)
+        self.check(rc, 'segx_conv3d_fwd_bias_act')
+
+    def bias_map_relu(self, Y, bmap, B, n):
+        """Y[b] = max(Y[b] + bmap, 0) in place over n floats per sample (the folded space-to-depth stem)"""
+        self._call('segx_bias_map_relu', Y, Y, bmap, B, n)
+
     # ---- 3 x 3 x 3 stride-1 'same' convolutions with an LDS-resident halo (conv3d_halo.hip, r06) ----
     def conv3d_halo_ok(self, B, Cout, geom):
         return bool(self.c.segx_conv3d_halo_ok(B, Cout, self._geom(geom)))
@@ -677,6 +690,14 @@ class SegxLib:
         call = lambda: self.c.segx_conv3d_halo_fwd(_ptr(X), _ptr(Wq), _ptr(Y), B, Cout, self._geom(geom), int(x_bs), int(y_bs), int(mtile), self.stream(Y))
         rc = self._timed(Y, 2.0 * B * Cout * P * K, ('conv3d_halo_fwd', Cout, P, K, B, 1), call)
         self.check(rc, 'segx_conv3d_halo_fwd')
+
+    def conv3d_halo_bias_act_fwd(self, X, Wq, bias, Y, B, Cout, geom, x_bs=0, y_bs=0, mtile=0, act=2):
+        """conv3d_halo_fwd with bias[co] and ReLU in the store loop (a 3 x 3 x 3 convolution with its BatchNorm folded in)"""
+        self._chk_t(X, Wq, bias, Y)
+        P = geom[4] * geom[5] * geom[6]; K = geom[0] * 27
+        call = lambda: self.c.segx_conv3d_halo_bias_act_fwd(_ptr(X), _ptr(Wq), _ptr(bias), _ptr(Y), B, Cout, self._geom(geom), int(x_bs), int(y_bs), int(mtile), int(act), self.stream(Y))
+        rc = self._timed(Y, 2.0 * B * Cout * P * K, ('conv3d_halo_fwd', Cout, P, K, B, 1), call)
+        self.check(rc, 'segx_conv3d_halo_bias_act_fwd')
 
     def conv3d_halo_wgrad_ok(self, B, Cout, geom):
         return bool(self.c.segx_conv3d_halo_wgrad_ok(B, Cout, self._geom(geom)))
@@ -805,7 +826,7 @@ _SIGS = {
     'segx_surface_border': 'ppliiiip', 'segx_edt_sq': 'ppliiip', 'segx_surface_hist': 'pppliiiip',
     'segx_ccl2d': 'pippliip', 'segx_frag_keep2': 'ppliip', 'segx_frag_apply': 'ppppliiip', 'segx_row_extent': 'ppliifp', 'segx_nhot_to_values': 'ppplilp',
     'segx_conv3d_fwd': 'pppiipipp', 'segx_conv3d_fwd_packed': 'pppiipipp', 'segx_conv3d_fwd_packed_bs': 'pppiipipllp', 'segx_conv3d_bwd_weight_packed_bs': 'pppiipipllp', 'segx_conv3d_pack_weights': 'ppiiiip', 'segx_conv3d_splitk': 'iipi', 'segx_conv3d_route': 'iipiiiip', 'segx_conv3d_fwd_terms': 'iipiii', 'segx_conv3d_flip_weights': 'ppiiip', 'segx_conv3d_bwd_weight': 'pppiipipp', 'segx_conv3d_bwd_weight_packed': 'pppiipipp', 'segx_conv3d_unpack_wgrad': 'ppiiip',
-    'segx_conv3d_halo_ok': 'iip', 'segx_conv3d_halo_wq_floats': 'ii', 'segx_conv3d_halo_pack': 'ppiiip', 'segx_conv3d_halo_fwd': 'pppiipllip', 'segx_conv3d_halo_wgrad_ok': 'iip', 'segx_conv3d_halo_wgrad_ws_floats': 'iip', 'segx_conv3d_halo_wgrad': 'ppppiipllp',
+    'segx_conv3d_halo_ok': 'iip', 'segx_conv3d_halo_wq_floats': 'ii', 'segx_conv3d_halo_pack': 'ppiiip', 'segx_conv3d_halo_fwd': 'pppiipllip', 'segx_conv3d_halo_bias_act_fwd': 'ppppiiplliip', 'segx_conv3d_fwd_bias_act': 'ppppiipipillip', 'segx_bias_map_relu': 'ppilp', 'segx_conv3d_halo_wgrad_ok': 'iip', 'segx_conv3d_halo_wgrad_ws_floats': 'iip', 'segx_conv3d_halo_wgrad': 'ppppiipllp',
     'segx_conv3d_bwd_data_direct': 'ppppiipp', 'segx_nonzero_mask': 'ppiiiiiiiip', 'segx_label_nhot': 'ppiilip',
     'segx_maxpool3d_fwd': 'ppplpp', 'segx_maxpool3d_bwd': 'ppplppp',
     'segx_bn_ws_floats': 'iil', 

@@ -6,6 +6,10 @@ One process: for every configuration (its BASELINE batch) the SAME model runs th
 forward timed with HIP events on the launch stream; the medians and their ratio are reported.  Then test_single_batch (sliding-window inference) on a 576 x 576 image
 with the cfg1 model, the same way.  Output: ONE JSON line.  The unfolded forward is the path every earlier commit ran, so the ratio needs no second box.
 
+  --3d    the 3-D models instead (BatchNorm3d folded into the I3D backbone's kernels, infer3d.fold_batchnorm): cfg4 112 x 112 x 96 and cfg5 128^3 at batch 4
+          and batch 1, each six-term and under inference_precision('bf16x3'); per case the median and quartiles of `reps` alternating forwards of one model after
+          `warmup` pairs (every switch of variant is followed by one untimed forward: a new fold fills its operand cache at its first call), and the device launches of one forward of each variant (torch.profiler, after the timing).  Written to --out
+          (profiles/fold_infer_bench_3d.json) and printed as one JSON line.
   --once cfgN:folded|unfolded   run ONE warm eval forward of one variant and exit (for a kernel trace: rocprofv3 --kernel-trace --stats -- python tools/infer_bench.py --once cfg2:folded)
 """
 import argparse
@@ -44,8 +48,73 @@ def alternate(net, run, reps, warmup):
     return statistics.median(ms[False]), statistics.median(ms[True])
 
 
+def count_kernels(fn):
+    """device kernels of one call (None where the profiler is not usable)"""
+    try:
+        from torch.profiler import profile, ProfilerActivity
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        return sum(1 for e in prof.events() if str(e.device_type).endswith('CUDA'))
+    except Exception as exc:                                   # a figure for the report, not a measurement the ratios rest on
+        print('launch count unavailable: %r' % (exc,), file=sys.stderr)
+        return None
+
+
+def _quartiles(v):
+    q1, q2, q3 = statistics.quantiles(v, n=4)
+    return [round(q1, 4), round(q2, 4), round(q3, 4)]
+
+
+def main_3d(a):
+    """the 3-D cases: one model per (configuration, batch); unfolded and folded forwards take turns inside each precision"""
+    from segtran_amd import infer3d
+    dev = torch.device('cuda', 0)
+    out = {'tool': 'infer_bench --3d', 'device': torch.cuda.get_device_name(0), 'reps': a.reps, 'warmup': a.warmup, 'cases': {}}
+    for name in a.cfgs.split(','):
+        c = engine.CONFIGS[name]
+        for batch in (c['bs'], 1):
+            net = engine.build_model(name, dev, dropout_prob=0.0).eval()
+            x, _ = engine.synth_batch(name, batch, dev)
+
+            def run():
+                net(x)
+            for precision in ('fp32', 'bf16x3'):
+                ms = {False: [], True: []}
+                with torch.no_grad(), infer3d.inference_precision(precision):
+                    for i in range(a.warmup + a.reps):
+                        for folded in (False, True):
+                            (infer3d.fold_batchnorm if folded else infer3d.unfold_batchnorm)(net)
+                            run()                               # untimed: the first forward after a fold fills its per-layer operand cache (unfolding drops it)
+                            t = timed(run)
+                            if i >= a.warmup:
+                                ms[folded].append(t)
+                    launches = {}
+                    for folded in (False, True):
+                        (infer3d.fold_batchnorm if folded else infer3d.unfold_batchnorm)(net)
+                        run()                                   # (a fresh fold: the first call fills its operand cache)
+                        launches[folded] = count_kernels(run)
+                    infer3d.unfold_batchnorm(net)
+                qu, qf = _quartiles(ms[False]), _quartiles(ms[True])
+                out['cases']['%s_b%d_%s' % (name, batch, precision)] = {
+                    'batch': batch, 'size': list(c['size']), 'precision': precision, 'unfolded_ms_q1_median_q3': qu, 'folded_ms_q1_median_q3': qf,
+                    'folded_over_unfolded': round(qf[1] / qu[1], 4), 'quartiles_overlap': not (qf[2] < qu[0] or qu[2] < qf[0]),
+                    'unfolded_launches': launches[False], 'folded_launches': launches[True]}
+                print(name, batch, precision, out['cases']['%s_b%d_%s' % (name, batch, precision)], file=sys.stderr, flush=True)
+            del net
+            torch.cuda.empty_cache()
+    line = json.dumps(out)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            f.write(json.dumps(out, indent=1, sort_keys=True) + '\n')
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--3d', dest='three_d', action='store_true')
+    ap.add_argument('--out', default=None)
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--cfgs', default='cfg1,cfg2,cfg3')
@@ -53,12 +122,22 @@ def main():
     ap.add_argument('--once', default=None)
     a = ap.parse_args()
     assert a.reps >= 20 or a.once, 'the median is taken over at least 20 repetitions'
+    if a.three_d:
+        if a.cfgs == 'cfg1,cfg2,cfg3':
+            a.cfgs = 'cfg4,cfg5'
+        if a.out is None:
+            a.out = os.path.join('profiles', 'fold_infer_bench_3d.json')
+        return main_3d(a)
     dev = torch.device('cuda', 0)
     if a.once:
         name, variant = a.once.split(':')
         net = engine.build_model(name, dev, dropout_prob=0.0).eval()
         if variant == 'folded':
-            net.fold_batchnorm()
+            if engine.CONFIGS[name]['dim'] == 3:
+                from segtran_amd import infer3d
+                infer3d.fold_batchnorm(net)
+            else:
+                net.fold_batchnorm()
         x, _ = engine.synth_batch(name, engine.CONFIGS[name]['bs'], dev)
         with torch.no_grad():
             for _ in range(3):
