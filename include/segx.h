@@ -208,11 +208,12 @@ int segx_seg_loss_bwd(const float* logits, const float* mask, const float* pos_w
  * params/grads/m/v = arrays of device pointers [ntensors]; sizes [ntensors]; tensors cut into `chunk`-element chunks:
  * chunk_tensor/chunk_off [nchunks], chunk_first [ntensors+1] (chunks of a tensor are consecutive); active[t] = 0 for
  * parameters that never receive a gradient (N3: skipped, no weight decay).  ws: nchunks + 2*ntensors + 2 floats;
- * afterwards ws[nchunks + 2*ntensors] = global grad norm. */
+ * afterwards ws[nchunks + 2*ntensors] = global grad norm.  b1 / b2 are doubles: the moments are weighted by float(1 - b), the complement
+ * taken in double as the reference takes it (1 - float(0.999) is off by 1.3e-5 of itself). */
 int segx_mt_bertadam_step(void* const* params, const void* const* grads, void* const* m, void* const* v, const int64_t* sizes,
                           const int* chunk_tensor, const int64_t* chunk_off, const int* chunk_first, const int* active,
                           const float* lr, const float* wd, int ntensors, int nchunks, int chunk,
-                          float max_global_norm, float max_tensor_norm, float sched, float b1, float b2, float eps,
+                          float max_global_norm, float max_tensor_norm, float sched, double b1, double b2, float eps,
                           float* ws, void* stream);
 
 /* Multi-tensor gather (data parallel): copies chunks [chunk_begin, chunk_begin + nchunks) of the tensors src[t] (this step's

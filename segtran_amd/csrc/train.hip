@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) void mt_clipcoef_kernel(const float* __restric
 }
 __global__ __launch_bounds__(256) void mt_bertadam_kernel(MtTables T, int chunk, const float* __restrict__ coef, const float* __restrict__ lr,
                                                           const float* __restrict__ wd, const int* __restrict__ active,
-                                                          float sched, float b1, float b2, float eps) {
+                                                          float sched, float b1, float b2, float omb1, float omb2, float eps) {
     const int ch = blockIdx.x, t = T.chunk_tensor[ch];
     if (!active[t]) return;                               // `if p.grad is None: continue` (optimization.py:100-101)
     const int64_t off = T.chunk_off[ch], n = i64min(chunk, T.sizes[t] - off);
@@ -152,8 +152,8 @@ __global__ __launch_bounds__(256) void mt_bertadam_kernel(MtTables T, int chunk,
     // one element of the update (optimization.py:104-130); the same arithmetic in the 16-byte and the scalar loop
     auto upd1 = [&](float gi, float& mi, float& vi, float& pi) {
         gi *= c;
-        mi = mi * b1 + (1.0f - b1) * gi;
-        vi = vi * b2 + (1.0f - b2) * gi * gi;
+        mi = mi * b1 + omb1 * gi;
+        vi = vi * b2 + omb2 * gi * gi;
         float upd = mi / (sqrtf(vi) + eps);
         if (decay > 0.f) upd += decay * pi;
         pi = pi - step * upd;
@@ -233,7 +233,7 @@ extern "C" int segx_mt_gather(const void* const* src, void* const* dst, const in
 extern "C" int segx_mt_bertadam_step(void* const* params, const void* const* grads, void* const* m, void* const* v, const int64_t* sizes,
                                      const int* chunk_tensor, const int64_t* chunk_off, const int* chunk_first, const int* active,
                                      const float* lr, const float* wd, int ntensors, int nchunks, int chunk,
-                                     float max_global_norm, float max_tensor_norm, float sched, float b1, float b2, float eps,
+                                     float max_global_norm, float max_tensor_norm, float sched, double b1, double b2, float eps,
                                      float* ws /* nchunks + 2*ntensors + 2 floats */, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     SEGX_REQUIRE(params && grads && m && v && sizes && chunk_tensor && chunk_off && chunk_first && active && lr && wd && ws,
@@ -244,6 +244,7 @@ extern "C" int segx_mt_bertadam_step(void* const* params, const void* const* gra
     hipLaunchKernelGGL(mt_sumsq_kernel, dim3(nchunks), dim3(256), 0, stream, T, chunk, chunk_ws);
     hipLaunchKernelGGL(mt_clipcoef_kernel, dim3(1), dim3(256), 0, stream, (const float*)chunk_ws, chunk_first, active, ntensors,
                        max_global_norm, max_tensor_norm, tnorm, coef, stats);
-    hipLaunchKernelGGL(mt_bertadam_kernel, dim3(nchunks), dim3(256), 0, stream, T, chunk, (const float*)coef, lr, wd, active, sched, b1, b2, eps);
+    hipLaunchKernelGGL(mt_bertadam_kernel, dim3(nchunks), dim3(256), 0, stream, T, chunk, (const float*)coef, lr, wd, active, sched, (float)b1,
+                       (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), eps);     // 1 - b in double, then rounded (optimization.py:125-126): 1.0f - 0.999f is 1.3e-5 off 0.001f
     return check_launch("segx_mt_bertadam_step");
 }

@@ -98,7 +98,7 @@ class SegxLib:
         self.emulated = 'emu' in os.path.basename(path)
         self.force_tile = None           # tools/gemm_bench.py: override the library's tile choice
         self.gemm_prof = None            # bench.py: list of (start_event, end_event, flops) per GEMM launch
-        kinds = {'p': c_p, 'i': c_i, 'l': c_l, 'f': c_f, 'u': c_u}
+        kinds = {'p': c_p, 'i': c_i, 'l': c_l, 'f': c_f, 'd': ctypes.c_double, 'u': c_u}
         for name, sig in _SIGS.items():
             fn = getattr(self.c, name)
             fn.argtypes = [kinds[k] for k in sig]
@@ -799,7 +799,7 @@ class SegxLib:
                    chunk_begin, nchunks, chunk)
 
 
-# C signatures (include/segx.h): p pointer, i int32, l int64, f float, u uint64; trailing p = stream
+# C signatures (include/segx.h): p pointer, i int32, l int64, f float, d double, u uint64; trailing p = stream
 _SIGS = {
     'segx_posbias_fwd': 'ppplipffpp', 'segx_posbias_bwd': 'pppplipffp',
     'segx_softmax_fwd': 'ppplifpfuup', 'segx_softmax_bwd': 'pppplifpfuup',
@@ -814,7 +814,7 @@ _SIGS = {
     'segx_modes_aggr_param_grad': 'pppppppppppilifuup', 'segx_gelu_bwd': 'ppplfuup',
     'segx_gelu_bwd_colsum': 'ppppplifuup', 'segx_gelu_bwd_colsum_ws_floats': 'li', 'segx_modes_aggr_bwd_all_ws_floats': 'ili', 'segx_modes_aggr_bwd_all': 'ppppppppppppilifuup',
     'segx_loss_ws_floats': 'ii', 'segx_seg_loss_fwd': 'ppppppiilfp', 'segx_seg_loss_bwd': 'pppppppiilfp',
-    'segx_mt_bertadam_step': 'pppppppppppiiiffffffpp', 'segx_mt_gather': 'pppppiiip',
+    'segx_mt_bertadam_step': 'pppppppppppiiifffddfpp', 'segx_mt_gather': 'pppppiiip',
     'segx_gn_ws_floats': 'iii', 'segx_groupnorm_fwd': 'pppppppiiilfp', 'segx_groupnorm_bwd': 'pppppppppiiilpp',
     'segx_interp_gn_nparts': 'li', 'segx_interp_linear_fwd_axis2_gn': 'pppliiiilipip', 'segx_groupnorm_fwd_parts': 'ppipppppiiilfp',
     'segx_groupnorm_stats_parts': 'pippifp', 'segx_gn_fold_bwd': 'pppppppppiiilp', 'segx_bridge_mask': 'ppppiiiiiiiiip', 'segx_gn_fold_bwd_proj': 'ppippppppppiiilp',

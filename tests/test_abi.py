@@ -20,6 +20,7 @@ def _declared():
             elif prm.startswith('int64_t'): sig += 'l'
             elif prm.startswith('uint64_t'): sig += 'u'
             elif prm.startswith('float'): sig += 'f'
+            elif prm.startswith('double'): sig += 'd'
             elif prm.startswith('int'): sig += 'i'
             else: sig += '?'
         out[name] = sig

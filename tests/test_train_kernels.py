@@ -1,4 +1,5 @@
-"""CPU: fused loss + multi-tensor BertAdam kernels on the emulator vs the golden fixtures from the reference."""
+"""Fused loss + multi-tensor BertAdam kernels vs the golden fixtures from the reference: on the fiber emulator and, under -m gpu, on the device
+(the `backend` fixture).  tests/test_train_kernels_sizes.py checks the same kernels against fp64 at the sizes where their loops split."""
 import pytest
 import torch
 from segtran_amd import segx
