@@ -321,6 +321,23 @@ int64_t segx_dwconv2d_wgrad_rows(int OH, int OW);
 int64_t segx_dwconv2d_bwd_fused_rows(int H, int Wd, int OH, int OW, int k, int stride, int pad_t, int pad_l);
 int segx_dwconv2d_bwd_fused(const float* dY, const float* X, const float* W, float* dX, float* part, int B, int C, int H, int Wd, int OH, int OW,
                             int k, int stride, int pad_t, int pad_l, void* stream);
+/* The channel-resident MIDDLE of a stride-1 MBConv block in training mode (efficientnet/model.py:96-106; mbconv_mid.hip): BatchNorm0 + swish, the k x k depthwise 'same'
+ * convolution (zero padding k / 2 on every side) and BatchNorm1 + swish + the squeeze-excite pooling sums in ONE launch, one workgroup per channel; the backward likewise.
+ * segx_mbconv_mid_ok: 1 where the pair serves the shape (1 <= B <= 6, W % 4 == 0, H * W in {1024, 4096}, k in {3, 5}), else 0 -- the callers then keep segx_bn_act_fwd2 /
+ * segx_dwconv2d_fwd / segx_bn_act_fwd2 and their backwards.
+ * fwd: E [B,C,H,W] is the expansion's output.  Writes D (the convolution's output, saved for backward), Y = swish(BatchNorm1(D)), psum[b * C + c] = sum of Y over the plane (ONE
+ *      chunk per plane: segx_se_fwd2 with nch = 1), the batch statistics mean0 / var0 / mean1 / var1 [C] (biased variance) and updates both running statistics (unbiased variance;
+ *      NULL pair: no update).  swish(BatchNorm0(E)) is never written: the backward recomputes it from E.  Results bit-identical to the three calls named above.
+ * bwd: dY = gradient w.r.t. Y; dpool [B*C] (required): dpool[b][c] * inv_S is added to it (the pooling's gradient, as in segx_bn_act_bwd2 without gate).  Writes dE, the BatchNorm
+ *      parameter gradients dw0 / db0 / dw1 / db1 [C] and the complete filter gradient dWdw [C][k*k].  All tensors 16-byte aligned. */
+int segx_mbconv_mid_ok(int B, int C, int H, int W, int k);
+int segx_mbconv_mid_fwd(const float* E, const float* w0, const float* b0, float* run_mean0, float* run_var0, const float* Wdw, const float* w1, const float* b1,
+                        float* run_mean1, float* run_var1, float* D, float* Y, float* psum, float* mean0, float* var0, float* mean1, float* var1,
+                        float momentum0, float eps0, float momentum1, float eps1, int B, int C, int H, int W, int k, void* stream);
+int segx_mbconv_mid_bwd(const float* dY, const float* dpool, const float* D, const float* E, const float* mean0, const float* var0, const float* mean1,
+                        const float* var1, const float* w0, const float* b0, const float* w1, const float* b1, const float* Wdw,
+                        float* dE, float* dw0, float* db0, float* dw1, float* db1, float* dWdw, float inv_S, float eps0, float eps1,
+                        int B, int C, int H, int W, int k, void* stream);
 /* r04: the weight gradient dW [C][k*k] in ONE launch where a channel's B planes are one workgroup's work (B <= 8, <= 8192 outputs per plane, the float4
  * layout): returns 1 when done, 0 when the shape needs the two-stage form above (nothing launched), < 0 on error */
 int segx_dwconv2d_bwd_weight_direct(const float* dY, const float* X, float* dW, int B, int C, int H, int Wd, int OH, int OW, int k,

@@ -11,19 +11,7 @@
 
 namespace segx {
 
-enum { ACT_NONE = 0, ACT_SWISH = 1, ACT_RELU = 2, ACT_LEAKY = 3 /* nn.LeakyReLU(0.2): the domain discriminator, networks/discriminator.py:14-21 */ };
-
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + __expf(-x)); }
-__device__ __forceinline__ float act_fwd(float u, int act) {
-    return act == ACT_SWISH ? u * sigm(u) : act == ACT_RELU ? fmaxf(u, 0.f) : act == ACT_LEAKY ? (u > 0.f ? u : 0.2f * u) : u;
-}
-// d act(u) / du   (swish: efficientnet/utils.py:64-79)
-__device__ __forceinline__ float act_grad(float u, int act) {
-    if (act == ACT_SWISH) { const float s = sigm(u); return s * (1.0f + u * (1.0f - s)); }
-    if (act == ACT_RELU) return u > 0.f ? 1.0f : 0.f;
-    if (act == ACT_LEAKY) return u > 0.f ? 1.0f : 0.2f;
-    return 1.0f;
-}
+// (the activations act_fwd / act_grad live in common.h: mbconv_mid.hip applies the same ones)
 
 // per-sample drop_connect scale (efficientnet/utils.py:129-154: floor(keep + U[0,1)) / keep): element `sample` of the Philox stream (seed, offset)
 __device__ __forceinline__ float drop_connect_scale(float p, uint64_t seed, uint64_t offset, const uint64_t* __restrict__ rbase, int sample) {

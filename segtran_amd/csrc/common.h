@@ -206,6 +206,21 @@ template <int NW> __device__ __forceinline__ float block_max(float v, float* red
     return s;
 }
 
+// ---- activations of the backbone kernels (backbone.hip, mbconv_mid.hip) --------------------------
+enum { ACT_NONE = 0, ACT_SWISH = 1, ACT_RELU = 2, ACT_LEAKY = 3 /* nn.LeakyReLU(0.2): the domain discriminator, networks/discriminator.py:14-21 */ };
+
+__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + __expf(-x)); }
+__device__ __forceinline__ float act_fwd(float u, int act) {
+    return act == ACT_SWISH ? u * sigm(u) : act == ACT_RELU ? fmaxf(u, 0.f) : act == ACT_LEAKY ? (u > 0.f ? u : 0.2f * u) : u;
+}
+// d act(u) / du   (swish: efficientnet/utils.py:64-79)
+__device__ __forceinline__ float act_grad(float u, int act) {
+    if (act == ACT_SWISH) { const float s = sigm(u); return s * (1.0f + u * (1.0f - s)); }
+    if (act == ACT_RELU) return u > 0.f ? 1.0f : 0.f;
+    if (act == ACT_LEAKY) return u > 0.f ? 1.0f : 0.2f;
+    return 1.0f;
+}
+
 // ---- Philox4x32-7 counter RNG (dropout masks are regenerated, never stored) -------------------
 // One call yields 4 x 32 random bits for elements 4*ctr .. 4*ctr+3 of stream (seed, offset).
 struct u32x4 { unsigned x, y, z, w; };

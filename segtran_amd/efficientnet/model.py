@@ -106,6 +106,18 @@ class MBConvBlock(nn.Module):
         self._bn2 = nn.BatchNorm2d(cout, momentum=BN_MOM, eps=BN_EPS)
 
     gate_in_weights = True     # False: the reference's op order (gate applied to the activation, model.py:110), as a separate pass
+    fused_middle = True        # _bn0 + swish, the depthwise convolution and _bn1 + swish + pooling as ONE channel-resident launch per direction where the library serves the
+                               # shape (stride-1 blocks with planes of 1024 / 4096 floats, batch <= 6: SF.mbconv_mid); False: the three ops everywhere (tools/ab_switch.py)
+
+    def _takes_fused_middle(self, x):
+        """training, one process (synchronised BatchNorm exchanges statistics between statistics and apply), an expansion, stride 1 with symmetric padding, a served shape"""
+        if not (MBConvBlock.fused_middle and MBConvBlock.gate_in_weights and self.training and SF._bn_stats_sync is None and self.expand_ratio != 1):
+            return False
+        dw = self._depthwise_conv
+        k = dw.kernel_size[0]
+        if not (self._bn0.training and self._bn1.training and dw.stride == (1, 1) and dw.kernel_size == (k, k) and tuple(dw.static_pad) == (k // 2,) * 4):
+            return False
+        return x.dim() == 4 and x.dtype == torch.float32 and SF.mbconv_mid_ok((x.shape[0], dw.in_channels, x.shape[2], x.shape[3]), k)
 
     def folded_operands(self):
         """(w0, b0) | None, (w1, b1), (w2, b2): expansion / depthwise / projection convolution with _bn0 / _bn1 / _bn2 folded in (EfficientNet.fold_batchnorm)"""
@@ -130,7 +142,8 @@ class MBConvBlock(nn.Module):
         """efficientnet/model.py:82-126"""
         x = skip_in = inputs
         skip = self.stride == 1 and self.input_filters == self.output_filters
-        if self.expand_ratio != 1:
+        fused = self._takes_fused_middle(x)
+        if self.expand_ratio != 1 and not fused:
             # (`inputs` has two consumers when there is a skip connection.  Routing the second through the GEMM op's input alias -- its gradient added
             # inside the expansion's dX GEMM, SF.conv1x1(pass_input=True), what the Inception modules do -- was measured here, r04_d: the residual keeps
             # those dX GEMMs off the wave-specialised tiles, +0.40 ms/step of GEMM time against 0.24 ms of accumulation adds saved.  Not used.)
@@ -139,7 +152,10 @@ class MBConvBlock(nn.Module):
         # drop_connect (utils.py:129-154, per-sample stochastic depth) and the skip add ride on the last BatchNorm pass: the sample's keep scale is
         # drawn inside the kernels from the library's Philox stream (H3: the reference's torch.rand stream cannot be matched anyway)
         rate = float(drop_connect_rate) if (skip and drop_connect_rate and self.training) else 0.0
-        if MBConvBlock.gate_in_weights:
+        if fused:
+            y, Wb = SF.mbconv_mid(self._expand_conv(x), self._bn0, self._depthwise_conv.weight, self._bn1, *se, self._project_conv.weight)
+            x = SF.conv1x1_per_sample(y, Wb)
+        elif MBConvBlock.gate_in_weights:
             # squeeze-excite gate folded into the projection weights (per-sample weights; the gated tensor is never written)
             y, Wb = SF.bn_act_gate_weights(self._depthwise_conv(x), self._bn1, SF.ACT_SWISH, *se, self._project_conv.weight)
             x = SF.conv1x1_per_sample(y, Wb)

@@ -1151,6 +1151,61 @@ def bn_act_gate_weights(x, bn, act, w1, b1, w2, b2, proj_weight):
                              proj_weight)
 
 
+class _MBConvMid(_Fn):
+    """The middle of a stride-1 MBConv block in training mode as ONE op: (y, Wb) = _BNActGateW(dwconv2d(_BNAct(e, bn0, swish)), bn1, swish, squeeze-excite, W_project)
+    with the three tensor ops in one launch per direction (segx_mbconv_mid_fwd / _bwd: one workgroup owns a channel; 3 + 4 passes over the expanded tensor instead
+    of 6 + 10).  Saved for backward: e, the convolution's output d and the four statistics; swish(bn0(e)) is recomputed.  Only for shapes segx_mbconv_mid_ok
+    accepts and one process (synchronised BatchNorm exchanges statistics between the launches' halves): MBConvBlock.forward routes."""
+
+    @staticmethod
+    def forward(ctx, e, w0, b0, rm0, rv0, mom0, eps0, wdw, w1, b1, rm1, rv1, mom1, eps1, sw1, sb1, sw2, sb2, Wproj):
+        L = segx.lib()
+        e, wdw = _c(e), _c(wdw)
+        if e.data_ptr() % 16:
+            e = e.clone()
+        B, C, H, W = e.shape
+        k, S = wdw.shape[-1], H * W
+        Wp = _c(Wproj.reshape(Wproj.shape[0], C))
+        d, y = torch.empty_like(e), torch.empty_like(e)
+        psum, stats = _empty(e, B * C), _empty(e, 4, C)                # stats: mean0, var0, mean1, var1
+        L.mbconv_mid_fwd(e, w0, b0, rm0, rv0, wdw, w1, b1, rm1, rv1, d, y, psum, stats[0], stats[1], stats[2], stats[3], mom0, eps0, mom1, eps1, B, C, H, W, k)
+        p, hpre, gate, W1, W2, Wb = _se_excite(L, y, psum, 1, S, sw1, sb1, sw2, sb2, Wp)
+        ctx.cfg = (B, C, H, W, k, eps0, eps1)
+        ctx.shapes = (tuple(sw1.shape), tuple(sw2.shape), tuple(Wproj.shape), tuple(wdw.shape))
+        ctx.save_for_backward(e, d, stats, w0, b0, wdw, w1, b1, p, hpre, gate, W1, W2, Wp)
+        return y, Wb
+
+    @staticmethod
+    def backward(ctx, dy, dWb):
+        L = segx.lib()
+        e, d, stats, w0, b0, wdw, w1, b1, p, hpre, gate, W1, W2, Wp = ctx.saved_tensors
+        B, C, H, W, k, eps0, eps1 = ctx.cfg
+        w1s, w2s, wps, wds = ctx.shapes
+        dWb = _c(dWb) if dWb is not None else torch.zeros(B, Wp.shape[0], C, dtype=torch.float32, device=e.device)
+        dy = _c(dy) if dy is not None else torch.zeros_like(e)
+        if dy.data_ptr() % 16:
+            dy = dy.clone()
+        dpool, dW1, db1, dW2, db2, dWp = _se_excite_backward(L, e, dWb, Wp, None, gate, hpre, p, W1, W2, H * W)
+        de, g, dwd = torch.empty_like(e), _empty(e, 4, C), _empty(e, C * k * k)       # g: dw0, db0, dw1, db1
+        L.mbconv_mid_bwd(dy, dpool, d, e, stats[0], stats[1], stats[2], stats[3], w0, b0, w1, b1, wdw, de, g[0], g[1], g[2], g[3], dwd, 1.0, eps0, eps1, B, C, H, W, k)
+        return (de, g[0], g[1], None, None, None, None, dwd.view(wds), g[2], g[3], None, None, None, None,
+                dW1.view(w1s), db1, dW2.view(w2s), db2, dWp.view(wps))
+
+
+def mbconv_mid_ok(e_shape, k):
+    """does the channel-resident op below serve an expanded tensor of this shape and a k x k stride-1 'same' depthwise convolution?"""
+    return len(e_shape) == 4 and segx.lib().mbconv_mid_ok(e_shape[0], e_shape[1], e_shape[2], e_shape[3], int(k))
+
+
+def mbconv_mid(e, bn0, dw_weight, bn1, w1, b1, w2, b2, proj_weight):
+    """(swish(bn1(dwconv(swish(bn0(e))))), per-sample projection weights carrying the squeeze-excite gate) -- see _MBConvMid; pair with conv1x1_per_sample.
+    Both BatchNorm modules are in training mode and mbconv_mid_ok(e.shape, k) holds (the caller checks)."""
+    _bn_tick(bn0)
+    _bn_tick(bn1)
+    return _MBConvMid.apply(e, bn0.weight, bn0.bias, bn0.running_mean, bn0.running_var, float(bn0.momentum), float(bn0.eps), dw_weight,
+                            bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var, float(bn1.momentum), float(bn1.eps), w1, b1, w2, b2, proj_weight)
+
+
 def conv1x1_per_sample(x, Wb, bias=None):
     """Pointwise convolution with one weight matrix per sample: y[b] = Wb[b] x[b] (+ bias[b])  (Wb [B, Cout, Cin], bias [B, Cout]); one batched GEMM, A strided
     over the batch."""

@@ -422,6 +422,18 @@ class SegxLib:
     def se_bwd2(self, dWb, Wproj, dgate, gate, hpre, p, W1, W2, inv_S, dpool, dW1, db1, dW2, db2, dWproj, ws, B, C, Cs, M):
         self._call('segx_se_bwd2', gate, dWb, Wproj, dgate, gate, hpre, p, W1, W2, inv_S, dpool, dW1, db1, dW2, db2, dWproj, ws, B, C, Cs, M)
 
+    def mbconv_mid_ok(self, B, C, H, W, k):
+        """does the channel-resident MBConv middle (mbconv_mid_fwd / mbconv_mid_bwd) serve this shape?"""
+        return bool(self.c.segx_mbconv_mid_ok(B, C, H, W, k))
+
+    def mbconv_mid_fwd(self, E, w0, b0, rm0, rv0, Wdw, w1, b1, rm1, rv1, D, Y, psum, mean0, var0, mean1, var1, mom0, eps0, mom1, eps1, B, C, H, W, k):
+        self._call('segx_mbconv_mid_fwd', E, E, w0, b0, rm0, rv0, Wdw, w1, b1, rm1, rv1, D, Y, psum, mean0, var0, mean1, var1, float(mom0), float(eps0), float(mom1), float(eps1),
+                   B, C, H, W, k)
+
+    def mbconv_mid_bwd(self, dY, dpool, D, E, mean0, var0, mean1, var1, w0, b0, w1, b1, Wdw, dE, dw0, db0, dw1, db1, dWdw, inv_S, eps0, eps1, B, C, H, W, k):
+        self._call('segx_mbconv_mid_bwd', dY, dY, dpool, D, E, mean0, var0, mean1, var1, w0, b0, w1, b1, Wdw, dE, dw0, db0, dw1, db1, dWdw, float(inv_S), float(eps0), float(eps1),
+                   B, C, H, W, k)
+
     def dwconv2d_fwd(self, X, W, Y, B, C, H, Wd, OH, OW, k, stride, pt, pl):
         self._call('segx_dwconv2d_fwd', X, X, W, Y, B, C, H, Wd, OH, OW, k, stride, pt, pl)
 
@@ -837,6 +849,7 @@ _SIGS = {
     'segx_plane_chunks': 'l', 'segx_bn_pool_chunks': 'ili', 'segx_bn_parts_floats': 'iil', 'segx_bn_stats_local': 'pppiilp',
     'segx_bn_act_fwd2': 'ppippppfpppppfuuiilfillp', 'segx_bn_act_bwd2': 'ppppppppppiilfiippffuullp',
     'segx_team_status': 'i', 'segx_team_cap': '', 'segx_occupy': 'iifpp',
+    'segx_mbconv_mid_ok': 'iiiii', 'segx_mbconv_mid_fwd': 'p' * 17 + 'ffff' + 'iiiii' + 'p', 'segx_mbconv_mid_bwd': 'p' * 19 + 'fff' + 'iiiii' + 'p',
     'segx_se_fwd2': 'pifpppppppppiiiip', 'segx_se_ws2_floats': 'iii', 'segx_se_bwd2': 'ppppppppfpppppppiiiip',
     'segx_bn_act_bwd_reduce': 'pppppppppiilfippffuup', 'segx_bn_act_bwd_apply': 'pppppppppiilfifppffuup',
 }
