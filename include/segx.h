@@ -685,6 +685,18 @@ int segx_edt_sq(const uint8_t* border, int32_t* d2, int64_t planes, int D, int H
  * counts): hist is int32 [planes][nbins], zeroed by the caller, nbins >= (D-1)^2 + (H-1)^2 + (W-1)^2 + 1; a voxel with k >= nbins (the sentinel) is not counted.
  * Integer atomic adds: the result does not depend on their order.  planes <= 65535. */
 int segx_surface_hist(const uint8_t* border_from, const int32_t* d2_to, int32_t* hist, int64_t planes, int D, int H, int W, int nbins, void* stream);
+/* The tail of one BraTS case (test_util3d.py:36-38, 67, 82-85) in one pass over the S voxels.  soft, hard: [4][S] as segx_window_merge / segx_harden_segmap leave them
+ * in mode 1 (bg, ET, WT, TC; plane 0 is not read); gt: [S] raw labels.
+ *   counts [3][3] (int32, initialised here): counts[c-1] = {sum pred * gt, sum pred, sum gt} for c = 1..3 with pred = hard[c] != 0 and gt = the n-hot map of
+ *     brats_map_label formed in registers: a raw 4 counts as 3; ET = label 3, WT = labels 1, 2, 3, TC = labels 1, 3; any other value sets no class.  Integer atomic
+ *     adds, one per counter per workgroup: exact and independent of the order of execution.
+ *   labels [S] (uint8): argmax_k inv[k] of brats_inv_map_label -- inv0 = 1 - soft2, inv1 = (soft3 - soft1) * 1.5f, inv2 = (soft2 - soft3) * 1.5f, inv3 = soft1 --
+ *     as torch.argmax takes it (the lowest index wins a tie, a NaN beats every number), a 3 written as 4.
+ * gt may be NULL when counts is; counts or labels may be NULL, not both.  0 < S < 2^31.  A thread takes four voxels per trip through 16-byte loads when S % 4 == 0 and
+ * the bases are 16-byte aligned (labels: 4), else through dword loads for the whole call.  No copy to the host, no synchronisation: the call can be captured. */
+#define SEGX_CASE_TAIL_THREADS 256        /* workgroup size; a workgroup covers 4 * SEGX_CASE_TAIL_THREADS voxels per trip: tests place their sizes by these */
+#define SEGX_CASE_TAIL_MAX_BLOCKS 2048    /* grid cap: above 4 * THREADS * MAX_BLOCKS voxels the grid-stride loop takes another trip */
+int segx_brats_case_tail(const float* soft, const float* hard, const int32_t* gt, int32_t* counts, uint8_t* labels, int64_t S, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Tail of the 2-D evaluation (components.hip): connected components, fragment removal (test_util2d.py:267-289), row extents for the vertical cup/disc ratio

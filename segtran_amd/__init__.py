@@ -20,4 +20,7 @@ def __getattr__(name):
     if name == 'GraphedSlidingWindow':          # infer2d.GraphedSlidingWindow: the whole sliding-window evaluation of one image shape as one replayable hipGraph
         from .infer2d import GraphedSlidingWindow
         return GraphedSlidingWindow
+    if name == 'GraphedSlidingWindow3d':        # infer3d.GraphedSlidingWindow3d: the same for one volume shape, with the BraTS case tail (label volume, metric counts)
+        from .infer3d import GraphedSlidingWindow3d
+        return GraphedSlidingWindow3d
     raise AttributeError('module %r has no attribute %r' % (__name__, name))

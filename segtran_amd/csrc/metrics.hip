@@ -5,6 +5,9 @@
 //                    one pass per axis, out[y] = min over y' of (f[y'] + (y - y')^2) over the WHOLE line -- O(extent) per voxel, no envelope bookkeeping, int32
 //   surface_hist     hist[plane][k] = number of border voxels of the other mask at squared distance k (integer atomic adds: order-independent, bit-reproducible)
 // The float64 finish (mean of sqrt(k) weighted by the counts, the 95th percentile from the cumulative counts) is a few lines on the host (infer3d.py).
+// And the tail of one BraTS case (test_util3d.py:36-38, 67, 82-85) in one pass over the voxels:
+//   brats_case_tail  counts[c-1] = {sum pred * gt, sum pred, sum gt} for the three foreground classes, the ground truth mapped from the raw labels in registers, and
+//                    labels = argmax(brats_inv_map_label(soft)) with 3 written as 4.  int32 counts through integer atomic adds: exact, order-independent.
 #include "common.h"
 
 namespace segx {
@@ -113,6 +116,104 @@ __global__ __launch_bounds__(256) void surface_hist_kernel(const uint8_t* __rest
         if (low[i]) atomicAdd(&h[i], low[i]);
 }
 
+constexpr int CT_THREADS = SEGX_CASE_TAIL_THREADS, CT_WAVES = CT_THREADS / 64;
+
+__global__ __launch_bounds__(64) void case_tail_init_kernel(int* __restrict__ counts) {
+    if (threadIdx.x < 9) counts[threadIdx.x] = 0;
+}
+
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// argmax over k of inv[k] as torch.argmax takes it: the lowest index wins a tie, a NaN beats every number (and the first NaN the later ones)
+__device__ __forceinline__ bool case_tail_beats(float v, float best) { return v > best || (v != v && best == best); }
+
+// soft / hard [4][S] (bg, ET, WT, TC; plane 0 is never read), gt [S] raw labels.  A thread owns four consecutive voxels per trip of the grid-stride loop.  VEC: S % 4 == 0
+// and every operand aligned for it, so a plane's quad is one 16-byte load and the four labels one 4-byte store; otherwise dword loads and byte stores, the last quad
+// cut at S.  counts == NULL: hard and gt are not read; labels == NULL: soft is not read (both conditions are the same in every thread of the grid).
+template <bool VEC>
+__global__ __launch_bounds__(CT_THREADS) void brats_case_tail_kernel(const float* __restrict__ soft, const float* __restrict__ hard, const int* __restrict__ gt,
+                                                                     int* __restrict__ counts, uint8_t* __restrict__ labels, int64_t S) {
+    __shared__ int red[CT_WAVES][9];
+    int i1 = 0, p1 = 0, g1 = 0, i2 = 0, p2 = 0, g2 = 0, i3 = 0, p3 = 0, g3 = 0;
+    const int64_t quads = (S + 3) >> 2;
+    for (int64_t q = (int64_t)blockIdx.x * CT_THREADS + threadIdx.x; q < quads; q += (int64_t)gridDim.x * CT_THREADS) {
+        const int64_t s = q << 2;
+        const int n = VEC ? 4 : (int)i64min(4, S - s);
+        if (counts) {
+            float h1[4] = {0.f, 0.f, 0.f, 0.f}, h2[4] = {0.f, 0.f, 0.f, 0.f}, h3[4] = {0.f, 0.f, 0.f, 0.f};
+            int g[4] = {0, 0, 0, 0};
+            if (VEC) {
+                const float4 a = *reinterpret_cast<const float4*>(hard + S + s), b = *reinterpret_cast<const float4*>(hard + 2 * S + s),
+                             c = *reinterpret_cast<const float4*>(hard + 3 * S + s);
+                const int4 l = *reinterpret_cast<const int4*>(gt + s);
+                h1[0] = a.x; h1[1] = a.y; h1[2] = a.z; h1[3] = a.w; h2[0] = b.x; h2[1] = b.y; h2[2] = b.z; h2[3] = b.w;
+                h3[0] = c.x; h3[1] = c.y; h3[2] = c.z; h3[3] = c.w; g[0] = l.x; g[1] = l.y; g[2] = l.z; g[3] = l.w;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (j < n) { h1[j] = hard[S + s + j]; h2[j] = hard[2 * S + s + j]; h3[j] = hard[3 * S + s + j]; g[j] = gt[s + j]; }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int v = g[j] == 4 ? 3 : g[j];                             // a raw 4 is class 3 (test_util3d.py:36)
+                const int et = v == 3, wt = v >= 1 && v <= 3, tc = v == 1 || v == 3;
+                const int a = h1[j] != 0.0f, b = h2[j] != 0.0f, c = h3[j] != 0.0f;
+                i1 += a & et; p1 += a; g1 += et; i2 += b & wt; p2 += b; g2 += wt; i3 += c & tc; p3 += c; g3 += tc;
+            }
+        }
+        if (labels) {
+            float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f}, s3[4] = {0.f, 0.f, 0.f, 0.f};
+            if (VEC) {
+                const float4 a = *reinterpret_cast<const float4*>(soft + S + s), b = *reinterpret_cast<const float4*>(soft + 2 * S + s),
+                             c = *reinterpret_cast<const float4*>(soft + 3 * S + s);
+                s1[0] = a.x; s1[1] = a.y; s1[2] = a.z; s1[3] = a.w; s2[0] = b.x; s2[1] = b.y; s2[2] = b.z; s2[3] = b.w;
+                s3[0] = c.x; s3[1] = c.y; s3[2] = c.z; s3[3] = c.w;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (j < n) { s1[j] = soft[S + s + j]; s2[j] = soft[2 * S + s + j]; s3[j] = soft[3 * S + s + j]; }
+            }
+            unsigned lab[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {                                       // brats_inv_map_label (datasets3d.py:65-90): one subtraction, at most one product each
+                const float inv0 = 1.0f - s2[j], inv1 = (s3[j] - s1[j]) * 1.5f, inv2 = (s2[j] - s3[j]) * 1.5f, inv3 = s1[j];
+                float best = inv0; unsigned k = 0;
+                if (case_tail_beats(inv1, best)) { best = inv1; k = 1; }
+                if (case_tail_beats(inv2, best)) { best = inv2; k = 2; }
+                if (case_tail_beats(inv3, best)) { best = inv3; k = 4; }        // label 3 is exported as 4 (test_util3d.py:84-85)
+                lab[j] = k;
+            }
+            if (VEC) {
+                *reinterpret_cast<uint32_t*>(labels + s) = lab[0] | (lab[1] << 8) | (lab[2] << 16) | (lab[3] << 24);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (j < n) labels[s + j] = (uint8_t)lab[j];
+            }
+        }
+    }
+    if (counts) {                                                               // wave -> LDS -> one atomic add per counter per workgroup
+        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+        i1 = wave_sum_int(i1); p1 = wave_sum_int(p1); g1 = wave_sum_int(g1); i2 = wave_sum_int(i2); p2 = wave_sum_int(p2); g2 = wave_sum_int(g2);
+        i3 = wave_sum_int(i3); p3 = wave_sum_int(p3); g3 = wave_sum_int(g3);
+        if (lane == 0) {
+            int* r = red[wave];
+            r[0] = i1; r[1] = p1; r[2] = g1; r[3] = i2; r[4] = p2; r[5] = g2; r[6] = i3; r[7] = p3; r[8] = g3;
+        }
+        __syncthreads();
+        if (threadIdx.x < 9) {
+            int t = 0;
+#pragma unroll
+            for (int w = 0; w < CT_WAVES; ++w) t += red[w][threadIdx.x];
+            if (t) atomicAdd(counts + threadIdx.x, t);
+        }
+    }
+}
+
 }  // namespace segx
 
 using namespace segx;
@@ -155,4 +256,19 @@ extern "C" int segx_surface_hist(const uint8_t* border_from, const int32_t* d2_t
     hipLaunchKernelGGL(surface_hist_kernel, dim3((unsigned)i64max(1, i64min(1024, (S + 4095) / 4096)), (unsigned)planes), dim3(256), 0, stream, border_from, d2_to,
                        hist, S, nbins);
     return check_launch("segx_surface_hist");
+}
+
+extern "C" int segx_brats_case_tail(const float* soft, const float* hard, const int32_t* gt, int32_t* counts, uint8_t* labels, int64_t S, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(soft && hard, "segx_brats_case_tail: null soft or hard");
+    SEGX_REQUIRE(counts || labels, "segx_brats_case_tail: neither counts nor labels asked for");
+    SEGX_REQUIRE(!counts || gt, "segx_brats_case_tail: counts need the ground truth");
+    SEGX_REQUIRE(S > 0 && S < ((int64_t)1 << 31), "segx_brats_case_tail: S = %lld is not in 1 .. 2^31 - 1", (long long)S);
+    if (counts) hipLaunchKernelGGL(case_tail_init_kernel, dim3(1), dim3(64), 0, stream, counts);
+    // a plane starts c * S floats into its tensor: 16-byte loads are legal only when S % 4 == 0 (and the bases are aligned)
+    const uintptr_t a16 = (uintptr_t)soft | (uintptr_t)hard | (counts ? (uintptr_t)gt : 0);
+    const bool vec = S % 4 == 0 && a16 % 16 == 0 && (uintptr_t)labels % 4 == 0;
+    const dim3 grid((unsigned)i64min(SEGX_CASE_TAIL_MAX_BLOCKS, ((S + 3) / 4 + CT_THREADS - 1) / CT_THREADS));
+    if (vec) hipLaunchKernelGGL(brats_case_tail_kernel<true>, grid, dim3(CT_THREADS), 0, stream, soft, hard, gt, counts, labels, S);
+    else hipLaunchKernelGGL(brats_case_tail_kernel<false>, grid, dim3(CT_THREADS), 0, stream, soft, hard, gt, counts, labels, S);
+    return check_launch("segx_brats_case_tail");
 }

@@ -2546,6 +2546,44 @@ def surface_hist(border_from, d2_to):
     return hist
 
 
+def brats_case_tail(soft, hard, gt=None, want_labels=True, counts=None, labels=None):
+    """The tail of one BraTS case in one launch (segx_brats_case_tail): soft, hard float32 [4, *spatial] (or [4, S]) as window_merge / harden_segmap leave them in mode 1;
+    gt: the raw label volume [*spatial] (converted to int32 when it is not), or None.  Returns (counts, labels):
+      counts int32 [3, 3] -- per foreground class {sum pred * gt, sum pred, sum gt} against brats_map_label(gt) (a raw 4 counts as 3), which never exists as a
+        tensor; None without gt;
+      labels uint8 [*spatial] -- argmax(brats_inv_map_label(soft)) with 3 written as 4, the volume the reference saves; None with want_labels=False.
+    counts / labels: tensors to write into (a captured graph passes its static ones); passing `labels` asks for them.  No copy to the host, no synchronisation.
+    Forward only."""
+    _no_grad_operands('brats_case_tail', soft, hard)
+    if soft.dim() < 2 or soft.shape[0] != 4 or soft.shape != hard.shape or soft.dtype != torch.float32 or hard.dtype != torch.float32:
+        raise ValueError('brats_case_tail: soft %s and hard %s must be float32 [4, *spatial] tensors of one shape' % (tuple(soft.shape), tuple(hard.shape)))
+    spatial = tuple(soft.shape[1:])
+    S = soft[0].numel()
+    if S < 1:
+        raise ValueError('brats_case_tail: empty tensor %s' % (tuple(soft.shape),))
+    soft, hard = _c(soft.detach()), _c(hard.detach())
+    if gt is None:
+        if counts is not None:
+            raise ValueError('brats_case_tail: counts need gt')
+    else:
+        if tuple(gt.shape) != spatial:
+            raise ValueError('brats_case_tail: gt %s is not the volume %s' % (tuple(gt.shape), spatial))
+        gt = _c(gt.detach().to(torch.int32))
+        if counts is None:
+            counts = torch.empty(3, 3, dtype=torch.int32, device=soft.device)
+        elif counts.dtype != torch.int32 or tuple(counts.shape) != (3, 3) or not counts.is_contiguous():
+            raise ValueError('brats_case_tail: counts is a contiguous int32 [3, 3] tensor')
+    if labels is not None:
+        if labels.dtype != torch.uint8 or tuple(labels.shape) != spatial or not labels.is_contiguous():
+            raise ValueError('brats_case_tail: labels is a contiguous uint8 %s tensor' % (spatial,))
+    elif want_labels:
+        labels = torch.empty(spatial, dtype=torch.uint8, device=soft.device)
+    if counts is None and labels is None:
+        raise ValueError('brats_case_tail: nothing to compute (no gt and want_labels=False)')
+    segx.lib().brats_case_tail(soft, hard, gt if counts is not None else None, counts, labels, S)
+    return counts, labels
+
+
 # -------------------------------------------------------------------------------------------------
 # Tail of the 2-D evaluation (components.hip): connected components, fragment removal, row extents, n-hot -> pixel values.  Stacks of planes [P, H, W] (or one
 # [H, W] plane); integer kernels with exact results; no copy to the host and no synchronisation, so the calls can be captured into a graph.  Forward only.

@@ -5,8 +5,14 @@ convolutions of Inception-I3D (conv3d.hip, conv3d_halo.hip) and the GEMMs of the
 accumulation and the hardening are test_util3d's own.
 
 It also holds the surface-distance half of calculate_metric_percase (reference test_util3d.py:203-213: medpy's asd, and the hd95 of the commented-out line), computed on
-the device in integers (metrics.hip) and finished here in float64; test_util3d.calculate_metric_percase keeps reporting those columns as invalid."""
+the device in integers (metrics.hip) and finished here in float64; test_util3d.calculate_metric_percase keeps reporting those columns as invalid.
+
+And the case evaluation in one pass: sliding_windows (the eager loops' geometry and batches), test_single_case(fused=True) (one gather launch, net() on the
+eager loop's batches, one merge launch), GraphedSlidingWindow3d (that sequence with the BraTS case tail, SF.brats_case_tail, as one replayable hipGraph), case_metrics
+and test_all_cases (the reference's loop over the cases of a dataset, test_util3d.py:15-91, without its file I/O)."""
 import contextlib
+import math
+import os
 
 import numpy as np
 import torch
@@ -41,14 +47,82 @@ def _folded(net, fold_bn):
             unfold_batchnorm(net)
 
 
+def sliding_windows(H, W, D, orig_patch_size, stride_xy, stride_z, batch_size):
+    """The window geometry of test_util3d.test_single_case for an H x W x D volume: ((xl, yl, zl), (H2, W2, D2), origins, chunks) -- the left pads, the padded extent,
+    the (xs, ys, zs) origin of every window in padded coordinates in the eager loops' order (x outer, then y, z innermost; the last origin of an axis clamped to
+    extent - window), and the eager loop's grouping of them into net() calls as (first, end) index ranges into `origins`: within an x row its sy * sz windows in runs
+    of batch_size, the row's last run shorter if need be -- the eager loop flushes at the end of every x row, so no chunk crosses one.  A stride that is not
+    positive, or above its window extent (cells no window covers), raises ValueError, as infer2d.sliding_windows does."""
+    dx, dy, dz = (int(v) for v in orig_patch_size)
+    sxy, sz_, bs = int(stride_xy), int(stride_z), int(batch_size)
+    if sxy <= 0 or sz_ <= 0 or sxy > min(dx, dy) or sz_ > dz:
+        raise ValueError('sliding_windows: strides (%r, %r) must be positive and at most the window %r' % (stride_xy, stride_z, tuple(orig_patch_size)))
+    if bs < 1:
+        raise ValueError('sliding_windows: batch_size must be at least 1')
+    pads = [max(dx - H, 0), max(dy - W, 0), max(dz - D, 0)]
+    H2, W2, D2 = H + pads[0], W + pads[1], D + pads[2]
+    nx = math.ceil((H2 - dx) / sxy) + 1
+    ny = math.ceil((W2 - dy) / sxy) + 1
+    nz = math.ceil((D2 - dz) / sz_) + 1
+    origins = [(min(sxy * x, H2 - dx), min(sxy * y, W2 - dy), min(sz_ * z, D2 - dz)) for x in range(nx) for y in range(ny) for z in range(nz)]
+    row = ny * nz
+    chunks = [(x * row + k, x * row + min(k + bs, row)) for x in range(nx) for k in range(0, row, bs)]
+    return tuple(p // 2 for p in pads), (H2, W2, D2), origins, chunks
+
+
+class _Plan3d:
+    """what the fused 3-D sequence needs beyond the image: the window table on the device, the geometry and the eager loop's chunks"""
+
+    def __init__(self, image_shape, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, device):
+        self.shape = tuple(int(v) for v in image_shape)
+        if len(self.shape) != 4:
+            raise ValueError('a [C, H, W, D] image, not %r' % (self.shape,))
+        self.window, self.patch = tuple(int(v) for v in orig_patch_size), tuple(int(v) for v in input_patch_size)
+        self.pads, self.canvas, origins, self.chunks = sliding_windows(*self.shape[1:], self.window, stride_xy, stride_z, batch_size)
+        self.table = SF.WindowTable(origins, device)
+
+    def run(self, net, image):
+        """gather -> net() per chunk of the eager loop -> merge; the caller holds torch.no_grad().  (preds_hard, preds_soft) [num_classes, H, W, D]"""
+        patches = SF.window_gather(image.unsqueeze(0), self.table, self.window, self.patch, self.pads, self.canvas)
+        scores = None
+        for k0, k1 in self.chunks:
+            part = net(patches[k0:k1])
+            if scores is None:
+                if len(self.chunks) == 1:
+                    scores = part
+                    break
+                scores = part.new_empty((self.table.nwin,) + tuple(part.shape[1:]))
+            scores[k0:k1] = part                                     # plumbing: the chunks' scores side by side, as merge reads them
+        preds_soft, preds_hard = SF.window_merge(scores, self.table, self.window, self.shape[1:], self.pads, self.canvas, mode=1)
+        return preds_hard[0], preds_soft[0]
+
+
+def _check_task(net_type, task_name):
+    """the refusals of test_util3d.test_single_case"""
+    if net_type != 'segtran':
+        raise NotImplementedError("net_type '%s': only segtran is built" % net_type)
+    if task_name != 'brats':
+        raise NotImplementedError('only the BraTS (n-hot, consistency rule) hardening is built; argmax tasks are not in BASELINE')
+
+
 def test_single_case(net, image, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, task_name, net_type='segtran', num_classes=4,
-                     precision='fp32', fold_bn=False):
-    """test_util3d.test_single_case with two more arguments.  precision: 'fp32' (default) -- exactly that function's results -- or 'bf16x3' -- the same loop under
+                     precision='fp32', fold_bn=False, fused=False):
+    """test_util3d.test_single_case with three more arguments.  precision: 'fp32' (default) -- exactly that function's results -- or 'bf16x3' -- the same loop under
     torch.no_grad() inside inference_precision('bf16x3'); the setting the process had comes back at the end, also after an exception.  Any other name: ValueError.
-    fold_bn: with the backbone's BatchNorm3d layers folded into its convolutions for this call (fold_batchnorm; a net the caller folded stays folded)."""
+    fold_bn: with the backbone's BatchNorm3d layers folded into its convolutions for this call (fold_batchnorm; a net the caller folded stays folded).
+    fused: one window_gather launch on the image (the padded canvas never exists), net() once per chunk of sliding_windows() -- exactly the samples the eager loop
+    stacks, so the forwards see the eager shapes --, the scores side by side in one buffer, one window_merge launch (no acc / cnt canvas, no accumulate pass per
+    window, no clone of the un-padded region).  The merge is the accumulate + harden arithmetic bit for bit, so (preds_hard, preds_soft) equal the eager ones
+    bit for bit for every batch_size.  The gather and the score buffer hold ALL windows at once: for a BraTS case (240 x 240 x 155, window 112 x 112 x 96 at
+    stride 56 / 48: 48 windows x 4 channels x 112 x 112 x 96 floats) about 0.93 GB each."""
     with _precision(precision), _folded(net, fold_bn):
-        return _T3.test_single_case(net, image, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, task_name, net_type=net_type,
-                                    num_classes=num_classes)
+        if not fused:
+            return _T3.test_single_case(net, image, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, task_name, net_type=net_type,
+                                        num_classes=num_classes)
+        _check_task(net_type, task_name)
+        plan = _Plan3d(image.shape, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, image.device)
+        with torch.no_grad():
+            return plan.run(net, image)
 
 
 # reference function name; not a pytest test
@@ -108,3 +182,191 @@ def calculate_metric_percase(allcls_pred, allcls_gt, num_classes, surface=False,
         metric[:, 2], metric[:, 3] = hd, asd
         valid[:, 2] = valid[:, 3] = ok
     return metric, valid
+
+
+def case_metrics(counts):
+    """(metric, valid) float64 [3, 4], columns [dice, jc, hd, asd], of one BraTS case from its integer counts [3, 3] = {sum pred * gt, sum pred, sum gt} per
+    foreground class (SF.brats_case_tail; a tensor or an array): the expressions of test_util3d.calculate_metric_percase -- dice = 2 i / (p + g), 0 when p + g == 0;
+    jc = i / (p + g - i), invalid when g == 0; the surface columns 0 / invalid.  The sums enter as float32 scalars, the type segx_dice_sums hands that function, so
+    the quotients are its quotients bit for bit wherever its float32 sums are exact (counts below 2^24); beyond that the counts here are still the exact ones."""
+    sums = (counts.cpu().numpy() if isinstance(counts, torch.Tensor) else np.asarray(counts)).astype(np.float32)
+    if sums.shape != (3, 3):
+        raise ValueError('case_metrics: counts [3, 3], not %r' % (sums.shape,))
+    metric = np.zeros((3, 4)); valid = np.ones((3, 4))
+    for c in range(3):
+        inter, ps, gs = sums[c]
+        dice = 2.0 * inter / (ps + gs) if ps + gs > 0 else 0.0
+        if gs > 0:
+            jc = inter / (ps + gs - inter)
+        else:
+            jc = 0.0; valid[c, 1] = 0
+        valid[c, 2] = valid[c, 3] = 0
+        metric[c] = [dice, jc, 0, 0]
+    return metric, valid
+
+
+class GraphedSlidingWindow3d:
+    """infer2d.GraphedSlidingWindow for a volume: the fused sliding-window evaluation of one image shape [C, H, W, D] -- gather, the forward of every chunk, merge and,
+    when asked, the case tail (SF.brats_case_tail) -- captured into one hipGraph and replayed; the BraTS task (n-hot hardening with the consistency rule).
+
+    net must be in eval mode (RuntimeError otherwise).  fold_bn folds its backbone's BatchNorm3d layers (fold_batchnorm) if they are not folded already; close()
+    unfolds what the constructor folded, and so does a failed construction.  with_labels: the export label volume (uint8 [H, W, D]) is part of the capture;
+    with_mask: the object owns a static int32 [H, W, D] ground-truth buffer and the capture also forms the case's counts (int32 [3, 3], case_metrics() turns them
+    into Dice / Jaccard).  __call__(image) or __call__(image, mask) copies into the static buffers, replays and returns (preds_hard, preds_soft, labels, counts):
+    STATIC tensors that the next call overwrites -- clone what must outlive it; entries that were not asked for are None.  A call raises RuntimeError once the net
+    was put in train mode or its fold state differs from the one captured, ValueError on another shape.
+    precision ('fp32' default, 'bf16x3'): warm-up and capture run inside inference_precision(precision); a replay needs no setting and leaves none behind.
+    The gather and score buffers hold all windows (test_single_case: about 0.93 GB each for a BraTS case) for the life of the object."""
+
+    def __init__(self, net, image_shape, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, num_classes=4, fold_bn=True, warmup=2,
+                 precision='fp32', with_labels=True, with_mask=False):
+        from . import segx
+        if net.training:
+            raise RuntimeError('GraphedSlidingWindow3d is for inference: call net.eval() first')
+        if precision not in PRECISIONS:
+            raise ValueError('precision: %r is not one of %s' % (precision, sorted(PRECISIONS)))
+        self.precision = precision
+        assert segx.lib().gemm_prof is None, 'per-launch event profiling cannot run inside a captured evaluation'
+        device = next(net.parameters()).device
+        self.net, self.num_classes = net, num_classes
+        self.with_labels, self.with_mask = bool(with_labels), bool(with_mask)
+        self._folded_here = bool(fold_bn) and not net.batchnorm_folded
+        if self._folded_here:
+            fold_batchnorm(net)
+        try:
+            self.folded = net.batchnorm_folded
+            self.plan = _Plan3d(image_shape, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, device)     # the window table: built before capture
+            spatial = self.plan.shape[1:]
+            self.image = torch.zeros(self.plan.shape, dtype=torch.float32, device=device)
+            self.mask = torch.zeros(spatial, dtype=torch.int32, device=device) if self.with_mask else None
+            self.counts = torch.zeros(3, 3, dtype=torch.int32, device=device) if self.with_mask else None
+            self.labels = torch.zeros(spatial, dtype=torch.uint8, device=device) if self.with_labels else None
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side), torch.no_grad(), _precision(precision):   # eager warm-up: GEMM plans, derived operands, allocator pools
+                for _ in range(warmup):
+                    self._sequence()
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.no_grad(), _precision(precision), torch.cuda.graph(self.graph):
+                self.preds_hard, self.preds_soft = self._sequence()
+            if self.preds_soft.shape[0] != num_classes:
+                raise ValueError('the net has %d classes, not %d' % (self.preds_soft.shape[0], num_classes))
+        except BaseException:                                   # leave the net as it was found
+            self.graph = None
+            if self._folded_here and net.batchnorm_folded:
+                unfold_batchnorm(net)
+            raise
+        self.replays = 0
+
+    def _sequence(self):
+        hard, soft = self.plan.run(self.net, self.image)
+        if self.with_labels or self.with_mask:
+            SF.brats_case_tail(soft, hard, self.mask, want_labels=self.with_labels, counts=self.counts, labels=self.labels)
+        return hard, soft
+
+    def __call__(self, image, mask=None):
+        if self.graph is None:
+            raise RuntimeError('GraphedSlidingWindow3d: closed')
+        if self.net.training:
+            raise RuntimeError('GraphedSlidingWindow3d: the net is in train mode; the captured evaluation is the eval-mode forward')
+        if self.net.batchnorm_folded != self.folded:
+            raise RuntimeError('GraphedSlidingWindow3d: the BatchNorm fold of the net changed since capture (train(), load_state_dict() or an in-place edit); '
+                               'build a new GraphedSlidingWindow3d')
+        if tuple(image.shape) != self.plan.shape:
+            raise ValueError('GraphedSlidingWindow3d: captured for images %r, got %r' % (self.plan.shape, tuple(image.shape)))
+        if (mask is not None) != self.with_mask:
+            raise ValueError('GraphedSlidingWindow3d: built with_mask=%r: call it %s a mask' % (self.with_mask, 'with' if self.with_mask else 'without'))
+        if mask is not None and tuple(mask.shape) != self.plan.shape[1:]:
+            raise ValueError('GraphedSlidingWindow3d: captured for masks %r, got %r' % (self.plan.shape[1:], tuple(mask.shape)))
+        if image is not self.image:
+            self.image.copy_(image, non_blocking=True)
+        if mask is not None and mask is not self.mask:
+            self.mask.copy_(mask, non_blocking=True)           # converts to int32
+        self.graph.replay()
+        self.replays += 1
+        return self.preds_hard, self.preds_soft, self.labels, self.counts
+
+    def close(self):
+        """drop the graph and its static tensors; unfold the net if the constructor folded it"""
+        self.graph = self.preds_hard = self.preds_soft = self.labels = self.counts = self.image = self.mask = None
+        if self._folded_here and self.net.batchnorm_folded:
+            unfold_batchnorm(self.net)
+        self._folded_here = False
+
+
+def test_all_cases(net, db_test, task_name='brats', net_type='segtran', num_classes=4, batch_size=8, orig_patch_size=(128, 112, 80),
+                   input_patch_size=(128, 112, 64), stride_xy=56, stride_z=40, has_mask=True, on_labels=None, fused=True, graph=False, surface=False, hd95=False,
+                   precision='fp32', fold_bn=False):
+    """The reference's evaluation loop over the cases of a dataset (test_util3d.py:15-91) for the BraTS task, without its file I/O; returns avg_metric
+    [num_classes - 1, 4] (columns dice, jc, hd, asd) = the sum of the cases' metrics over the number of cases in which each entry is valid, as the reference does
+    (an entry valid in no case is 0 / 0 = NaN).
+
+    db_test: anything indexable with len(), of samples holding 'image' [C, H, W, D], 'mask' [H, W, D] (raw BraTS labels) and 'image_path'.  Per case: the
+    sliding-window evaluation (test_single_case with fused=; graph=True: one GraphedSlidingWindow3d per distinct image shape, closed at the end), then ONE
+    tail launch (SF.brats_case_tail) that maps the ground truth in registers, forms the case's integer counts and, when on_labels is given, the export label
+    volume.  The counts of all cases stay on the device ([ncases, 3, 3]) and are read once after the loop: the default path has no copy to the host per case.
+    on_labels(image_name, labels) receives the uint8 [H, W, D] device volume the reference would save (image_name = the file name up to its first dot); writing
+    NIfTI is the caller's.  has_mask=False: no metrics (every entry 0 over ncases, as in the reference).
+    surface=True (hd95=True implies it): columns 2 and 3 through surface_metrics on the float ground truth of SF.label_nhot(., 'brats') -- that builds the
+    [4, S] maps and reads its histograms from the device once per case.
+    fold_bn: ONE fold for all the cases; precision: as test_single_case.  The reference's test_interp is not built."""
+    _check_task(net_type, task_name)
+    if num_classes != 4:
+        raise NotImplementedError('num_classes %r: only the 4-class BraTS task is built' % (num_classes,))
+    surface = bool(surface or hd95)
+    ncases = len(db_test)
+    device = next(net.parameters()).device
+    counts_all = torch.zeros(ncases, 3, 3, dtype=torch.int32, device=device) if has_mask else None
+    surf = []
+    graphs = {}
+    try:
+        with _precision(precision), _folded(net, fold_bn), torch.no_grad():
+            for i in range(ncases):
+                sample = db_test[i]
+                image, mask = sample['image'].to(device), (sample['mask'].to(device) if has_mask else None)
+                image_name = os.path.basename(os.path.normpath(sample['image_path'])).split('.')[0]
+                want_labels = on_labels is not None
+                if graph:
+                    g = graphs.get(tuple(image.shape))
+                    if g is None:
+                        g = graphs[tuple(image.shape)] = GraphedSlidingWindow3d(net, image.shape, orig_patch_size, input_patch_size, batch_size, stride_xy,
+                                                                                stride_z, num_classes, fold_bn=False, precision=precision,
+                                                                                with_labels=want_labels, with_mask=has_mask)
+                    preds_hard, _, labels, counts = g(image, mask) if has_mask else g(image)
+                    if has_mask:
+                        counts_all[i].copy_(counts)
+                    if want_labels:
+                        labels = labels.clone()                 # the graph's static volume: the next replay overwrites it
+                else:
+                    preds_hard, preds_soft = test_single_case(net, image, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, task_name,
+                                                              net_type=net_type, num_classes=num_classes, fused=fused)
+                    labels = None
+                    if has_mask or want_labels:
+                        _, labels = SF.brats_case_tail(preds_soft, preds_hard, mask, want_labels=want_labels, counts=counts_all[i] if has_mask else None)
+                if surface and has_mask:
+                    gt = SF.label_nhot((mask - (mask == 4).to(mask.dtype)).unsqueeze(0), 'brats')[0]
+                    surf.append(surface_metrics(preds_hard[1:num_classes], gt[1:num_classes], hd95=hd95))
+                if want_labels:
+                    on_labels(image_name, labels)
+    finally:
+        for g in graphs.values():
+            g.close()
+    total, valid_counts = np.zeros((num_classes - 1, 4)), np.zeros((num_classes - 1, 4))
+    if has_mask:
+        for i, c in enumerate(counts_all.cpu().numpy()):       # the one device-to-host copy of the default path
+            metric, valid = case_metrics(c)
+            if surface:
+                asd, hd, ok = surf[i]
+                metric[:, 2], metric[:, 3] = hd, asd
+                valid[:, 2] = valid[:, 3] = ok
+            total += metric
+            valid_counts += valid
+    else:
+        valid_counts += ncases
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return total / valid_counts
+
+
+test_all_cases.__test__ = False
