@@ -634,7 +634,9 @@ int segx_window_accum(const float* scores, float* acc, float* cnt, int B, int C,
 /* soft = acc / cnt (cnt NULL: soft = acc), then
  *   mode 0: harden_segmap2d/3d (datasets2d.py:178-196, datasets3d.py:92-111): hard[c>=1] = soft[c] >= T, hard[0] = no other class on
  *   mode 1: make_brats_pred_consistent(is_conservative=False) (datasets3d.py:43-63) first, C == 4 (test_util3d.py:169-174)
- * acc/soft/hard [B, C, S] (hard as 0/1 floats), cnt [B, S]; soft may be NULL */
+ * acc/soft/hard [B, C, S] (hard as 0/1 floats), cnt [B, S]; soft may be NULL.  2 <= C <= SEGX_MAX_CLASSES */
+#define SEGX_MAX_CLASSES 16             /* class cap of segx_harden_segmap, segx_window_merge and the one-hot calls below: a cell's classes are held in registers, in
+                                         * an 8-entry form for C <= 8 and a 16-entry form above (the OCT task has 10 classes) */
 int segx_harden_segmap(const float* acc, const float* cnt, float* soft, float* hard, int B, int C, int64_t S, int mode, float T,
                        void* stream);
 /* The whole sliding-window evaluation as a fixed sequence: segx_window_gather, the network on the stacked windows, segx_window_merge.
@@ -648,7 +650,7 @@ int segx_window_gather(const float* image, const int* origins, const int* origin
                        void* stream);
 /* segx_window_merge: what nwin segx_window_accum calls (ascending k, on zeroed acc / cnt) and one segx_harden_segmap leave, restricted to the image:
  *   soft[b][c][cell] = (sum over the windows k covering the cell of sigmoid(F.interpolate(scores[k * B + b][c], size=window))) / (their number), bit for bit;
- *   hard as segx_harden_segmap (mode 0 / mode 1 with C == 4, threshold T).  acc and cnt never exist.
+ *   hard as segx_harden_segmap (mode 0 / mode 1 with C == 4, threshold T; 2 <= C <= SEGX_MAX_CLASSES).  acc and cnt never exist.
  *   scores [nwin * B, C, d, h, w]; soft, hard [B, C, ID, IH, IW];
  *   geom (int32[15]) = {d, h, w (scores), D, H, W (window), CD, CH, CW (padded canvas), pz, py, px (left pads), ID, IH, IW (image)} */
 int segx_window_merge(const float* scores, const int* origins, const int* origins_host, float* soft, float* hard, int nwin, int B, int C,
@@ -697,6 +699,28 @@ int segx_surface_hist(const uint8_t* border_from, const int32_t* d2_to, int32_t*
 #define SEGX_CASE_TAIL_THREADS 256        /* workgroup size; a workgroup covers 4 * SEGX_CASE_TAIL_THREADS voxels per trip: tests place their sizes by these */
 #define SEGX_CASE_TAIL_MAX_BLOCKS 2048    /* grid cap: above 4 * THREADS * MAX_BLOCKS voxels the grid-stride loop takes another trip */
 int segx_brats_case_tail(const float* soft, const float* hard, const int32_t* gt, int32_t* counts, uint8_t* labels, int64_t S, void* stream);
+
+/* One-hot tasks (metrics.hip): the OCT task's 10 retinal-layer classes (train2d.py:369-384), labelled by index masks.
+ * index_to_onehot (datasets2d.py:22-51): out[b][c][s] = (labels[b][s] == c) as floats; labels [B][S] are uint8 (label_bytes = 1) or int32 (label_bytes = 4),
+ * out [B][C][S], 1 <= C <= SEGX_MAX_CLASSES.  A label >= C or negative sets no class: the reference's scatter_ raises an index error there, which a kernel cannot. */
+int segx_index_onehot(const void* labels, int label_bytes, float* out, int64_t B, int C, int64_t S, void* stream);
+/* onehot_inv_map (datasets2d.py:54-88): out[b][s][0..2] = colormap[argmax_c nhot[b][c][s]], the arg-max as torch.argmax takes it (the lowest index wins a tie, a NaN
+ * beats every number).  nhot [B][C][S] floats, colormap uint8 [C][3] in device memory, out uint8 [B][S][3]; colormap = NULL writes the index to all three bytes.
+ * 1 <= C <= SEGX_MAX_CLASSES. */
+int segx_onehot_colormap(const float* nhot, const uint8_t* colormap, uint8_t* out, int64_t B, int C, int64_t S, void* stream);
+/* The evaluation tail of a one-hot task in one pass over soft (test_util2d.py:241-265 calc_batch_metric, test2d.py:640-649 onehot_inv_map), the counterpart of
+ * segx_brats_case_tail: the same counting scheme, workgroup size, grid cap and alignment rule (SEGX_CASE_TAIL_*), one grid row per image.
+ *   soft [B][C][S] as segx_window_merge leaves it (plane 0 is not read); gt [B][S] uint8 index labels; T the hardening threshold.
+ *   counts [B][C-1][3] (int32, initialised here): {sum pred * gt, sum pred, sum gt} for c = 1..C-1 with pred = soft[c] >= T (a NaN is off) and gt = (label == c);
+ *     a label >= C counts for no class.  Vector integer atomic adds, one per counter per workgroup: exact and independent of the order of execution.
+ *   labels [B][S] (uint8): the lowest class >= 1 that is on, 0 where none is -- onehot_inv_map(harden_segmap2d(soft)) without a table, i.e. the arg-max over the
+ *     hardened map whose plane 0 is "no other class on".
+ *   rgb [B][S][3] (uint8) = colormap[label]; colormap uint8 [C][3] in device memory.
+ * gt with counts, labels, and colormap with rgb may each be NULL, but not all three outputs.  1 <= B <= 65535, 2 <= C <= SEGX_MAX_CLASSES, 0 < S < 2^31.  Wide accesses
+ * (16-byte loads of soft, dword accesses of gt / labels / rgb) when S % 4 == 0, soft is 16-byte and the others 4-byte aligned, else dword loads and byte accesses for
+ * the whole call.  No copy to the host, no synchronisation: the call can be captured. */
+int segx_onehot_case_tail(const float* soft, const uint8_t* gt, const uint8_t* colormap, int32_t* counts, uint8_t* labels, uint8_t* rgb, int B, int C, int64_t S,
+                          float T, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Tail of the 2-D evaluation (components.hip): connected components, fragment removal (test_util2d.py:267-289), row extents for the vertical cup/disc ratio

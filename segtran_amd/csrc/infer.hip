@@ -41,6 +41,9 @@ __device__ __forceinline__ float mean_prob(float a, float n) { return a / n; }
 // One cell's C soft values p[] -> soft / hard planes (both already offset to the cell of class 0; classes lie S floats apart).  mode 1 first makes a BraTS
 // prediction consistent, the permissive way (is_conservative=False): P(WT) = max(P(ET), P(WT), P(TC)), P(TC) = max(P(ET), P(TC));  then
 // hard[c >= 1] = soft[c] >= T and hard[0] = (no other class is on).  harden_kernel and window_merge_kernel both call it.
+// MAXC: the compile-time class bound (8 or 16, C <= MAXC).  Every loop over the classes runs MAXC trips under a `c < C` predicate, so p[] is indexed by constants
+// only and stays in registers (an array indexed by a run-time class count goes to scratch at 16 entries); the C <= 8 calls run the 8 form and keep its registers.
+template <int MAXC>
 __device__ __forceinline__ void harden_cell(float* p, int C, int mode, float T, float* __restrict__ soft, float* __restrict__ hard, int64_t S) {
     if (mode == 1) {                                   // C == 4: [bg, ET, WT, TC]
         const float et = p[1], wt = p[2], tc = p[3];
@@ -48,26 +51,34 @@ __device__ __forceinline__ void harden_cell(float* p, int C, int mode, float T, 
         p[3] = fmaxf(et, tc);
     }
     bool any = false;
-    for (int c = 1; c < C; ++c) {
-        const bool on = p[c] >= T;
-        any = any || on;
-        hard[c * S] = on ? 1.0f : 0.0f;
-        if (soft) soft[c * S] = p[c];
+#pragma unroll
+    for (int c = 1; c < MAXC; ++c) {
+        if (c < C) {
+            const bool on = p[c] >= T;
+            any = any || on;
+            hard[c * S] = on ? 1.0f : 0.0f;
+            if (soft) soft[c * S] = p[c];
+        }
     }
     hard[0] = any ? 0.0f : 1.0f;
     if (soft) soft[0] = p[0];
 }
 
 // soft = acc / cnt (cnt == NULL: acc already is the soft map), then harden_cell.  One thread per voxel.
+template <int MAXC>
 __global__ __launch_bounds__(256) void harden_kernel(const float* __restrict__ acc, const float* __restrict__ cnt, float* __restrict__ soft,
                                                      float* __restrict__ hard, int B, int C, int64_t S, int mode, float T) {
     const int64_t total = (int64_t)B * S;
     for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
         const int64_t b = idx / S, s = idx - b * S;
         const float n = cnt ? cnt[idx] : 1.0f;
-        float p[8];
-        for (int c = 0; c < C; ++c) p[c] = cnt ? mean_prob(acc[(b * C + c) * S + s], n) : acc[(b * C + c) * S + s];
-        harden_cell(p, C, mode, T, soft ? soft + (b * C) * S + s : nullptr, hard + (b * C) * S + s, S);
+        float p[MAXC];
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c) {
+            p[c] = 0.0f;
+            if (c < C) p[c] = cnt ? mean_prob(acc[(b * C + c) * S + s], n) : acc[(b * C + c) * S + s];
+        }
+        harden_cell<MAXC>(p, C, mode, T, soft ? soft + (b * C) * S + s : nullptr, hard + (b * C) * S + s, S);
     }
 }
 
@@ -94,24 +105,32 @@ __global__ __launch_bounds__(256) void window_gather_kernel(const float* __restr
 // soft[b][c][cell] = (sum over the windows k covering the cell, ascending k, of window_prob(scores[k * B + b][c])) / (their count), then harden_cell: what
 // nwin segx_window_accum passes over zeroed acc / cnt followed by segx_harden_segmap leave, restricted to the image (the un-padded region), without acc / cnt
 // in memory.  One thread per image cell (all classes); the covering windows are found by a pass over the table (uniform loads: k is the same in every lane).
+// MAXC as in harden_cell.  EXACT: the class count IS MAXC (the 2-, 3- and 4-class tasks): no predicate is left, the classes' loads of a window issue together.
+template <int MAXC, bool EXACT>
 __global__ __launch_bounds__(256) void window_merge_kernel(const float* __restrict__ scores, const int* __restrict__ origins, float* __restrict__ soft,
-                                                           float* __restrict__ hard, int nwin, int B, int C, InterpDims q, Sliding sl, int mode, float T) {
+                                                           float* __restrict__ hard, int nwin, int B, int C_, InterpDims q, Sliding sl, int mode, float T) {
+    const int C = EXACT ? MAXC : C_;
     const int64_t isz = (int64_t)sl.ID * sl.IH * sl.IW, ssz = (int64_t)q.d * q.h * q.w, total = (int64_t)B * isz;
     const bool same = q.d == q.D && q.h == q.H && q.w == q.W;
     for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
         const int64_t b = idx / isz, cell = idx - b * isz; int64_t r = cell;
         const int z = (int)(r / ((int64_t)sl.IH * sl.IW)); r -= (int64_t)z * sl.IH * sl.IW;
         const int y = (int)(r / sl.IW), x = (int)(r - (int64_t)y * sl.IW);
-        float p[8], n = 0.0f;
-        for (int c = 0; c < C; ++c) p[c] = 0.0f;
+        float p[MAXC], n = 0.0f;
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c) p[c] = 0.0f;
         for (int k = 0; k < nwin; ++k) {
             const int wz = z + sl.pz - origins[3 * k], wy = y + sl.py - origins[3 * k + 1], wx = x + sl.px - origins[3 * k + 2];
             if ((unsigned)wz >= (unsigned)q.D || (unsigned)wy >= (unsigned)q.H || (unsigned)wx >= (unsigned)q.W) continue;
-            for (int c = 0; c < C; ++c) p[c] += window_prob(scores + (((int64_t)k * B + b) * C + c) * ssz, q, same, wz, wy, wx);
+#pragma unroll
+            for (int c = 0; c < MAXC; ++c)
+                if (c < C) p[c] += window_prob(scores + (((int64_t)k * B + b) * C + c) * ssz, q, same, wz, wy, wx);
             n += 1.0f;
         }
-        for (int c = 0; c < C; ++c) p[c] = mean_prob(p[c], n);
-        harden_cell(p, C, mode, T, soft + (b * C) * isz + cell, hard + (b * C) * isz + cell, isz);
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c)
+            if (c < C) p[c] = mean_prob(p[c], n);
+        harden_cell<MAXC>(p, C, mode, T, soft + (b * C) * isz + cell, hard + (b * C) * isz + cell, isz);
     }
 }
 
@@ -151,9 +170,11 @@ extern "C" int segx_window_accum(const float* scores, float* acc, float* cnt, in
  * cnt may be NULL (acc is already a probability map); soft may be NULL. */
 extern "C" int segx_harden_segmap(const float* acc, const float* cnt, float* soft, float* hard, int B, int C, int64_t S, int mode, float T,
                                   void* stream_) {
-    SEGX_STREAM; SEGX_REQUIRE(acc && hard && B > 0 && C >= 2 && C <= 8 && S > 0 && (mode == 0 || (mode == 1 && C == 4)), "segx_harden_segmap: bad args");
+    SEGX_STREAM; SEGX_REQUIRE(acc && hard && B > 0 && C >= 2 && C <= SEGX_MAX_CLASSES && S > 0 && (mode == 0 || (mode == 1 && C == 4)), "segx_harden_segmap: bad args");
     const int64_t total = (int64_t)B * S;
-    hipLaunchKernelGGL(harden_kernel, dim3((unsigned)i64min(65536, (total + 255) / 256)), dim3(256), 0, stream, acc, cnt, soft, hard, B, C, S, mode, T);
+    const dim3 grid((unsigned)i64min(65536, (total + 255) / 256));
+    if (C <= 8) hipLaunchKernelGGL(harden_kernel<8>, grid, dim3(256), 0, stream, acc, cnt, soft, hard, B, C, S, mode, T);
+    else hipLaunchKernelGGL(harden_kernel<SEGX_MAX_CLASSES>, grid, dim3(256), 0, stream, acc, cnt, soft, hard, B, C, S, mode, T);
     return check_launch("segx_harden_segmap");
 }
 // every window of the host copy of the table inside the padded canvas, and the image inside it at the left pads
@@ -183,15 +204,22 @@ extern "C" int segx_window_gather(const float* image, const int* origins, const 
 extern "C" int segx_window_merge(const float* scores, const int* origins, const int* origins_host, float* soft, float* hard, int nwin, int B, int C,
                                  const int* geom, int mode, float T, void* stream_) {
     SEGX_STREAM; SEGX_REQUIRE(scores && origins && origins_host && soft && hard && geom, "segx_window_merge: null pointer");
-    SEGX_REQUIRE(nwin > 0 && B > 0 && C >= 2 && C <= 8, "segx_window_merge: nwin and B must be positive, 2 <= C <= 8");
+    SEGX_REQUIRE(nwin > 0 && B > 0 && C >= 2 && C <= SEGX_MAX_CLASSES, "segx_window_merge: nwin and B must be positive, 2 <= C <= %d", SEGX_MAX_CLASSES);
     SEGX_REQUIRE(mode == 0 || (mode == 1 && C == 4), "segx_window_merge: mode is 0, or 1 with C == 4");
     SEGX_REQUIRE(geom[0] > 0 && geom[1] > 0 && geom[2] > 0 && geom[3] > 0 && geom[4] > 0 && geom[5] > 0, "segx_window_merge: bad scores / window size");
     const InterpDims q = make_dims(geom[0], geom[1], geom[2], geom[3], geom[4], geom[5]);
     const Sliding sl{geom[6], geom[7], geom[8], geom[9], geom[10], geom[11], geom[12], geom[13], geom[14]};
     SEGX_REQUIRE(sliding_ok(origins_host, nwin, q.D, q.H, q.W, sl), "segx_window_merge: window outside the padded canvas");
     const int64_t total = (int64_t)B * sl.ID * sl.IH * sl.IW;
-    hipLaunchKernelGGL(window_merge_kernel, dim3((unsigned)i64min(65536, (total + 255) / 256)), dim3(256), 0, stream, scores, origins, soft, hard, nwin, B, C, q,
-                       sl, mode, T);
+    const dim3 grid((unsigned)i64min(65536, (total + 255) / 256));
+    const dim3 block(256);
+#define SEGX_MERGE(MAXC, EXACT) hipLaunchKernelGGL((window_merge_kernel<MAXC, EXACT>), grid, block, 0, stream, scores, origins, soft, hard, nwin, B, C, q, sl, mode, T)
+    if (C == 2) SEGX_MERGE(2, true);                       // polyp
+    else if (C == 3) SEGX_MERGE(3, true);                  // fundus
+    else if (C == 4) SEGX_MERGE(4, true);                  // BraTS
+    else if (C <= 8) SEGX_MERGE(8, false);
+    else SEGX_MERGE(SEGX_MAX_CLASSES, false);
+#undef SEGX_MERGE
     return check_launch("segx_window_merge");
 }
 extern "C" int64_t segx_dice_ws_floats(int64_t planes, int64_t S) { return 3 * planes * i64max(1, i64min(64, (S + 4095) / 4096)); }

@@ -214,6 +214,139 @@ __global__ __launch_bounds__(CT_THREADS) void brats_case_tail_kernel(const float
     }
 }
 
+// ---- one-hot tasks (OCT: 10 retinal-layer classes; datasets2d.py:22-86, test_util2d.py:241-265) ----
+// out[b][c][s] = (labels[b][s] == c); labels are bytes (BYTES == 1) or int32 (BYTES == 4).  A label outside 0..C-1 matches no class.  One thread per pixel.
+template <int BYTES>
+__global__ __launch_bounds__(256) void index_onehot_kernel(const void* __restrict__ labels, float* __restrict__ out, int64_t B, int C, int64_t S) {
+    const int64_t total = B * S;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        const int64_t b = idx / S, s = idx - b * S;
+        const int l = BYTES == 1 ? (int)reinterpret_cast<const uint8_t*>(labels)[idx] : reinterpret_cast<const int*>(labels)[idx];
+        float* o = out + b * C * S + s;
+        for (int c = 0; c < C; ++c) o[c * S] = l == c ? 1.0f : 0.0f;
+    }
+}
+
+// out[b][s][0..2] = colormap[argmax_c nhot[b][c][s]] (colormap == NULL: the index itself, three times); the arg-max as torch.argmax takes it (case_tail_beats)
+__global__ __launch_bounds__(256) void onehot_colormap_kernel(const float* __restrict__ nhot, const uint8_t* __restrict__ colormap, uint8_t* __restrict__ out,
+                                                              int64_t B, int C, int64_t S) {
+    const int64_t total = B * S;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        const int64_t b = idx / S, s = idx - b * S;
+        const float* src = nhot + b * C * S + s;
+        float best = src[0]; int k = 0;
+        for (int c = 1; c < C; ++c) {
+            const float v = src[c * S];
+            if (case_tail_beats(v, best)) { best = v; k = c; }
+        }
+        uint8_t* o = out + idx * 3;
+        if (colormap) { o[0] = colormap[3 * k]; o[1] = colormap[3 * k + 1]; o[2] = colormap[3 * k + 2]; }
+        else { o[0] = o[1] = o[2] = (uint8_t)k; }
+    }
+}
+
+__global__ __launch_bounds__(256) void onehot_tail_init_kernel(int* __restrict__ counts, int n) {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) counts[i] = 0;
+}
+
+// The evaluation tail of a one-hot task: soft [B][C][S], gt [B][S] index labels (bytes).  blockIdx.y = image; within it the scheme of brats_case_tail_kernel: a thread
+// owns four consecutive pixels per trip of the grid-stride loop, VEC as there (S % 4 == 0 and every operand aligned: a class's quad is one 16-byte load, the four
+// ground-truth bytes one dword, the four labels one dword store, the four colours three).  Per class c = 1..C-1: pred = soft[c] >= T (a NaN is off), gt = (label == c);
+// the pixel's label is the lowest class that is on, 0 when none is.  MAXC as in infer.hip: constant trip counts under `c < C`, so the 3 (MAXC - 1) counters of a
+// thread stay in registers.  counts == NULL: gt is not read; labels == NULL and rgb == NULL: nothing is stored (all three conditions are uniform over the grid).
+template <int MAXC, bool VEC>
+__global__ __launch_bounds__(CT_THREADS) void onehot_case_tail_kernel(const float* __restrict__ soft, const uint8_t* __restrict__ gt,
+                                                                      const uint8_t* __restrict__ colormap, int* __restrict__ counts, uint8_t* __restrict__ labels,
+                                                                      uint8_t* __restrict__ rgb, int C, int64_t S, float T) {
+    __shared__ int red[CT_WAVES][3 * (MAXC - 1)];
+    __shared__ uint32_t cmap[MAXC];                                             // r | g << 8 | b << 16 per class
+    const int64_t b = blockIdx.y;
+    soft += b * C * S;
+    if (rgb) {
+        if (threadIdx.x < C) cmap[threadIdx.x] = colormap[3 * threadIdx.x] | ((uint32_t)colormap[3 * threadIdx.x + 1] << 8) | ((uint32_t)colormap[3 * threadIdx.x + 2] << 16);
+        __syncthreads();
+    }
+    int ci[MAXC - 1], cp[MAXC - 1], cg[MAXC - 1];
+#pragma unroll
+    for (int c = 0; c < MAXC - 1; ++c) { ci[c] = 0; cp[c] = 0; cg[c] = 0; }
+    const int64_t quads = (S + 3) >> 2;
+    for (int64_t q = (int64_t)blockIdx.x * CT_THREADS + threadIdx.x; q < quads; q += (int64_t)gridDim.x * CT_THREADS) {
+        const int64_t s = q << 2;
+        const int n = VEC ? 4 : (int)i64min(4, S - s);
+        int g[4] = {0, 0, 0, 0};                                                // class 0 is not counted: a cut quad's missing pixels count nowhere
+        if (counts) {
+            if (VEC) {
+                const uint32_t l = *reinterpret_cast<const uint32_t*>(gt + b * S + s);
+                g[0] = l & 255; g[1] = (l >> 8) & 255; g[2] = (l >> 16) & 255; g[3] = l >> 24;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (j < n) g[j] = gt[b * S + s + j];
+            }
+        }
+        unsigned lab[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int c = 1; c < MAXC; ++c) {
+            if (c < C) {
+                float v[4] = {0.f, 0.f, 0.f, 0.f};
+                if (VEC) {
+                    const float4 a = *reinterpret_cast<const float4*>(soft + c * S + s);
+                    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (j < n) v[j] = soft[c * S + s + j];
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int on = (j < n) & (v[j] >= T), hit = g[j] == c;
+                    ci[c - 1] += on & hit; cp[c - 1] += on; cg[c - 1] += hit;
+                    if (on && lab[j] == 0) lab[j] = c;
+                }
+            }
+        }
+        if (labels) {
+            if (VEC) {
+                *reinterpret_cast<uint32_t*>(labels + b * S + s) = lab[0] | (lab[1] << 8) | (lab[2] << 16) | (lab[3] << 24);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (j < n) labels[b * S + s + j] = (uint8_t)lab[j];
+            }
+        }
+        if (rgb) {
+            const uint32_t k0 = cmap[lab[0]], k1 = cmap[lab[1]], k2 = cmap[lab[2]], k3 = cmap[lab[3]];
+            uint8_t* o = rgb + (b * S + s) * 3;
+            if (VEC) {                                                          // 12 bytes: r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+                uint32_t* o4 = reinterpret_cast<uint32_t*>(o);
+                o4[0] = k0 | (k1 << 24); o4[1] = (k1 >> 8) | (k2 << 16); o4[2] = (k2 >> 16) | (k3 << 8);
+            } else {
+                const uint32_t k[4] = {k0, k1, k2, k3};
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (j < n) { o[3 * j] = (uint8_t)k[j]; o[3 * j + 1] = (uint8_t)(k[j] >> 8); o[3 * j + 2] = (uint8_t)(k[j] >> 16); }
+            }
+        }
+    }
+    if (counts) {                                                               // wave -> LDS -> one atomic add per counter per workgroup
+        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+        for (int c = 0; c < MAXC - 1; ++c) {
+            if (c < C - 1) {
+                const int a = wave_sum_int(ci[c]), p = wave_sum_int(cp[c]), h = wave_sum_int(cg[c]);
+                if (lane == 0) { red[wave][3 * c] = a; red[wave][3 * c + 1] = p; red[wave][3 * c + 2] = h; }
+            }
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < 3 * (C - 1)) {
+            int t = 0;
+#pragma unroll
+            for (int w = 0; w < CT_WAVES; ++w) t += red[w][threadIdx.x];
+            if (t) atomicAdd(counts + b * 3 * (C - 1) + threadIdx.x, t);
+        }
+    }
+}
+
 }  // namespace segx
 
 using namespace segx;
@@ -271,4 +404,51 @@ extern "C" int segx_brats_case_tail(const float* soft, const float* hard, const 
     if (vec) hipLaunchKernelGGL(brats_case_tail_kernel<true>, grid, dim3(CT_THREADS), 0, stream, soft, hard, gt, counts, labels, S);
     else hipLaunchKernelGGL(brats_case_tail_kernel<false>, grid, dim3(CT_THREADS), 0, stream, soft, hard, gt, counts, labels, S);
     return check_launch("segx_brats_case_tail");
+}
+
+extern "C" int segx_index_onehot(const void* labels, int label_bytes, float* out, int64_t B, int C, int64_t S, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(labels && out, "segx_index_onehot: null pointer");
+    SEGX_REQUIRE(label_bytes == 1 || label_bytes == 4, "segx_index_onehot: labels are uint8 (1) or int32 (4), not %d bytes", label_bytes);
+    SEGX_REQUIRE(B > 0 && S > 0, "segx_index_onehot: B and S must be positive");
+    SEGX_REQUIRE(C >= 1 && C <= SEGX_MAX_CLASSES, "segx_index_onehot: C = %d is not in 1 .. %d", C, SEGX_MAX_CLASSES);
+    const dim3 grid((unsigned)i64min(65536, (B * S + 255) / 256));
+    if (label_bytes == 1) hipLaunchKernelGGL(index_onehot_kernel<1>, grid, dim3(256), 0, stream, labels, out, B, C, S);
+    else hipLaunchKernelGGL(index_onehot_kernel<4>, grid, dim3(256), 0, stream, labels, out, B, C, S);
+    return check_launch("segx_index_onehot");
+}
+
+extern "C" int segx_onehot_colormap(const float* nhot, const uint8_t* colormap, uint8_t* out, int64_t B, int C, int64_t S, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(nhot && out, "segx_onehot_colormap: null nhot or out");
+    SEGX_REQUIRE(B > 0 && S > 0, "segx_onehot_colormap: B and S must be positive");
+    SEGX_REQUIRE(C >= 1 && C <= SEGX_MAX_CLASSES, "segx_onehot_colormap: C = %d is not in 1 .. %d", C, SEGX_MAX_CLASSES);
+    hipLaunchKernelGGL(onehot_colormap_kernel, dim3((unsigned)i64min(65536, (B * S + 255) / 256)), dim3(256), 0, stream, nhot, colormap, out, B, C, S);
+    return check_launch("segx_onehot_colormap");
+}
+
+template <int MAXC>
+static void launch_onehot_case_tail(bool vec, dim3 grid, hipStream_t stream, const float* soft, const uint8_t* gt, const uint8_t* colormap, int32_t* counts,
+                                    uint8_t* labels, uint8_t* rgb, int C, int64_t S, float T) {
+    if (vec) hipLaunchKernelGGL((onehot_case_tail_kernel<MAXC, true>), grid, dim3(CT_THREADS), 0, stream, soft, gt, colormap, counts, labels, rgb, C, S, T);
+    else hipLaunchKernelGGL((onehot_case_tail_kernel<MAXC, false>), grid, dim3(CT_THREADS), 0, stream, soft, gt, colormap, counts, labels, rgb, C, S, T);
+}
+
+extern "C" int segx_onehot_case_tail(const float* soft, const uint8_t* gt, const uint8_t* colormap, int32_t* counts, uint8_t* labels, uint8_t* rgb, int B, int C,
+                                     int64_t S, float T, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(soft, "segx_onehot_case_tail: null soft");
+    SEGX_REQUIRE(counts || labels || rgb, "segx_onehot_case_tail: none of counts, labels and rgb asked for");
+    SEGX_REQUIRE(!counts || gt, "segx_onehot_case_tail: counts need the ground truth");
+    SEGX_REQUIRE(!rgb || colormap, "segx_onehot_case_tail: rgb needs the colormap");
+    SEGX_REQUIRE(B > 0 && B <= 65535, "segx_onehot_case_tail: B = %d is not in 1 .. 65535", B);
+    SEGX_REQUIRE(C >= 2 && C <= SEGX_MAX_CLASSES, "segx_onehot_case_tail: C = %d is not in 2 .. %d", C, SEGX_MAX_CLASSES);
+    SEGX_REQUIRE(S > 0 && S < ((int64_t)1 << 31), "segx_onehot_case_tail: S = %lld is not in 1 .. 2^31 - 1", (long long)S);
+    if (counts) {
+        const int n = B * 3 * (C - 1);
+        hipLaunchKernelGGL(onehot_tail_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, counts, n);
+    }
+    // a plane starts (b * C + c) * S floats into soft, an image b * S bytes into gt / labels and 3 * b * S into rgb: wide accesses are legal only when S % 4 == 0
+    const bool vec = S % 4 == 0 && (uintptr_t)soft % 16 == 0 && ((counts ? (uintptr_t)gt : 0) | (uintptr_t)labels | (uintptr_t)rgb) % 4 == 0;
+    const dim3 grid((unsigned)i64min(SEGX_CASE_TAIL_MAX_BLOCKS, ((S + 3) / 4 + CT_THREADS - 1) / CT_THREADS), (unsigned)B);
+    if (C <= 8) launch_onehot_case_tail<8>(vec, grid, stream, soft, gt, colormap, counts, labels, rgb, C, S, T);
+    else launch_onehot_case_tail<SEGX_MAX_CLASSES>(vec, grid, stream, soft, gt, colormap, counts, labels, rgb, C, S, T);
+    return check_launch("segx_onehot_case_tail");
 }

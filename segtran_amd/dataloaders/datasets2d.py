@@ -1,6 +1,38 @@
-"""On-device label maps of the 2D train step and of the evaluation's export (mirror of reference code/dataloaders/datasets2d.py:90-171, 200-250).
+"""On-device label maps of the 2D train step and of the evaluation's export (mirror of reference code/dataloaders/datasets2d.py:22-171, 200-250).
 Only the in-step label -> n-hot maps and the n-hot -> pixel-value maps are built; file I/O and imgaug pipelines are out of scope."""
 import torch
+
+
+def index_to_onehot(mask, num_classes):
+    """reference datasets2d.py:22-51 for tensors: an integer index mask [B, 1, H, W], [B, H, W] or [H, W] -> float32 one-hot maps with the class dimension first
+    ([C, H, W]) or after the batch ([B, C, H, W]).  On the device this is segx_index_onehot; for CPU tensors the torch expression below states it.  A label outside
+    0 .. num_classes - 1 sets no class (the reference's scatter_ raises there)."""
+    if mask.dim() == 4 and mask.shape[1] == 1:
+        lab = mask[:, 0]
+    elif mask.dim() in (2, 3):
+        lab = mask if mask.dim() == 3 else mask.unsqueeze(0)
+    else:
+        raise ValueError('index_to_onehot: an index mask [B, 1, H, W], [B, H, W] or [H, W], not %s' % (tuple(mask.shape),))
+    if lab.is_cuda:
+        from .. import functional as SF
+        out = SF.index_onehot(lab, num_classes)
+    else:
+        classes = torch.arange(num_classes, device=lab.device).view(1, num_classes, 1, 1)
+        out = (lab.long().unsqueeze(1) == classes).float()
+    return out[0] if mask.dim() == 2 else out
+
+
+def onehot_inv_map(mask_onehot, colormap=None):
+    """reference datasets2d.py:54-88: n-hot maps [B, C, H, W] or [C, H, W] -> [..., H, W, 3]: the arg-max over the classes (the lowest index wins a tie) looked up
+    in colormap ([C, 3] colours 0 .. 255: uint8 result) or, without one, repeated three times (int64 result, as the reference returns).  segx_onehot_colormap."""
+    from .. import functional as SF
+    if mask_onehot.dim() not in (3, 4):
+        raise ValueError('onehot_inv_map: n-hot maps [C, H, W] or [B, C, H, W], not %s' % (tuple(mask_onehot.shape),))
+    batched = mask_onehot.dim() == 4
+    out = SF.onehot_colormap(mask_onehot if batched else mask_onehot.unsqueeze(0), colormap)
+    if colormap is None:
+        out = out.long()
+    return out if batched else out[0]
 
 
 def fundus_map_mask(mask, exclusive=False):

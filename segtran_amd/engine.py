@@ -8,8 +8,8 @@ import torch.nn.functional as F
 from . import functional as SF
 from . import segx
 from .optimization import BertAdam
-from .synth import load_synth, synth_image2d, synth_fundus_mask, synth_brats
-from .dataloaders.datasets2d import fundus_map_mask, polyp_map_mask
+from .synth import load_synth, synth_image2d, synth_fundus_mask, synth_oct_mask, synth_brats
+from .dataloaders.datasets2d import fundus_map_mask, polyp_map_mask, index_to_onehot
 from .dataloaders.datasets3d import brats_map_label
 
 # the BASELINE.json configs (flags as in SURVEY.md 8(d)); 'bs' = per-GPU batch of the benchmark
@@ -20,7 +20,8 @@ CONFIGS = {
     'cfg4': dict(dim=3, task='brats', num_classes=4, translayers=1, compress=[1, 1], attractors=1024, bs=4, size=(112, 112, 96)),
     'cfg5': dict(dim=3, task='brats', num_classes=4, translayers=2, compress=[1, 1, 1], attractors=1024, bs=4, size=(128, 128, 128)),
 }
-BCE_WEIGHT = {'fundus': [0., 1., 2.], 'polyp': [0., 1.], 'brats': [0., 3., 1., 1.75]}   # train2d.py:293,344; train3d.py:223
+BCE_WEIGHT = {'fundus': [0., 1., 2.], 'polyp': [0., 1.], 'brats': [0., 3., 1., 1.75],   # train2d.py:293,344; train3d.py:223
+              'oct': [0.] + [1.] * 9}                                                    # train2d.py:369-371 (10 retinal-layer classes)
 DEFAULTS = dict(lr=2e-4, decay=1e-4, grad_clip=0.1, dropout_prob=0.2, num_modes=4)        # train2d.py:266-385 (segtran)
 
 
@@ -114,11 +115,17 @@ def init_optimizer(net, c_or_task, t_total=10000, warmup_steps=500, lr=None, dec
                     global_grad_clip=DEFAULTS['grad_clip'] if grad_clip is None else grad_clip)
 
 
-def loss_weights(task, device):
+def loss_weights(task, device, focus_class=-1):
+    """(pos_weight, class_w) of the BCE and Dice terms; focus_class (train2d.py --focus): that class weighs 2 in class_w when the task has more than 2 classes"""
     w = torch.tensor(BCE_WEIGHT[task], dtype=torch.float32)
     nc = len(BCE_WEIGHT[task])
     pos_weight = (w * (nc - 1) / w.sum()).to(device)                           # train2d.py:813-814
-    cw = torch.ones(nc); cw[0] = 0; cw = (cw / cw.sum()).to(device)           # train2d.py:1123-1127
+    cw = torch.ones(nc); cw[0] = 0
+    if focus_class != -1 and nc > 2:                                           # train2d.py:1125-1126
+        if not -nc <= focus_class < nc:
+            raise ValueError('focus_class %d is no class of the %d-class task %r' % (focus_class, nc, task))
+        cw[focus_class] = 2
+    cw = (cw / cw.sum()).to(device)                                            # train2d.py:1123-1127
     return pos_weight, cw
 
 
@@ -126,9 +133,11 @@ def synth_batch(cfg, B, device, seed=1337):
     """(input, raw mask/label) in the encodings the reference's loaders deliver, resident on `device`."""
     c = CONFIGS[cfg] if isinstance(cfg, str) else cfg
     if c['dim'] == 2:
-        S = c['size'][0]
-        x = synth_image2d(B, S, seed)
-        m = synth_fundus_mask(B, S, seed + 1)
+        H, W = c['size']
+        x = synth_image2d(B, H, seed, W)
+        if c['task'] == 'oct':                               # index mask [B, 1, H, W]: stacked bands, every class present
+            return x.to(device), synth_oct_mask(B, H, W, c['num_classes'], seed + 1).to(device)
+        m = synth_fundus_mask(B, H, seed + 1, W)
         if c['task'] == 'polyp':
             m = m[:, :1].repeat(1, 3, 1, 1)
         return x.to(device), m.to(device)
@@ -140,6 +149,8 @@ def map_mask(task, raw, exclusive=False):
     """In-step label -> n-hot map.  On the GPU this is libsegx's label kernel; the torch expressions in
     segtran_amd/dataloaders (same semantics, used by CPU-side tooling) are the readable statement of it.
     exclusive: train2d.py --exclusive (fundus only, datasets2d.py:110-111)."""
+    if task == 'oct':                                        # train2d.py:1177-1178; the class count is the task's
+        return index_to_onehot(raw, len(BCE_WEIGHT['oct']))
     if raw.is_cuda:
         return SF.label_nhot(raw, task, exclusive)
     if task == 'fundus':
@@ -152,8 +163,8 @@ def map_mask(task, raw, exclusive=False):
 class TrainStep:
     """One data-parallel train step (train2d.py:1147-1337 / train3d.py:708-768 for --net segtran)."""
 
-    def __init__(self, net, optimizer, task, reducer=None, dice_w=0.5, exclusive=False, augment=None):
-        """dice_w: args.MAX_DICE_W (train2d.py:1223 / train3d.py:735, --diceweight); exclusive: --exclusive fundus masks;
+    def __init__(self, net, optimizer, task, reducer=None, dice_w=0.5, exclusive=False, augment=None, focus_class=-1):
+        """dice_w: args.MAX_DICE_W (train2d.py:1223 / train3d.py:735, --diceweight); exclusive: --exclusive fundus masks; focus_class: --focus (loss_weights);
         augment: optional callable (x, nhot_mask) -> (x, nhot_mask) applied on the device before the forward pass
         (train3d.py:713-715 RandomResizedCrop under --randscale)."""
         self.net, self.opt, self.task, self.reducer = net, optimizer, task, reducer
@@ -161,7 +172,7 @@ class TrainStep:
         if reducer is None and hasattr(optimizer, 'release_flat_grads') and getattr(optimizer, '_tabs', None) is None:
             optimizer.release_flat_grads()          # single process: no flat bucket needed, no per-parameter accumulate kernels
         dev = next(net.parameters()).device
-        self.pos_weight, self.class_w = loss_weights(task, dev)
+        self.pos_weight, self.class_w = loss_weights(task, dev, focus_class)
         self.stats = None
         self._bs = None
 
@@ -244,7 +255,7 @@ class AdversarialTrainStep:
     reference's weight: loss = SUPERVISED_W * ((1 - DICE_W) ce + DICE_W dice) + DOMAIN_LOSS_W * domain + RECON_W * recon."""
 
     def __init__(self, net, optimizer, task, adversarial_mode, adda=False, discriminator_optim=None, supervised_w=1.0, domain_w=0.002, recon_w=0.0,
-                 dice_w=0.5, exclusive=False):
+                 dice_w=0.5, exclusive=False, focus_class=-1):
         if adversarial_mode and getattr(net, 'discriminator', None) is None:
             raise ValueError('attach_adversarial(net, ...) first: the network carries no discriminator')
         if adda and discriminator_optim is None:
@@ -255,7 +266,7 @@ class AdversarialTrainStep:
             if o is not None and hasattr(o, 'release_flat_grads') and getattr(o, '_tabs', None) is None:
                 o.release_flat_grads()
         dev = next(net.parameters()).device
-        self.pos_weight, self.class_w = loss_weights(task, dev)
+        self.pos_weight, self.class_w = loss_weights(task, dev, focus_class)
         self.stats = self.parts = None
 
     def __call__(self, image, raw_mask, target_unsup_image, source_image):

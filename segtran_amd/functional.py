@@ -2256,9 +2256,13 @@ def bridge_mask(batch, weight, bias, pool):
     return out
 
 
-def label_nhot(labels, mode, exclusive=False):
+def label_nhot(labels, mode, exclusive=False, num_classes=None):
     """mode 'fundus' | 'polyp' (uint8 [B,Cin,*S]) | 'brats' (integer [B,*S]) -> float n-hot [B,C,*S].
-    exclusive (fundus only, train2d.py --exclusive): the disc channel excludes the cup (datasets2d.py:110-111)."""
+    exclusive (fundus only, train2d.py --exclusive): the disc channel excludes the cup (datasets2d.py:110-111).
+    mode 'oct': index masks [B,1,H,W] / [B,H,W] -> one-hot [B,num_classes,H,W] (index_onehot; num_classes defaults to the task's 10)."""
+    if mode == 'oct':
+        lab = labels[:, 0] if labels.dim() == 4 else labels
+        return index_onehot(lab, 10 if num_classes is None else num_classes)
     L = segx.lib()
     m = {'fundus': 0, 'polyp': 1, 'brats': 2}[mode]
     if m == 0 and exclusive:
@@ -2582,6 +2586,129 @@ def brats_case_tail(soft, hard, gt=None, want_labels=True, counts=None, labels=N
         raise ValueError('brats_case_tail: nothing to compute (no gt and want_labels=False)')
     segx.lib().brats_case_tail(soft, hard, gt if counts is not None else None, counts, labels, S)
     return counts, labels
+
+
+# -------------------------------------------------------------------------------------------------
+# One-hot tasks (metrics.hip; the OCT task): index masks -> one-hot floats, n-hot maps -> colours, and the evaluation tail in one pass.  Forward only, no copy to the
+# host and no synchronisation.
+# -------------------------------------------------------------------------------------------------
+def _class_count(what, C, low=1):
+    if int(C) != C or not low <= int(C) <= segx.SegxLib.MAX_CLASSES:
+        raise ValueError('%s: %r classes, not %d .. %d' % (what, C, low, segx.SegxLib.MAX_CLASSES))
+    return int(C)
+
+
+def index_onehot(labels, num_classes):
+    """float32 [B, num_classes, *spatial] from an integer index mask [B, *spatial] (segx_index_onehot): out[b, c] = (labels[b] == c).  uint8 and int32 masks are read
+    as they are, other integer types are converted to int32 first.  A label outside 0 .. num_classes - 1 sets no class (the reference's scatter_ raises there)."""
+    _no_grad_operands('index_onehot', labels)
+    C = _class_count('index_onehot', num_classes)
+    if labels.dim() < 2:
+        raise ValueError('index_onehot: an index mask [B, *spatial], not rank %d' % labels.dim())
+    if labels.is_floating_point() or labels.is_complex() or labels.dtype == torch.bool:
+        raise TypeError('index_onehot: an integer index mask, not %s' % labels.dtype)
+    lab = _c(labels.detach() if labels.dtype in (torch.uint8, torch.int32) else labels.detach().to(torch.int32))
+    B = lab.shape[0]
+    if lab.numel() == 0:
+        raise ValueError('index_onehot: empty tensor %s' % (tuple(labels.shape),))
+    out = torch.empty((B, C) + tuple(lab.shape[1:]), dtype=torch.float32, device=lab.device)
+    segx.lib().index_onehot(lab, lab.element_size(), out, B, C, lab.numel() // B)
+    return out
+
+
+_COLOR_TABLES = {}
+
+
+def _color_table(what, colormap, C, device):
+    """the uint8 [C, 3] device table of a colormap given as a tensor (used as it is when it already is one) or as C (r, g, b) triples (built once per device and kept)"""
+    if isinstance(colormap, torch.Tensor):
+        if colormap.dim() != 2 or colormap.shape[1] != 3 or colormap.shape[0] < C:
+            raise ValueError('%s: colormap %s is no [C, 3] table with C >= %d' % (what, tuple(colormap.shape), C))
+        if colormap.dtype == torch.uint8 and colormap.device == device and colormap.is_contiguous():
+            return colormap
+        if colormap.is_floating_point():
+            raise TypeError('%s: colormap holds integer colours 0 .. 255, not %s' % (what, colormap.dtype))
+        return _c(colormap.to(device=device, dtype=torch.uint8))
+    rows = tuple(tuple(_uint8_value(what + ': colormap', v) for v in row) for row in colormap)
+    if len(rows) < C or any(len(r) != 3 for r in rows):
+        raise ValueError('%s: colormap needs %d (r, g, b) rows' % (what, C))
+    key = (rows, device)
+    table = _COLOR_TABLES.get(key)
+    if table is None:
+        table = _COLOR_TABLES[key] = torch.tensor(rows, dtype=torch.uint8, device=device)
+    return table
+
+
+def onehot_colormap(nhot, colormap=None):
+    """uint8 [B, *spatial, 3] from n-hot floats [B, C, *spatial] (segx_onehot_colormap): colormap[argmax over the classes], the lowest index winning a tie as in
+    torch.argmax; colormap None: the index itself in all three bytes.  colormap: a [C, 3] tensor of colours 0 .. 255 (a uint8 tensor on the device is read in place)
+    or C (r, g, b) triples."""
+    _no_grad_operands('onehot_colormap', nhot)
+    if nhot.dim() < 3:
+        raise ValueError('onehot_colormap: [B, C, *spatial] maps, not rank %d' % nhot.dim())
+    B, C = nhot.shape[:2]
+    C = _class_count('onehot_colormap', C)
+    x = _c(nhot.detach().float())
+    if x.numel() == 0:
+        raise ValueError('onehot_colormap: empty tensor %s' % (tuple(nhot.shape),))
+    table = None if colormap is None else _color_table('onehot_colormap', colormap, C, x.device)
+    out = torch.empty((B,) + tuple(x.shape[2:]) + (3,), dtype=torch.uint8, device=x.device)
+    segx.lib().onehot_colormap(x, table, out, B, C, x[0, 0].numel())
+    return out
+
+
+def onehot_case_tail(soft, gt=None, colormap=None, T=0.5, want_labels=True, counts=None, labels=None, rgb=None):
+    """The evaluation tail of a one-hot task in one launch (segx_onehot_case_tail): soft float32 [B, C, *spatial] as window_merge leaves it; gt: the index mask
+    [B, *spatial] (converted to uint8 when it is not), or None.  Returns (counts, labels, rgb):
+      counts int32 [B, C - 1, 3] -- per image and foreground class {sum pred * gt, sum pred, sum gt} with pred = soft[:, c] >= T and gt = (mask == c); None without gt;
+      labels uint8 [B, *spatial] -- the lowest class >= 1 that is on, 0 where none is: onehot_inv_map(harden_segmap2d(soft)) as indices; None with want_labels=False;
+      rgb uint8 [B, *spatial, 3] -- colormap[labels]; None without a colormap (a [C, 3] tensor or C triples, as onehot_colormap takes it).
+    counts / labels / rgb: tensors to write into (a captured graph passes its static ones); passing `labels` asks for them.  Forward only."""
+    _no_grad_operands('onehot_case_tail', soft)
+    if soft.dim() < 3 or soft.dtype != torch.float32:
+        raise ValueError('onehot_case_tail: soft %s %s must be a float32 [B, C, *spatial] tensor' % (soft.dtype, tuple(soft.shape)))
+    B, C = soft.shape[:2]
+    C = _class_count('onehot_case_tail', C, low=2)
+    spatial = tuple(soft.shape[2:])
+    S = soft[0, 0].numel() if B else 0
+    if B < 1 or S < 1:
+        raise ValueError('onehot_case_tail: empty tensor %s' % (tuple(soft.shape),))
+    soft = _c(soft.detach())
+    dev = soft.device
+    if gt is None:
+        if counts is not None:
+            raise ValueError('onehot_case_tail: counts need gt')
+    else:
+        if tuple(gt.shape) != (B,) + spatial:
+            raise ValueError('onehot_case_tail: gt %s is not the index mask %s' % (tuple(gt.shape), (B,) + spatial))
+        if gt.is_floating_point() or gt.dtype == torch.bool:
+            raise TypeError('onehot_case_tail: gt is an integer index mask, not %s' % gt.dtype)
+        if gt.dtype != torch.uint8:
+            gt = gt.detach().clamp(-1, 255).to(torch.uint8)           # -1 -> 255: outside every class, as any label >= C
+        gt = _c(gt.detach())
+        if counts is None:
+            counts = torch.empty(B, C - 1, 3, dtype=torch.int32, device=dev)
+        elif counts.dtype != torch.int32 or tuple(counts.shape) != (B, C - 1, 3) or not counts.is_contiguous():
+            raise ValueError('onehot_case_tail: counts is a contiguous int32 [%d, %d, 3] tensor' % (B, C - 1))
+    if labels is not None:
+        if labels.dtype != torch.uint8 or tuple(labels.shape) != (B,) + spatial or not labels.is_contiguous():
+            raise ValueError('onehot_case_tail: labels is a contiguous uint8 %s tensor' % ((B,) + spatial,))
+    elif want_labels:
+        labels = torch.empty((B,) + spatial, dtype=torch.uint8, device=dev)
+    table = None
+    if colormap is None:
+        if rgb is not None:
+            raise ValueError('onehot_case_tail: rgb needs a colormap')
+    else:
+        table = _color_table('onehot_case_tail', colormap, C, dev)
+        if rgb is None:
+            rgb = torch.empty((B,) + spatial + (3,), dtype=torch.uint8, device=dev)
+        elif rgb.dtype != torch.uint8 or tuple(rgb.shape) != (B,) + spatial + (3,) or not rgb.is_contiguous():
+            raise ValueError('onehot_case_tail: rgb is a contiguous uint8 %s tensor' % ((B,) + spatial + (3,),))
+    if counts is None and labels is None and rgb is None:
+        raise ValueError('onehot_case_tail: nothing to compute (no gt, no colormap and want_labels=False)')
+    segx.lib().onehot_case_tail(soft, gt if counts is not None else None, table, counts, labels, rgb, B, C, S, T)
+    return counts, labels, rgb
 
 
 # -------------------------------------------------------------------------------------------------

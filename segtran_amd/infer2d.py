@@ -2,7 +2,8 @@
 (one gather launch, the network on stacked windows, one merge launch) and that form captured as one replayable hipGraph (GraphedSlidingWindow).
 
 test_util2d.py mirrors the reference's file of that name and keeps the reference's signatures; the switch lives here.  So does the tail of the evaluation after
-preds_soft: calc_vcdr, calc_batch_metric with the vCDR-error column, remove_fragmentary_segs, export_masks.  fold_bn=True folds the (eval-mode) net for
+preds_soft: calc_vcdr, calc_batch_metric with the vCDR-error column, remove_fragmentary_segs, export_masks; and the one-hot tasks' form of it
+(DESIGN.md 5t): calc_batch_metric_onehot and test_all_cases(gt_is_index=True), which work from index masks through one tail launch.  fold_bn=True folds the (eval-mode) net for
 the call if it is not folded already (Segtran2d.fold_batchnorm) and unfolds it afterwards; a net the caller folded stays folded."""
 import contextlib
 import math
@@ -193,11 +194,52 @@ def remove_fragmentary_segs(segmap, bg_value):
     return SF.remove_fragments(segmap, bg_value)
 
 
+def _index_mask(what, preds_soft, gt_index):
+    """the index mask as [B, H, W] next to preds_soft [B, C, H, W]"""
+    if not isinstance(preds_soft, torch.Tensor) or preds_soft.dim() != 4:
+        raise ValueError('%s: preds_soft is a [B, C, H, W] tensor' % what)
+    gt = gt_index[:, 0] if gt_index.dim() == 4 and gt_index.shape[1] == 1 else gt_index
+    if gt.dim() != 3 or gt.shape[0] != preds_soft.shape[0]:
+        raise ValueError('%s: an index mask [B, H, W] or [B, 1, H, W] for %d images, not %s' % (what, preds_soft.shape[0], tuple(gt_index.shape)))
+    return gt
+
+
+def _onehot_counts(preds_soft, gt, num_classes):
+    """int32 [B, C - 1, 3] on the device: {sum pred * gt, sum pred, sum gt} per image and foreground class (SF.onehot_case_tail); preds_soft is resampled to the
+    mask's size first when it differs, as calc_batch_metric does"""
+    if preds_soft.shape[1] != num_classes:
+        raise ValueError('preds_soft has %d classes, not %d' % (preds_soft.shape[1], num_classes))
+    if tuple(preds_soft.shape[2:]) != tuple(gt.shape[1:]):
+        preds_soft = SF.interp_linear(preds_soft.contiguous(), tuple(gt.shape[1:]))
+    return SF.onehot_case_tail(preds_soft.float(), gt, want_labels=False)[0]
+
+
+def calc_batch_metric_onehot(preds_soft, gt_index, num_classes):
+    """calc_batch_metric (reference test_util2d.py:241-265) for a one-hot task, from the index mask: preds_soft [B, C, H, W], gt_index [B, H, W] or [B, 1, H, W]
+    integer labels.  One launch forms the integer counts {I, Z, Y} = {sum pred * gt, sum pred, sum gt} of every image and class (the hardened maps and the
+    one-hot mask never exist), ONE read brings them to the host, and Dice is calc_dice's expression (2 I + 1e-5) / (Z + Y + 1e-5) in float32.  0 / 1 maps square to
+    themselves and float32 holds every integer below 2^24, so the table equals the reference's exactly while a plane has fewer than 2^24 pixels.
+    Returns the float64 [B, C - 1] table."""
+    np = _T2.np
+    with torch.no_grad():
+        counts = _onehot_counts(preds_soft, _index_mask('calc_batch_metric_onehot', preds_soft, gt_index), num_classes)
+    c = counts.cpu().numpy().astype(np.float32)
+    smooth = np.float32(1e-5)
+    return ((np.float32(2) * c[..., 0] + smooth) / (c[..., 1] + c[..., 2] + smooth)).astype(np.float64)
+
+
 def test_all_cases(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, mask_prepred_mapping_func=None, fold_bn=False, fused=False,
-                   window_batch=None, precision='fp32', do_calc_vcdr_error=False):
+                   window_batch=None, precision='fp32', do_calc_vcdr_error=False, gt_is_index=False):
     """test_util2d.test_all_cases; fold_bn: ONE fold for all the batches; fused / window_batch / precision: as test_single_batch; do_calc_vcdr_error: the vCDR
-    error as one more entry (both returned vectors then have num_classes entries, as in the reference)."""
+    error as one more entry (both returned vectors then have num_classes entries, as in the reference).
+    gt_is_index (one-hot tasks: oct): the masks are index masks [B, H, W] / [B, 1, H, W] and stay so -- no mapping function, no one-hot mask, no hardened map; each
+    batch's Dice rows are formed on the device from the integer counts of SF.onehot_case_tail (calc_dice's expression in float32) and stay there; they are read
+    ONCE after the last batch and summed as the default path sums its tables."""
+    if gt_is_index and (do_calc_vcdr_error or mask_prepred_mapping_func is not None):
+        raise ValueError('test_all_cases: gt_is_index takes the index masks as they are (no mask_prepred_mapping_func) and has no vCDR column')
     with _precision(precision), _folded(net, fold_bn):
+        if gt_is_index:
+            return _test_all_cases_index(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, fused, window_batch)
         if not fused and not do_calc_vcdr_error:
             return _T2.test_all_cases(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, mask_prepred_mapping_func)
         np = _T2.np
@@ -210,11 +252,29 @@ def test_all_cases(net, batches, task_name, num_classes, orig_input_size, patch_
         return total / np.maximum(count, 1), count
 
 
+def _test_all_cases_index(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, fused, window_batch):
+    np = _T2.np
+    rows, smooth = [], 1e-5
+    for image_batch, mask_batch in batches:
+        _, preds_soft = test_single_batch(net, image_batch, orig_input_size, patch_size, stride, task_name, num_classes, fused=fused, window_batch=window_batch)
+        with torch.no_grad():
+            c = _onehot_counts(preds_soft, _index_mask('test_all_cases', preds_soft, mask_batch), num_classes).float()
+            rows.append((2 * c[..., 0] + smooth) / (c[..., 1] + c[..., 2] + smooth))          # SF.dice_scores' expression on the same sums
+    total, count = np.zeros(num_classes - 1), 0
+    if rows:
+        sizes = [len(r) for r in rows]
+        table = torch.cat(rows).cpu().numpy().astype(np.float64)                                # the one read
+        for m in np.split(table, np.cumsum(sizes)[:-1]):
+            total += m.sum(axis=0); count += len(m)
+    return total / max(count, 1), count
+
+
 def export_masks(preds_soft, unscaled_sizes, inv_map, remove_frag=False, bg_value=255):
     """The arithmetic of the reference's save loop (test_util2d.py:93-106, and test2d.py's --removefrag) without the files: per image i, preds_soft[i] [C, H, W] is
     resampled to unscaled_sizes[i] = (H0, W0) (interp_linear), hardened (harden_segmap2d), mapped to pixel values by inv_map (fundus_inv_map_mask /
-    polyp_inv_map_mask of dataloaders.datasets2d) and, with remove_frag, cleaned by remove_fragmentary_segs(., bg_value).  Returns the list of uint8 [H0, W0]
-    device tensors; writing them in an image format is the caller's."""
+    polyp_inv_map_mask of dataloaders.datasets2d, or functools.partial(onehot_inv_map, colormap=...) for a one-hot task: test2d.py:640-649) and, with remove_frag,
+    cleaned by remove_fragmentary_segs(., bg_value).  Returns the list of uint8 [H0, W0] device tensors ([H0, W0, 3] from onehot_inv_map; fragment removal is
+    defined on single-channel label images and refuses those); writing them in an image format is the caller's."""
     if len(unscaled_sizes) != len(preds_soft):
         raise ValueError('export_masks: %d sizes for %d predictions' % (len(unscaled_sizes), len(preds_soft)))
     out = []
@@ -225,6 +285,8 @@ def export_masks(preds_soft, unscaled_sizes, inv_map, remove_frag=False, bg_valu
             if (H0, W0) != tuple(soft.shape[2:]):
                 soft = SF.interp_linear(soft, (H0, W0))
             mask = inv_map(harden_segmap2d(soft[0]))
+            if remove_frag and mask.dim() != 2:
+                raise ValueError('export_masks: remove_frag works on single-channel label images, not on the %s result of this inv_map' % (tuple(mask.shape),))
             out.append(remove_fragmentary_segs(mask, bg_value) if remove_frag else mask)
     return out
 

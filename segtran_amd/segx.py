@@ -627,6 +627,19 @@ class SegxLib:
         ref = next(t for t in (soft, hard, counts, labels, gt) if t is not None)       # a NULL operand is the library's to refuse: the stream comes from any tensor
         self._call('segx_brats_case_tail', ref, soft, hard, gt, counts, labels, S)
 
+    # ---- one-hot tasks (metrics.hip) ----------------------------------------------------------------------
+    MAX_CLASSES = 16                                     # SEGX_MAX_CLASSES of include/segx.h
+
+    def index_onehot(self, labels, label_bytes, out, B, C, S):
+        self._call('segx_index_onehot', out, labels, int(label_bytes), out, B, C, S)
+
+    def onehot_colormap(self, nhot, colormap, out, B, C, S):
+        self._call('segx_onehot_colormap', out, nhot, colormap, out, B, C, S)
+
+    def onehot_case_tail(self, soft, gt, colormap, counts, labels, rgb, B, C, S, T=0.5):
+        ref = next(t for t in (soft, counts, labels, rgb, gt, colormap) if t is not None)     # a NULL operand is the library's to refuse
+        self._call('segx_onehot_case_tail', ref, soft, gt, colormap, counts, labels, rgb, B, C, S, float(T))
+
     # ---- components, fragment removal, row extents, n-hot -> values (components.hip) --------------------
     CCL_TILE, CCL_MAX_PLANE = (32, 64), 1 << 30          # SEGX_CCL_TILE_H / _W, SEGX_CCL_MAX_PLANE of include/segx.h
 
@@ -842,6 +855,7 @@ _SIGS = {
     'segx_x6_presplit_elems': 'iiii', 'segx_x6_presplit': 'piilliillpp',
     'segx_tune': 'ii', 'segx_tune_get': 'i', 'segx_x3_launches': '', 'segx_gemm_route': 'pppp', 'segx_set_rng_base': 'p', 'segx_rng_advance': 'pup', 'segx_resized_crop3d': 'pplpp', 'segx_stem_compose_fwd': 'ppppiiiiip', 'segx_stem_compose_bwd': 'pppppppiiiiip', 'segx_bridge_input': 'ppiiiiiip', 'segx_stem_s2d_input': 'ppiiiiiip', 'segx_conv2d_stem_fwd': 'pppiiiiiiiiiiip', 'segx_conv2d_stem_im2col': 'ppiiiiiiiiiiip', 'segx_dropout': 'pplfuup', 'segx_avgpool2_fwd': 'ppliip', 'segx_avgpool2_bwd': 'ppliip', 'segx_transpose': 'ppliip', 'segx_interp_linear_fwd_axis': 'pppliilfp', 'segx_window_accum': 'pppiipp', 'segx_harden_segmap': 'ppppiilifp', 'segx_window_gather': 'ppppiiipp', 'segx_window_merge': 'pppppiiipifp', 'segx_dice_ws_floats': 'll', 'segx_dice_sums': 'pppllp',
     'segx_surface_border': 'ppliiiip', 'segx_edt_sq': 'ppliiip', 'segx_surface_hist': 'pppliiiip', 'segx_brats_case_tail': 'ppppplp',
+    'segx_index_onehot': 'piplilp', 'segx_onehot_colormap': 'ppplilp', 'segx_onehot_case_tail': 'ppppppiilfp',
     'segx_ccl2d': 'pippliip', 'segx_frag_keep2': 'ppliip', 'segx_frag_apply': 'ppppliiip', 'segx_row_extent': 'ppliifp', 'segx_nhot_to_values': 'ppplilp',
     'segx_conv3d_fwd': 'pppiipipp', 'segx_conv3d_fwd_packed': 'pppiipipp', 'segx_conv3d_fwd_packed_bs': 'pppiipipllp', 'segx_conv3d_bwd_weight_packed_bs': 'pppiipipllp', 'segx_conv3d_pack_weights': 'ppiiiip', 'segx_conv3d_splitk': 'iipi', 'segx_conv3d_route': 'iipiiiip', 'segx_conv3d_fwd_terms': 'iipiii', 'segx_conv3d_flip_weights': 'ppiiip', 'segx_conv3d_bwd_weight': 'pppiipipp', 'segx_conv3d_bwd_weight_packed': 'pppiipipp', 'segx_conv3d_unpack_wgrad': 'ppiiip',
     'segx_conv3d_halo_ok': 'iip', 'segx_conv3d_halo_wq_floats': 'ii', 'segx_conv3d_halo_pack': 'ppiiip', 'segx_conv3d_halo_fwd': 'pppiipllip', 'segx_conv3d_halo_bias_act_fwd': 'ppppiiplliip', 'segx_conv3d_fwd_bias_act': 'ppppiipipillip', 'segx_bias_map_relu': 'ppilp', 'segx_conv3d_halo_wgrad_ok': 'iip', 'segx_conv3d_halo_wgrad_ws_floats': 'iip', 'segx_conv3d_halo_wgrad': 'ppppiipllp',

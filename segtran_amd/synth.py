@@ -101,18 +101,34 @@ def synth_image2d(B, S, seed=1337, S2=None):
     return torch.randn(B, 3, S, S2 or S, generator=g, device='cpu')
 
 
-def synth_fundus_mask(B, S, seed=1338):
-    """uint8 {0,255} [B,3,S,S] in the loaders' on-disk encoding: ch0 = optic-disc region (incl. cup),
-    ch1 = cup (nested disc), ch2 = 0."""
+def synth_fundus_mask(B, S, seed=1338, S2=None):
+    """uint8 {0,255} [B,3,S,S2 or S] in the loaders' on-disk encoding: ch0 = optic-disc region (incl. cup),
+    ch1 = cup (nested disc), ch2 = 0.  A rectangular mask places the centre per axis and sizes the disc by the shorter side."""
     g = torch.Generator(device='cpu'); g.manual_seed(seed)
-    yy, xx = torch.meshgrid(torch.arange(S, device='cpu'), torch.arange(S, device='cpu'), indexing='ij')
-    m = torch.zeros(B, 3, S, S, dtype=torch.uint8, device='cpu')
+    W = S2 or S
+    yy, xx = torch.meshgrid(torch.arange(S, device='cpu'), torch.arange(W, device='cpu'), indexing='ij')
+    m = torch.zeros(B, 3, S, W, dtype=torch.uint8, device='cpu')
     for b in range(B):
-        c = (torch.rand(2, generator=g, device='cpu') * 0.3 + 0.35) * S
-        r = (torch.rand(1, generator=g, device='cpu') * 0.1 + 0.25) * S
+        c = (torch.rand(2, generator=g, device='cpu') * 0.3 + 0.35) * torch.tensor([S, W], device='cpu')
+        r = (torch.rand(1, generator=g, device='cpu') * 0.1 + 0.25) * min(S, W)
         d2 = (yy - c[0]) ** 2 + (xx - c[1]) ** 2
         m[b, 0][d2 <= r * r] = 255
         m[b, 1][d2 <= (0.5 * r) ** 2] = 255
+    return m
+
+
+def synth_oct_mask(B, H, W, num_classes=10, seed=1338):
+    """uint8 index mask [B, 1, H, W] of an OCT-like scan: num_classes stacked bands (retinal layers) from top to bottom, class c over class c + 1, whose boundaries
+    undulate along the width with a per-image phase (a deterministic function of seed and image).  Every class is present in every image whenever
+    H >= 2 * num_classes: the undulation stays below half of the thinnest band."""
+    yy = torch.arange(H, device='cpu', dtype=torch.float32).view(H, 1)
+    xx = torch.arange(W, device='cpu', dtype=torch.float32).view(1, W)
+    band = H / float(num_classes)
+    m = torch.zeros(B, 1, H, W, dtype=torch.uint8, device='cpu')
+    for b in range(B):
+        phase = ((seed * 31 + b * 7) % 16) / 16.0 * 2 * math.pi
+        shift = 0.45 * (band - 1) * torch.sin(2 * math.pi * xx / W + phase)             # |shift| < band / 2: no band vanishes
+        m[b, 0] = torch.clamp(torch.floor((yy + shift) / band), 0, num_classes - 1).to(torch.uint8)
     return m
 
 

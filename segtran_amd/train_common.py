@@ -289,7 +289,7 @@ def run(args, cfg, batches=None):
                                t_total=args.maxiter, weight_decay=args.decay)
         step = engine.AdversarialTrainStep(net, opt, args.task_name, adv, adda=getattr(args, 'adda', False), discriminator_optim=dis_opt,
                                            supervised_w=args.SUPERVISED_W, domain_w=args.DOMAIN_LOSS_W, recon_w=args.RECON_W, dice_w=args.MAX_DICE_W,
-                                           exclusive=getattr(args, 'use_exclusive_masks', False))
+                                           exclusive=getattr(args, 'use_exclusive_masks', False), focus_class=getattr(args, 'focus_class', -1))
         if batches is None:
             sb = args.source_batch_size if args.source_batch_size > 0 else args.batch_size
             tb = args.target_unsup_batch_size if args.target_unsup_batch_size > 0 else args.batch_size
@@ -298,7 +298,7 @@ def run(args, cfg, batches=None):
             batches = iter(lambda: fixed, None)                           # (image, mask, unsupervised target images, source images), train2d.py:1147-1170
     else:
         step = engine.TrainStep(net, opt, args.task_name, reducer, dice_w=args.MAX_DICE_W,
-                                exclusive=getattr(args, 'use_exclusive_masks', False), augment=augment)
+                                exclusive=getattr(args, 'use_exclusive_masks', False), augment=augment, focus_class=getattr(args, 'focus_class', -1))
         if batches is None:
             fixed = engine.synth_batch(cfg, args.batch_size, dev, seed=args.seed + rank)
             batches = iter(lambda: fixed, None)
