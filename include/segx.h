@@ -353,6 +353,16 @@ int segx_plane_bias_add(const float* X, const float* bias, float* Y, int64_t pla
 int segx_plane_dot(const float* A, const float* Bm, float* out, int64_t planes, int64_t S, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * ResNet block end (resnet.hip) on dense [planes = B*C][S] maps
+ * ------------------------------------------------------------------------------------------- */
+/* Y[p][s] = relu((Z[p][s] + bias[p % C]) + R[p][s]), the additions in that order in fp32; R == NULL / bias == NULL drops the term (C is read only with a bias:
+ * planes must then be a multiple of C and stay below 2^31).  A NaN operand gives NaN, like torch.relu.  Y may alias Z.  16-byte accesses where the pointers are
+ * 16-byte aligned (and, with a bias, S % 4 == 0); grid-stride over the planes, so no grid axis bounds them. */
+int segx_add_relu_fwd(const float* Z, const float* R, const float* bias, float* Y, int64_t planes, int C, int64_t S, void* stream);
+/* dZ = Y > 0 ? dY : 0 (torch's threshold_backward; 0 at Y == 0): the gradient of Z and of R alike.  Needs the OUTPUT only.  dZ may alias dY, not Y. */
+int segx_add_relu_bwd(const float* dY, const float* Y, float* dZ, int64_t planes, int64_t S, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Feature-pyramid kernels (fpn.hip)
  * ------------------------------------------------------------------------------------------- */
 /* nn.GroupNorm(G, C) on [B, C, S] (segtran2d.py:148-149,190-192; segtran3d.py:182-183,225-227).  mean/rstd: [B*G].

@@ -978,6 +978,60 @@ def bn_act(x, bn, act=ACT_NONE, resid=None, drop_connect=0.0):
                         float(drop_connect or 0.0))
 
 
+class _AddRelu(_Fn):
+    """y = relu(z + resid): the end of a ResNet block (resnet.py:59-64 / :110-115 of the reference) as one streaming pass (resnet.hip).  The backward needs y
+    only, and z and resid receive the same gradient tensor."""
+
+    @staticmethod
+    def forward(ctx, z, resid):
+        L = segx.lib()
+        z = _c(z)
+        resid = _c(resid) if resid is not None else None
+        B, C = z.shape[0], z.shape[1]
+        S = z.numel() // (B * C)
+        y = torch.empty_like(z)
+        L.add_relu_fwd(z, resid, None, y, B * C, C, S)
+        ctx.cfg = (B * C, S)
+        ctx.has_resid = resid is not None
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        L = segx.lib()
+        (y,) = ctx.saved_tensors
+        dz = torch.empty_like(y)
+        L.add_relu_bwd(_c(dy), y, dz, *ctx.cfg)
+        return dz, (dz if ctx.has_resid else None)
+
+
+def add_relu(z, resid=None, bias=None, out=None):
+    """relu((z + bias[channel]) + resid) on [B, C, *spatial] maps, the additions in that order; a NaN operand gives NaN (torch.relu).  The end of a ResNet block:
+    training / unfolded    add_relu(bn_act(conv_out, bn_last, ACT_NONE, resid=shortcut))   -- the skip add stays in the BatchNorm apply pass;
+    BatchNorm folded       add_relu(z, shortcut, bias=b_last + b_down, out=z)             -- forward only (_no_grad_operands), in place.
+    resid: same shape as z.  bias: [C].  out: a dense tensor of z's shape that receives the result (z itself allowed); forward only as well."""
+    if z.dim() < 2 or z.numel() == 0:
+        raise ValueError('add_relu: z must be a non-empty [B, C, *spatial] map, got %s' % (tuple(z.shape),))
+    if resid is not None and resid.shape != z.shape:
+        raise ValueError('add_relu: resid %s does not match z %s' % (tuple(resid.shape), tuple(z.shape)))
+    if bias is None and out is None:
+        return _AddRelu.apply(z, resid)
+    if bias is not None and bias.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError('add_relu: the bias gradient is not built (a bias exists only with BatchNorm folded, in inference): call it under torch.no_grad() '
+                           'or with a bias that does not require grad')
+    _no_grad_operands('add_relu(bias= / out=)', z, resid, bias, out)
+    B, C = z.shape[0], z.shape[1]
+    if bias is not None and bias.numel() != C:
+        raise ValueError('add_relu: bias has %d elements for %d channels' % (bias.numel(), C))
+    if out is None:
+        out = torch.empty_like(z, memory_format=torch.contiguous_format)
+    elif out.shape != z.shape or not out.is_contiguous():
+        raise ValueError('add_relu: out must be a dense tensor of the shape of z')
+    zc = _c(z)
+    segx.lib().add_relu_fwd(zc, _c(resid) if resid is not None else None, _c(bias) if bias is not None else None, out, B * C, C, z.numel() // (B * C))
+    return out
+
+
 def bn_act_multi(x, bns, act=ACT_NONE):
     """BatchNorm (+ activation) of SEVERAL BatchNorm modules in one pass: x's channels are the concatenation of the modules' channels (the outputs
     of convolutions that were run as one convolution with concatenated filters).  BatchNorm is per channel, so this is exactly the separate

@@ -4,8 +4,8 @@ Same constructor (`Segtran2d(config)` with `CONFIG.update_config(args)`), same f
 ([B,3,H,W] -> [B,num_classes,H,W] logits), same attribute surface read by the trainer
 (`voxel_fusion.translayers[i]...`, `layers_attn_scores`, `orig_feat_shape`, `feature_maps`,
 `backbone._blocks`, `backbone.endpoint_blk_indices`, `num_vis_layers`) and the same state_dict keys.
-Built: eff-b* backbones, in_fpn '34' / out_fpn '1234' with scheme 'AN' and GroupNorm (the values the
-trainer forces / defaults to).  ResNet / EfficientNet-V2 backbones, BN FPNs, modalities and the global-bias
+Built: eff-b* and resnet34/50/101 backbones (`--bb`), in_fpn '34' / out_fpn '1234' with scheme 'AN' and GroupNorm (the values the
+trainer forces / defaults to).  EfficientNet-V2 backbones, resnet_bn_to_gn, BN FPNs, modalities and the global-bias
 ablation are outside the hot path and raise.
 
 Kernel status: fusion encoder, every 1x1 conv (MFMA GEMM), GroupNorm and the bilinear resampling with the fused
@@ -18,6 +18,7 @@ import torch.nn.functional as F
 from argparse import Namespace
 
 from .. import functional as SF
+from .. import resnet
 from ..efficientnet.model import EfficientNet
 from .segtran_shared import (SegtranConfig, bb2feat_dims, SegtranFusionEncoder, CrossAttFeatTrans,  # noqa: F401
                              ExpandedFeatTrans, SegtranInitWeights, gen_all_indices, gen_scaled_positions)
@@ -55,6 +56,8 @@ class Segtran2dConfig(SegtranConfig):
         if 'dropout_prob' in a and a['dropout_prob'] >= 0:
             self.hidden_dropout_prob = a['dropout_prob']
             self.attention_probs_dropout_prob = a['dropout_prob']
+        if self.backbone_type not in bb2feat_dims:
+            raise NotImplementedError("backbone '%s' has no bb2feat_dims row: eff-b0..b4 and resnet34 / resnet50 / resnet101 are built" % self.backbone_type)
         self.bb_feat_dims = bb2feat_dims[self.backbone_type]
         self.set_fpn_layers('args', args, do_print=False)
 
@@ -88,15 +91,22 @@ class Segtran2d(SegtranInitWeights):
         self.use_global_bias = False
         self.voxel_fusion = SegtranFusionEncoder(config, 'Fusion')
         self.backbone_type = config.backbone_type
-        if not self.backbone_type.startswith('eff-'):
-            raise NotImplementedError("backbone '%s': only EfficientNet-V1 (eff-b0..b7) is built" % self.backbone_type)
-        stem_stride = 1 if self.bb_feat_upsize else 2
         self.use_pretrained = config.use_pretrained
-        bb_name = self.backbone_type.replace('eff', 'efficientnet')
-        if self.use_pretrained:                                 # segtran2d.py:98-101 (advprop checkpoint, local file: no network)
-            self.backbone = EfficientNet.from_pretrained(bb_name, advprop=True, ignore_missing_keys=True, stem_stride=stem_stride)
+        if self.backbone_type.startswith('resnet') or self.backbone_type.startswith('resibn'):      # segtran2d.py:89-92
+            if getattr(config, 'resnet_bn_to_gn', False):
+                raise NotImplementedError('resnet_bn_to_gn is not built')
+            if self.backbone_type not in resnet.BACKBONES:
+                raise NotImplementedError("backbone '%s': of the ResNets only %s are built" % (self.backbone_type, ', '.join(sorted(resnet.BACKBONES))))
+            self.backbone = resnet.BACKBONES[self.backbone_type](pretrained=self.use_pretrained, do_pool1=not self.bb_feat_upsize)
+        elif self.backbone_type.startswith('eff-'):
+            stem_stride = 1 if self.bb_feat_upsize else 2
+            bb_name = self.backbone_type.replace('eff', 'efficientnet')
+            if self.use_pretrained:                             # segtran2d.py:98-101 (advprop checkpoint, local file: no network)
+                self.backbone = EfficientNet.from_pretrained(bb_name, advprop=True, ignore_missing_keys=True, stem_stride=stem_stride)
+            else:
+                self.backbone = EfficientNet.from_name(bb_name, stem_stride=stem_stride)
         else:
-            self.backbone = EfficientNet.from_name(bb_name, stem_stride=stem_stride)
+            raise NotImplementedError("backbone '%s': only EfficientNet-V1 (eff-b0..b7) and resnet34 / resnet50 / resnet101 are built" % self.backbone_type)
         self.in_fpn_layers, self.in_fpn_scheme = config.in_fpn_layers, config.in_fpn_scheme
         self.out_fpn_layers, self.out_fpn_scheme = config.out_fpn_layers, config.out_fpn_scheme
         if self.in_fpn_layers != [3, 4] or self.out_fpn_layers != [1, 2, 3, 4] or self.in_fpn_scheme != 'AN' \
@@ -180,8 +190,8 @@ class Segtran2d(SegtranInitWeights):
         return _up(scores, size)
 
     def fold_batchnorm(self):
-        """Inference only (eval mode, else RuntimeError): fold every BatchNorm of the EfficientNet backbone into the convolution in front of it (scale into the weights,
-        shift into a bias, swish into the producer's epilogue), so that a forward issues no BatchNorm launch.  The folded operands are derived tensors: state_dict() is
+        """Inference only (eval mode, else RuntimeError): fold every BatchNorm of the backbone (EfficientNet or ResNet) into the convolution in front of it (scale into the weights,
+        shift into a bias, swish / ReLU into the producer's epilogue or the block's closing pass), so that a forward issues no BatchNorm launch.  The folded operands are derived tensors: state_dict() is
         unchanged.  train() and load_state_dict() drop the fold; the model is then exactly the one that was never folded.  GroupNorm (FPNs) is data-dependent and stays."""
         if self.training:
             raise RuntimeError('fold_batchnorm() is for inference: call .eval() first')
@@ -212,8 +222,11 @@ class Segtran2d(SegtranInitWeights):
         if H % 8 or W % 8:
             raise ValueError('Segtran2d needs H and W divisible by 8 (reference segtran2d.py:379), got %dx%d' % (H, W))
         nonzero_mask = self.get_mask(batch)
-        ep = self.backbone.extract_endpoints(batch)
-        feats = tuple(ep['reduction_%d' % i] for i in range(1, 6))
+        if self.backbone_type.startswith('resnet'):                       # segtran2d.py:341-342
+            feats = self.backbone.ext_features(batch)
+        else:
+            ep = self.backbone.extract_endpoints(batch)
+            feats = tuple(ep['reduction_%d' % i] for i in range(1, 6))
         vfeat, vmask, H2, W2 = self.in_fpn_forward(feats, nonzero_mask, B)
         xy_shape = torch.Size((H2, W2))
         voxels_pos = gen_scaled_positions(xy_shape, (H // H2, W // W2), batch.device)            # [N, 2], batch-invariant

@@ -475,6 +475,13 @@ class SegxLib:
     def bn_act_bwd_apply(self, dY, X, mean, var, w, b, sdw, sdb, dX, B, C, S, eps, act, inv_n, gate=None, dpool=None, inv_S=0.0, dc_p=0.0, seed=0, offset=0):
         self._call('segx_bn_act_bwd_apply', X, dY, X, mean, var, w, b, sdw, sdb, dX, B, C, S, eps, act, inv_n, gate, dpool, float(inv_S), float(dc_p), seed, offset)
 
+    # ---- ResNet block end (resnet.hip) -----------------------------------------------------------
+    def add_relu_fwd(self, Z, R, bias, Y, planes, C, S):
+        self._call('segx_add_relu_fwd', Y, Z, R, bias, Y, planes, C, S)
+
+    def add_relu_bwd(self, dY, Y, dZ, planes, S):
+        self._call('segx_add_relu_bwd', dZ, dY, Y, dZ, planes, S)
+
     def plane_bias_add(self, X, bias, Y, planes, C, S):
         self._call('segx_plane_bias_add', X, X, bias, Y, planes, C, S)
 
@@ -865,7 +872,8 @@ _SIGS = {
     'segx_dwconv2d_fwd': 'pppiiiiiiiiiip', 'segx_dwconv2d_bwd_data': 'pppiiiiiiiiiip',
     'segx_dwconv2d_pool_chunks': 'ii', 'segx_dwconv2d_bias_act_pool': 'pppppiiiiiiiiiiip', 'segx_conv2d_stem_bias_act_fwd': 'ppppiiiiiiiiiiiip',
     'segx_dwconv2d_bwd_weight': 'pppiiiiiiiiiip', 'segx_dwconv2d_bwd_weight_direct': 'pppiiiiiiiiiip', 'segx_dwconv2d_wgrad_rows': 'ii', 'segx_dwconv2d_bwd_fused_rows': 'iiiiiiii', 'segx_dwconv2d_bwd_fused': 'pppppiiiiiiiiiip', 'segx_plane_scale': 'pppllp', 'segx_plane_dot': 'pppllp',
-     'segx_plane_bias_add': 'ppplilp', 
+     'segx_plane_bias_add': 'ppplilp',
+    'segx_add_relu_fwd': 'pppplilp', 'segx_add_relu_bwd': 'pppllp',
     'segx_plane_chunks': 'l', 'segx_bn_pool_chunks': 'ili', 'segx_bn_parts_floats': 'iil', 'segx_bn_stats_local': 'pppiilp',
     'segx_bn_act_fwd2': 'ppippppfpppppfuuiilfillp', 'segx_bn_act_bwd2': 'ppppppppppiilfiippffuullp',
     'segx_team_status': 'i', 'segx_team_cap': '', 'segx_occupy': 'iifpp',

@@ -25,7 +25,6 @@ def parse_size(text, flag='--patch'):
 def parse_args(argv=None):
     """the finalised argument namespace and the run's config (size, classes) -- everything main() decides before a device is touched"""
     p = tc.common_flags(argparse.ArgumentParser(description=__doc__), 2)
-    p.add_argument('--bb', dest='backbone_type', type=str, default='eff-b4')
     p.add_argument('--insize', dest='orig_input_size', type=str, default=None, help='S or H,W')
     p.add_argument('--patch', dest='patch_size', type=str, default=None, help='S or H,W (default: --insize)')
     p.add_argument('--exclusive', dest='use_exclusive_masks', action='store_true')
@@ -35,8 +34,10 @@ def parse_args(argv=None):
         raise SystemExit('--exclusive only changes the fundus label map (datasets2d.py:110-111)')
     if args.task_name not in NUM_CLASSES:
         raise SystemExit("--task %s: only 'fundus', 'polyp' and 'oct' are wired" % args.task_name)
-    if args.backbone_type != 'eff-b4' and not args.backbone_type.startswith('eff-b'):
-        raise SystemExit('--bb %s: only EfficientNet-V1 backbones are built' % args.backbone_type)
+    if not args.backbone_type.startswith('eff-b') and args.backbone_type not in ('resnet34', 'resnet50', 'resnet101'):
+        raise SystemExit('--bb %s: only EfficientNet-V1 (eff-b*) and resnet34 / resnet50 / resnet101 backbones are built' % args.backbone_type)
+    if args.tune_bn_only and not args.backbone_type.startswith('eff'):    # train2d.py:1089-1100: --tunebn walks the EfficientNet blocks
+        raise SystemExit("Backbone '%s' not supported by --tunebn." % args.backbone_type)
     nc = NUM_CLASSES[args.task_name]
     if args.focus_class != -1 and not 0 <= args.focus_class < nc:
         raise SystemExit('--focus %d: the %s task has classes 0 .. %d' % (args.focus_class, args.task_name, nc - 1))

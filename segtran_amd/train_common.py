@@ -66,6 +66,8 @@ def common_flags(p, dim):
     p.add_argument('--outdrop', dest='out_fpn_do_dropout', action='store_true')
     p.add_argument('--inbn', dest='in_fpn_use_bn', action='store_true')
     p.add_argument('--nofeatup', dest='bb_feat_upsize', action='store_false')
+    if dim == 2:          # train2d.py:171; the 3-D models stay on 'i3d' (engine.model_args)
+        p.add_argument('--bb', dest='backbone_type', type=str, default='eff-b4', help='eff-b0 .. eff-b4, resnet34, resnet50 or resnet101')
     if dim == 2:          # the few-shot / adversarial recipe (train2d.py:87-107); file datasets are out of scope: the source / target batches are synthetic
         p.add_argument('--adv', dest='adversarial_mode', type=str, default=None, choices=[None, 'none', 'feat', 'mask'])
         p.add_argument('--featdisinchan', dest='num_feat_dis_in_chan', type=int, default=64)
@@ -118,7 +120,7 @@ def finalize_args(args, dim):
 
 
 ARCH_FLAGS = ('use_squeezed_transformer', 'has_FFN_in_squeeze', 'in_fpn_use_bn', 'out_fpn_do_dropout', 'qk_have_bias', 'num_modes', 'pos_code_type', 'pos_code_weight', 'pos_bias_radius', 'attn_clip',
-              'use_mince_transformer', 'mince_scales', 'mince_channel_props', 'in_fpn_layers', 'out_fpn_layers', 'bb_feat_upsize')
+              'use_mince_transformer', 'mince_scales', 'mince_channel_props', 'in_fpn_layers', 'out_fpn_layers', 'bb_feat_upsize', 'backbone_type')
 
 
 def arch_overrides(args):

@@ -45,11 +45,11 @@ def ref_shared():
     return ss
 
 
-def ref_segtran2d(num_classes=3, num_attractors=256, num_translayers=3, compress=(1, 1, 2, 2), **over):
+def ref_segtran2d(num_classes=3, num_attractors=256, num_translayers=3, compress=(1, 1, 2, 2), backbone_type='eff-b4', **over):
     _install_stubs()
     from networks.segtran2d import Segtran2d, CONFIG
     kw = dict(COMMON); kw.update(over)
-    a = Namespace(num_classes=num_classes, backbone_type='eff-b4', num_attractors=num_attractors,
+    a = Namespace(num_classes=num_classes, backbone_type=backbone_type, num_attractors=num_attractors,
                   num_translayers=num_translayers, translayer_compress_ratios=list(compress),
                   num_modalities=0, use_global_bias=False, **kw)
     def build():
