@@ -18,6 +18,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from .. import functional as SF
+from ..fold import FoldableBackbone, fold_conv_bn, pair_sources
 
 BN_MOM, BN_EPS = 1 - 0.99, 1e-3
 
@@ -77,16 +78,6 @@ def drop_connect(x, p, training):
     keep = 1 - p
     r = keep + torch.rand([x.shape[0], 1, 1, 1], dtype=x.dtype, device=x.device)
     return x / keep * torch.floor(r)
-
-
-def fold_conv_bn(weight, bn):
-    """BatchNorm in eval mode is the per-channel affine map y = x * s + (beta - mu * s), s = gamma / sqrt(var + eps): folded into the convolution that feeds it,
-    w' = w * s[out channel], b' = beta - mu * s.  Derived in fp64 on the parameters' device and rounded once to fp32; plain tensors (no Parameter, no buffer)."""
-    with torch.no_grad():
-        s = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
-        w = (weight.double() * s.view(-1, *([1] * (weight.dim() - 1)))).float().contiguous()
-        b = (bn.bias.double() - bn.running_mean.double() * s).float().contiguous()
-    return w, b
 
 
 class MBConvBlock(nn.Module):
@@ -164,7 +155,7 @@ class MBConvBlock(nn.Module):
         return SF.bn_act(x, self._bn2, SF.ACT_NONE, resid=skip_in if skip else None, drop_connect=rate)
 
 
-class EfficientNet(nn.Module):
+class EfficientNet(FoldableBackbone, nn.Module):
     def __init__(self, model_name='efficientnet-b4', stem_stride=2, drop_connect_rate=0.2, num_classes=1000):
         super().__init__()
         width, depth, res, _ = _PARAMS[model_name]
@@ -190,51 +181,14 @@ class EfficientNet(nn.Module):
         self._bn1 = nn.BatchNorm2d(chead, momentum=BN_MOM, eps=BN_EPS)
         self._fc = nn.Linear(chead, num_classes)               # kept for checkpoint compatibility; never used (N3)
 
-    # ---- inference with BatchNorm folded into the convolutions (opt-in) -------------------------------------------------------------
-    _folded = None             # None, or (stem, [per block], head, sources, versions): derived tensors, neither Parameters nor buffers -- never in state_dict()
-
-    def _fold_sources(self):
-        """every tensor the folded operands were derived from (convolution weights, BatchNorm parameters and running statistics)"""
-        src = []
-        for conv, bn in [(self._conv_stem, self._bn0), (self._conv_head, self._bn1)] + \
+    # ---- inference with BatchNorm folded into the convolutions (opt-in; the lifecycle is fold.FoldableBackbone's) ---------------------------
+    def _fold_build(self):
+        """_folded = (stem, [per block], head, sources, versions): the stem, the three pairs of each MBConv block, the head"""
+        pairs = [(self._conv_stem, self._bn0), (self._conv_head, self._bn1)] + \
                 [(c, b) for blk in self._blocks for c, b in ((getattr(blk, '_expand_conv', None), getattr(blk, '_bn0', None)), (blk._depthwise_conv, blk._bn1),
-                                                            (blk._project_conv, blk._bn2)) if c is not None]:
-            src += [conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var]
-        return src
-
-    def fold_batchnorm(self):
-        """Derive the folded operands of every conv -> BatchNorm pair (stem, the three pairs of each MBConv block, head).  Eval mode only.  extract_endpoints then
-        issues no BatchNorm launch.  train(), load_state_dict(), a device / dtype move and an in-place change of a source tensor (torch's version counters) drop the fold again."""
-        if self.training:
-            raise RuntimeError('fold_batchnorm() is for inference: call .eval() first (in training mode BatchNorm uses batch statistics and cannot be folded)')
-        src = self._fold_sources()
-        self._folded = (fold_conv_bn(self._conv_stem.weight, self._bn0), [blk.folded_operands() for blk in self._blocks],
-                        fold_conv_bn(self._conv_head.weight, self._bn1), src, [t._version for t in src])
-        return self
-
-    def unfold_batchnorm(self):
-        self._folded = None
-
-    @property
-    def batchnorm_folded(self):
-        """True while extract_endpoints runs on folded operands; a source tensor changed in place since fold_batchnorm() drops the fold here"""
-        f = self._folded
-        if f is not None and (self.training or any(t._version != v for t, v in zip(f[3], f[4]))):
-            self._folded = f = None
-        return f is not None
-
-    def train(self, mode=True):
-        if mode:
-            self._folded = None
-        return super().train(mode)
-
-    def _apply(self, fn, *args, **kwargs):
-        self._folded = None                # .to() / .cuda() / .float(): the derived tensors would stay behind
-        return super()._apply(fn, *args, **kwargs)
-
-    def _load_from_state_dict(self, *args, **kwargs):
-        self._folded = None                # reached from load_state_dict() of this module and of any module that contains it
-        return super()._load_from_state_dict(*args, **kwargs)
+                                                            (blk._project_conv, blk._bn2)) if c is not None]
+        return (fold_conv_bn(self._conv_stem.weight, self._bn0), [blk.folded_operands() for blk in self._blocks],
+                fold_conv_bn(self._conv_head.weight, self._bn1)), pair_sources(pairs)
 
     def _extract_endpoints_folded(self, inputs):
         (ws, bs), blocks, (wh, bh) = self._folded[:3]

@@ -5,7 +5,6 @@ test_util2d.py mirrors the reference's file of that name and keeps the reference
 preds_soft: calc_vcdr, calc_batch_metric with the vCDR-error column, remove_fragmentary_segs, export_masks; and the one-hot tasks' form of it
 (DESIGN.md 5t): calc_batch_metric_onehot and test_all_cases(gt_is_index=True), which work from index masks through one tail launch.  fold_bn=True folds the (eval-mode) net for
 the call if it is not folded already (Segtran2d.fold_batchnorm) and unfolds it afterwards; a net the caller folded stays folded."""
-import contextlib
 import math
 
 import torch
@@ -14,49 +13,12 @@ from . import functional as SF
 from . import test_util2d as _T2
 from .test_util2d import calc_dice          # noqa: F401  (same module surface)
 from .dataloaders.datasets2d import harden_segmap2d
+from .infer_common import PRECISIONS, GraphedEvaluation, _precision, folded, inference_precision, run_chunks      # noqa: F401  (same module surface)
 
 
-@contextlib.contextmanager
 def _folded(net, fold_bn):
-    here = bool(fold_bn) and not net.batchnorm_folded
-    if here:
-        net.fold_batchnorm()
-    try:
-        yield
-    finally:
-        if here:
-            net.unfold_batchnorm()
-
-
-PRECISIONS = {'fp32': 6, 'bf16x3': 3}           # name -> Knob.X6_TERMS: bf16 products per block of the bf16 tile engine
-
-
-@contextlib.contextmanager
-def inference_precision(name):
-    """with inference_precision('bf16x3'): the GEMMs and the forward 3-D convolutions of the bf16 tile engine run the three-term product (hi.mid + mid.hi + hi.hi on
-    two bf16 planes per operand) on the routes that have such a kernel -- accurate to (2^-15 + 2^-16) |A|.|B| per element instead of fp32-equivalent; 'fp32' is the default behaviour.
-    The setting is process-wide for the duration of the block (segx_tune knob X6_TERMS) and the value it held comes back at the end, also after an exception.
-    Inference only: the training parity bar rules the mode out, so entering with gradients enabled raises RuntimeError; an unknown name raises ValueError."""
-    if name not in PRECISIONS:
-        raise ValueError('inference_precision: %r is not one of %s' % (name, sorted(PRECISIONS)))
-    if torch.is_grad_enabled():
-        raise RuntimeError("inference_precision(%r) is for inference: enter it under torch.no_grad()" % (name,))
-    from . import segx
-    with segx.lib().tuned(x6_terms=PRECISIONS[name]):
-        yield
-
-
-@contextlib.contextmanager
-def _precision(precision):
-    """the `precision` argument of the evaluation entry points: 'fp32' leaves everything as the caller has it, 'bf16x3' runs the block without gradients inside
-    inference_precision('bf16x3')"""
-    if precision not in PRECISIONS:
-        raise ValueError('precision: %r is not one of %s' % (precision, sorted(PRECISIONS)))
-    if precision == 'fp32':
-        yield
-    else:
-        with torch.no_grad(), inference_precision(precision):
-            yield
+    """fold for the block if asked and not folded already (Segtran2d.fold_batchnorm); a net the caller folded stays folded"""
+    return folded(net, fold_bn, lambda n: n.fold_batchnorm(), lambda n: n.unfold_batchnorm())
 
 
 def sliding_windows(H, W, orig_input_size, stride):
@@ -105,15 +67,7 @@ class _Plan:
         """gather -> net() on chunks of window_batch windows (window_batch * B samples each) -> merge; the caller holds torch.no_grad()"""
         B, nwin = self.shape[0], self.table.nwin
         patches = SF.window_gather(image_batch, self.table, self.window, self.patch, self.pads, self.canvas)
-        if self.window_batch >= nwin:
-            scores = net(patches)
-        else:
-            scores = None
-            for k in range(0, nwin, self.window_batch):
-                part = net(patches[k * B:(k + self.window_batch) * B])
-                if scores is None:
-                    scores = part.new_empty((nwin * B,) + tuple(part.shape[1:]))
-                scores[k * B:k * B + part.shape[0]] = part               # plumbing: the chunks' scores side by side, as merge reads them
+        scores = run_chunks(net, patches, [(k * B, min(k + self.window_batch, nwin) * B) for k in range(0, nwin, self.window_batch)])
         preds_soft, preds_hard = SF.window_merge(scores, self.table, self.window, self.shape[2:], self.pads, self.canvas, mode=0)
         return preds_hard.to(torch.int32), preds_soft
 
@@ -291,7 +245,7 @@ def export_masks(preds_soft, unscaled_sizes, inv_map, remove_frag=False, bg_valu
     return out
 
 
-class GraphedSlidingWindow:
+class GraphedSlidingWindow(GraphedEvaluation):
     """The fused sliding-window evaluation of one image-batch shape captured into a hipGraph and replayed: gather, the forward(s) and merge -- a few hundred
     launches per forward -- become one graph launch, which takes the host out of a launch-bound evaluation (as engine.GraphedTrainStep does for the train step).
 
@@ -304,61 +258,21 @@ class GraphedSlidingWindow:
     replay needs no setting and leaves none behind.  The object reports it as .precision."""
 
     def __init__(self, net, image_shape, orig_input_size, patch_size, stride, num_classes, fold_bn=True, window_batch=None, warmup=2, precision='fp32'):
-        from . import segx
-        if net.training:
-            raise RuntimeError('GraphedSlidingWindow is for inference: call net.eval() first')
-        if precision not in PRECISIONS:
-            raise ValueError('precision: %r is not one of %s' % (precision, sorted(PRECISIONS)))
-        self.precision = precision
-        assert segx.lib().gemm_prof is None, 'per-launch event profiling cannot run inside a captured evaluation'
-        device = next(net.parameters()).device
-        self.net, self.num_classes = net, num_classes
-        self._folded_here = bool(fold_bn) and not net.batchnorm_folded
-        if self._folded_here:
-            net.fold_batchnorm()
-        try:
-            self.folded = net.batchnorm_folded
-            self.plan = _Plan(net, image_shape, orig_input_size, patch_size, stride, device, window_batch)
-            self.image = torch.zeros(self.plan.shape, dtype=torch.float32, device=device)
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side), torch.no_grad(), _precision(precision):   # eager warm-up: GEMM plans, derived operands, allocator pools
-                for _ in range(warmup):
-                    self.plan.run(net, self.image)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.no_grad(), _precision(precision), torch.cuda.graph(self.graph):
-                self.preds_hard, self.preds_soft = self.plan.run(net, self.image)
-            assert self.preds_soft.shape[1] == num_classes, 'the net has %d classes, not %d' % (self.preds_soft.shape[1], num_classes)
-        except BaseException:                                   # leave the net as it was found
-            if self._folded_here and net.batchnorm_folded:
-                net.unfold_batchnorm()
-            raise
-        self.replays = 0
+        super().__init__(net, num_classes, fold_bn, warmup, precision, image_shape, orig_input_size, patch_size, stride, window_batch)
+
+    def _build(self, device, image_shape, orig_input_size, patch_size, stride, window_batch):
+        self.plan = _Plan(self.net, image_shape, orig_input_size, patch_size, stride, device, window_batch)
+
+    def _sequence(self):
+        return self.plan.run(self.net, self.image)
+
+    def _check_classes(self):
+        assert self.preds_soft.shape[1] == self.num_classes, 'the net has %d classes, not %d' % (self.preds_soft.shape[1], self.num_classes)
 
     def __call__(self, image_batch):
-        if self.graph is None:
-            raise RuntimeError('GraphedSlidingWindow: closed')
-        if self.net.training:
-            raise RuntimeError('GraphedSlidingWindow: the net is in train mode; the captured evaluation is the eval-mode forward')
-        if self.net.batchnorm_folded != self.folded:
-            raise RuntimeError('GraphedSlidingWindow: the BatchNorm fold of the net changed since capture (train(), load_state_dict() or an in-place edit); '
-                               'build a new GraphedSlidingWindow')
-        if tuple(image_batch.shape) != self.plan.shape:
-            raise ValueError('GraphedSlidingWindow: captured for images %r, got %r' % (self.plan.shape, tuple(image_batch.shape)))
-        if image_batch is not self.image:
-            self.image.copy_(image_batch, non_blocking=True)
-        self.graph.replay()
-        self.replays += 1
+        self._check(image_batch)
+        self._replay(image_batch)
         return self.preds_hard, self.preds_soft
-
-    def close(self):
-        """drop the graph and its static tensors; unfold the net if the constructor folded it"""
-        self.graph = self.preds_hard = self.preds_soft = None
-        if self._folded_here and self.net.batchnorm_folded:
-            self.net.unfold_batchnorm()
-        self._folded_here = False
 
 
 # reference function names; not pytest tests

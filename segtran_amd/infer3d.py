@@ -10,7 +10,6 @@ the device in integers (metrics.hip, DESIGN.md 5o) and finished here in float64;
 And the case evaluation in one pass: sliding_windows (the eager loops' geometry and batches), test_single_case(fused=True) (one gather launch, net() on the
 eager loop's batches, one merge launch), GraphedSlidingWindow3d (that sequence with the BraTS case tail, SF.brats_case_tail, as one replayable hipGraph), case_metrics
 and test_all_cases (the reference's loop over the cases of a dataset, test_util3d.py:15-91, without its file I/O)."""
-import contextlib
 import math
 import os
 
@@ -19,7 +18,7 @@ import torch
 
 from . import functional as SF
 from . import test_util3d as _T3
-from .infer2d import PRECISIONS, _precision, inference_precision          # noqa: F401  (inference_precision: re-exported)
+from .infer_common import PRECISIONS, GraphedEvaluation, _precision, folded, inference_precision, run_chunks      # noqa: F401  (inference_precision: re-exported)
 
 
 def fold_batchnorm(net):
@@ -34,17 +33,9 @@ def unfold_batchnorm(net):
     return net
 
 
-@contextlib.contextmanager
 def _folded(net, fold_bn):
-    """infer2d._folded for a Segtran3d: fold for the block if asked and not folded already; a net the caller folded stays folded"""
-    here = bool(fold_bn) and not net.batchnorm_folded
-    if here:
-        fold_batchnorm(net)
-    try:
-        yield
-    finally:
-        if here:
-            unfold_batchnorm(net)
+    """fold for the block if asked and not folded already (fold_batchnorm: the backbone's); a net the caller folded stays folded"""
+    return folded(net, fold_bn, fold_batchnorm, unfold_batchnorm)
 
 
 def sliding_windows(H, W, D, orig_patch_size, stride_xy, stride_z, batch_size):
@@ -84,15 +75,7 @@ class _Plan3d:
     def run(self, net, image):
         """gather -> net() per chunk of the eager loop -> merge; the caller holds torch.no_grad().  (preds_hard, preds_soft) [num_classes, H, W, D]"""
         patches = SF.window_gather(image.unsqueeze(0), self.table, self.window, self.patch, self.pads, self.canvas)
-        scores = None
-        for k0, k1 in self.chunks:
-            part = net(patches[k0:k1])
-            if scores is None:
-                if len(self.chunks) == 1:
-                    scores = part
-                    break
-                scores = part.new_empty((self.table.nwin,) + tuple(part.shape[1:]))
-            scores[k0:k1] = part                                     # plumbing: the chunks' scores side by side, as merge reads them
+        scores = run_chunks(net, patches, self.chunks)
         preds_soft, preds_hard = SF.window_merge(scores, self.table, self.window, self.shape[1:], self.pads, self.canvas, mode=1)
         return preds_hard[0], preds_soft[0]
 
@@ -205,7 +188,7 @@ def case_metrics(counts):
     return metric, valid
 
 
-class GraphedSlidingWindow3d:
+class GraphedSlidingWindow3d(GraphedEvaluation):
     """infer2d.GraphedSlidingWindow for a volume: the fused sliding-window evaluation of one image shape [C, H, W, D] -- gather, the forward of every chunk, merge and,
     when asked, the case tail (SF.brats_case_tail) -- captured into one hipGraph and replayed; the BraTS task (n-hot hardening with the consistency rule).
 
@@ -218,47 +201,19 @@ class GraphedSlidingWindow3d:
     precision ('fp32' default, 'bf16x3'): warm-up and capture run inside inference_precision(precision); a replay needs no setting and leaves none behind.
     The gather and score buffers hold all windows (test_single_case: about 0.93 GB each for a BraTS case) for the life of the object."""
 
+    _fold, _unfold = staticmethod(fold_batchnorm), staticmethod(unfold_batchnorm)
+
     def __init__(self, net, image_shape, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, num_classes=4, fold_bn=True, warmup=2,
                  precision='fp32', with_labels=True, with_mask=False):
-        from . import segx
-        if net.training:
-            raise RuntimeError('GraphedSlidingWindow3d is for inference: call net.eval() first')
-        if precision not in PRECISIONS:
-            raise ValueError('precision: %r is not one of %s' % (precision, sorted(PRECISIONS)))
-        self.precision = precision
-        assert segx.lib().gemm_prof is None, 'per-launch event profiling cannot run inside a captured evaluation'
-        device = next(net.parameters()).device
-        self.net, self.num_classes = net, num_classes
         self.with_labels, self.with_mask = bool(with_labels), bool(with_mask)
-        self._folded_here = bool(fold_bn) and not net.batchnorm_folded
-        if self._folded_here:
-            fold_batchnorm(net)
-        try:
-            self.folded = net.batchnorm_folded
-            self.plan = _Plan3d(image_shape, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, device)     # the window table: built before capture
-            spatial = self.plan.shape[1:]
-            self.image = torch.zeros(self.plan.shape, dtype=torch.float32, device=device)
-            self.mask = torch.zeros(spatial, dtype=torch.int32, device=device) if self.with_mask else None
-            self.counts = torch.zeros(3, 3, dtype=torch.int32, device=device) if self.with_mask else None
-            self.labels = torch.zeros(spatial, dtype=torch.uint8, device=device) if self.with_labels else None
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side), torch.no_grad(), _precision(precision):   # eager warm-up: GEMM plans, derived operands, allocator pools
-                for _ in range(warmup):
-                    self._sequence()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.no_grad(), _precision(precision), torch.cuda.graph(self.graph):
-                self.preds_hard, self.preds_soft = self._sequence()
-            if self.preds_soft.shape[0] != num_classes:
-                raise ValueError('the net has %d classes, not %d' % (self.preds_soft.shape[0], num_classes))
-        except BaseException:                                   # leave the net as it was found
-            self.graph = None
-            if self._folded_here and net.batchnorm_folded:
-                unfold_batchnorm(net)
-            raise
-        self.replays = 0
+        super().__init__(net, num_classes, fold_bn, warmup, precision, image_shape, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z)
+
+    def _build(self, device, *plan_args):
+        self.plan = _Plan3d(*plan_args, device)
+        spatial = self.plan.shape[1:]
+        self.mask = torch.zeros(spatial, dtype=torch.int32, device=device) if self.with_mask else None
+        self.counts = torch.zeros(3, 3, dtype=torch.int32, device=device) if self.with_mask else None
+        self.labels = torch.zeros(spatial, dtype=torch.uint8, device=device) if self.with_labels else None
 
     def _sequence(self):
         hard, soft = self.plan.run(self.net, self.image)
@@ -266,34 +221,25 @@ class GraphedSlidingWindow3d:
             SF.brats_case_tail(soft, hard, self.mask, want_labels=self.with_labels, counts=self.counts, labels=self.labels)
         return hard, soft
 
+    def _check_classes(self):
+        if self.preds_soft.shape[0] != self.num_classes:
+            raise ValueError('the net has %d classes, not %d' % (self.preds_soft.shape[0], self.num_classes))
+
     def __call__(self, image, mask=None):
-        if self.graph is None:
-            raise RuntimeError('GraphedSlidingWindow3d: closed')
-        if self.net.training:
-            raise RuntimeError('GraphedSlidingWindow3d: the net is in train mode; the captured evaluation is the eval-mode forward')
-        if self.net.batchnorm_folded != self.folded:
-            raise RuntimeError('GraphedSlidingWindow3d: the BatchNorm fold of the net changed since capture (train(), load_state_dict() or an in-place edit); '
-                               'build a new GraphedSlidingWindow3d')
-        if tuple(image.shape) != self.plan.shape:
-            raise ValueError('GraphedSlidingWindow3d: captured for images %r, got %r' % (self.plan.shape, tuple(image.shape)))
+        self._check(image)
         if (mask is not None) != self.with_mask:
             raise ValueError('GraphedSlidingWindow3d: built with_mask=%r: call it %s a mask' % (self.with_mask, 'with' if self.with_mask else 'without'))
         if mask is not None and tuple(mask.shape) != self.plan.shape[1:]:
             raise ValueError('GraphedSlidingWindow3d: captured for masks %r, got %r' % (self.plan.shape[1:], tuple(mask.shape)))
-        if image is not self.image:
-            self.image.copy_(image, non_blocking=True)
         if mask is not None and mask is not self.mask:
             self.mask.copy_(mask, non_blocking=True)           # converts to int32
-        self.graph.replay()
-        self.replays += 1
+        self._replay(image)
         return self.preds_hard, self.preds_soft, self.labels, self.counts
 
     def close(self):
-        """drop the graph and its static tensors; unfold the net if the constructor folded it"""
-        self.graph = self.preds_hard = self.preds_soft = self.labels = self.counts = self.image = self.mask = None
-        if self._folded_here and self.net.batchnorm_folded:
-            unfold_batchnorm(self.net)
-        self._folded_here = False
+        """GraphedEvaluation.close(), and drop the case's static buffers as well"""
+        super().close()
+        self.labels = self.counts = self.image = self.mask = None
 
 
 def test_all_cases(net, db_test, task_name='brats', net_type='segtran', num_classes=4, batch_size=8, orig_patch_size=(128, 112, 80),

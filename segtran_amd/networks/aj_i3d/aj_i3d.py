@@ -18,6 +18,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ... import functional as SF
+from ...fold import FoldableBackbone, fold_conv_bn, pair_sources
 
 
 class MaxPool3dSamePadding(nn.MaxPool3d):
@@ -108,7 +109,6 @@ class InceptionModule(nn.Module):
 
     def folded_operands(self):
         """[[w', b', ops] of b0, b1a, b1b, b2a, b2b, b3b]: what forward_folded takes (InceptionI3d.fold_batchnorm derives the same per module)"""
-        from ...efficientnet.model import fold_conv_bn
         return [list(fold_conv_bn(u.conv3d.weight, u.bn)) + [{}] for u in (self.b0, self.b1a, self.b1b, self.b2a, self.b2b, self.b3b)]
 
     def forward_folded(self, x, layers):
@@ -136,7 +136,7 @@ class InceptionModule(nn.Module):
         return out
 
 
-class InceptionI3d(nn.Module):
+class InceptionI3d(FoldableBackbone, nn.Module):
     VALID_ENDPOINTS = ('Conv3d_1a_7x7', 'MaxPool3d_2a_3x3', 'Conv3d_2b_1x1', 'Conv3d_2c_3x3', 'MaxPool3d_3a_3x3',
                        'Mixed_3b', 'Mixed_3c', 'MaxPool3d_4a_3x3', 'Mixed_4b', 'Mixed_4c', 'Mixed_4d', 'Mixed_4e',
                        'Mixed_4f', 'MaxPool3d_5a_2x2', 'Mixed_5b', 'Mixed_5c', 'Logits', 'Predictions')
@@ -191,49 +191,19 @@ class InceptionI3d(nn.Module):
 
     pyramid_endpoints = ('Conv3d_2c_3x3', 'Mixed_3c', 'Mixed_4f')      # feats[1..3] of Segtran3d (each is followed by a strided pool)
 
-    # ---- inference with BatchNorm3d folded into the convolutions (opt-in; DESIGN.md 5q; mirrors EfficientNet.fold_batchnorm) ---------------------------
-    _folded = None             # None, or (layers, sources, versions): layers = {module path of a Unit3D: [w', b', ops]} -- derived tensors, neither Parameters nor buffers
-
+    # ---- inference with BatchNorm3d folded into the convolutions (opt-in; DESIGN.md 5q; the lifecycle is fold.FoldableBackbone's, DESIGN.md 5v) -----------
     def _foldable_units(self):
         """[(module path, Unit3D)]: 'Conv3d_1a_7x7', 'Mixed_3b.b1a', ..."""
         return [(name + ('.' + sub if sub else ''), m) for name in self.end_points for sub, m in self._modules[name].named_modules() if isinstance(m, Unit3D) and m.foldable]
 
-    def fold_batchnorm(self):
+    def _fold_build(self):
         """Derive (w', b') = (w gamma / sqrt(var + eps), beta - mean gamma / sqrt(var + eps)) of every convolution -> BatchNorm3d -> ReLU layer of the feature extractor
         (fp64 on the parameters' device, rounded once).  Eval mode only.  extract_features then issues no BatchNorm launch, no torch.cat and -- after the first call,
         which fills the per-layer operand cache (concatenated reduction filters, halo / packed filter banks, the stem's constants) -- no pack launch.  train(),
-        load_state_dict(), a device / dtype move and an in-place change of a source tensor (torch's version counters) drop the fold and its cache."""
-        if self.training:
-            raise RuntimeError('fold_batchnorm() is for inference: call .eval() first (in training mode BatchNorm uses batch statistics and cannot be folded)')
-        from ...efficientnet.model import fold_conv_bn
+        load_state_dict(), a device / dtype move and an in-place change of a source tensor (torch's version counters) drop the fold and its cache.
+        _folded = (layers, sources, versions): layers = {module path of a Unit3D: [w', b', ops]}"""
         units = self._foldable_units()
-        src = [t for _, u in units for t in (u.conv3d.weight, u.bn.weight, u.bn.bias, u.bn.running_mean, u.bn.running_var)]
-        self._folded = ({path: list(fold_conv_bn(u.conv3d.weight, u.bn)) + [{}] for path, u in units}, src, [t._version for t in src])
-        return self
-
-    def unfold_batchnorm(self):
-        self._folded = None
-
-    @property
-    def batchnorm_folded(self):
-        """True while extract_features runs on folded operands; a source tensor changed in place since fold_batchnorm() drops the fold here"""
-        f = self._folded
-        if f is not None and (self.training or any(t._version != v for t, v in zip(f[1], f[2]))):
-            self._folded = f = None
-        return f is not None
-
-    def train(self, mode=True):
-        if mode:
-            self._folded = None
-        return super().train(mode)
-
-    def _apply(self, fn, *args, **kwargs):
-        self._folded = None                # .to() / .cuda() / .float(): the derived tensors would stay behind
-        return super()._apply(fn, *args, **kwargs)
-
-    def _load_from_state_dict(self, *args, **kwargs):
-        self._folded = None                # reached from load_state_dict() of this module and of any module that contains it
-        return super()._load_from_state_dict(*args, **kwargs)
+        return ({path: list(fold_conv_bn(u.conv3d.weight, u.bn)) + [{}] for path, u in units},), pair_sources([(u.conv3d, u.bn) for _, u in units])
 
     def folded_operands(self, path):
         """[w', b', ops] of one Unit3D of the folded extractor by its module path ('Conv3d_1a_7x7', 'Mixed_3b.b1b'; ops: the layer's operand cache)"""

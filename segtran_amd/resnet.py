@@ -22,7 +22,7 @@ import torch
 from torch import nn
 
 from . import functional as SF
-from .efficientnet.model import fold_conv_bn
+from .fold import FoldableBackbone, fold_conv_bn, pair_sources
 
 __all__ = ['ResNet', 'BasicBlock', 'Bottleneck', 'resnet34', 'resnet50', 'resnet101']
 
@@ -142,7 +142,7 @@ class Bottleneck(_Block):
         return [(self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)]
 
 
-class ResNet(nn.Module):
+class ResNet(FoldableBackbone, nn.Module):
     """set do_pool1=False when taking small images as input (resnet.py:122): Segtran2d passes do_pool1 = not bb_feat_upsize"""
 
     def __init__(self, block, layers, num_classes=1000, lens_stage=None, no_fc=False, no_avgpool=False, do_pool1=True):
@@ -208,47 +208,12 @@ class ResNet(nn.Module):
     def forward(self, x):
         raise NotImplementedError('ResNet.forward (the ImageNet classifier head) is not built: Segtran2d calls ext_features()')
 
-    # ---- inference with BatchNorm folded into the convolutions (the lifecycle of EfficientNet.fold_batchnorm) ----------------------------------------
-    _folded = None             # None, or (stem, [per block], sources, versions): derived tensors, neither Parameters nor buffers -- never in state_dict()
-
-    def _fold_sources(self):
-        src = []
-        for conv, bn in [(self.conv1, self.bn1)] + [pair for blk in self._blocks_in_order() for pair in blk._fold_pairs()]:
-            src += [conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var]
-        return src
-
-    def fold_batchnorm(self):
-        """Derive the folded operands of every conv -> BatchNorm pair.  Eval mode only.  ext_features then issues no BatchNorm launch.  train(), load_state_dict(), a
-        device / dtype move and an in-place change of a source tensor (torch's version counters) drop the fold again."""
-        if self.training:
-            raise RuntimeError('fold_batchnorm() is for inference: call .eval() first (in training mode BatchNorm uses batch statistics and cannot be folded)')
-        src = self._fold_sources()
-        self._folded = (fold_conv_bn(self.conv1.weight, self.bn1) + ({},), [blk.folded_operands() for blk in self._blocks_in_order()], src, [t._version for t in src])
-        return self
-
-    def unfold_batchnorm(self):
-        self._folded = None
-
-    @property
-    def batchnorm_folded(self):
-        """True while ext_features runs on folded operands; a source tensor changed in place since fold_batchnorm() drops the fold here"""
-        f = self._folded
-        if f is not None and (self.training or any(t._version != v for t, v in zip(f[2], f[3]))):
-            self._folded = f = None
-        return f is not None
-
-    def train(self, mode=True):
-        if mode:
-            self._folded = None
-        return super().train(mode)
-
-    def _apply(self, fn, *args, **kwargs):
-        self._folded = None                # .to() / .cuda() / .float(): the derived tensors would stay behind
-        return super()._apply(fn, *args, **kwargs)
-
-    def _load_from_state_dict(self, *args, **kwargs):
-        self._folded = None                # reached from load_state_dict() of this module and of any module that contains it
-        return super()._load_from_state_dict(*args, **kwargs)
+    # ---- inference with BatchNorm folded into the convolutions (the lifecycle is fold.FoldableBackbone's) ------------------------------------
+    def _fold_build(self):
+        """_folded = (stem, [per block], sources, versions)"""
+        blocks = self._blocks_in_order()
+        pairs = [(self.conv1, self.bn1)] + [pair for blk in blocks for pair in blk._fold_pairs()]
+        return (fold_conv_bn(self.conv1.weight, self.bn1) + ({},), [blk.folded_operands() for blk in blocks]), pair_sources(pairs)
 
     def _ext_features_folded(self, x):
         (ws, bs, ops), blocks = self._folded[:2]
