@@ -731,6 +731,27 @@ int segx_onehot_colormap(const float* nhot, const uint8_t* colormap, uint8_t* ou
  * the whole call.  No copy to the host, no synchronisation: the call can be captured. */
 int segx_onehot_case_tail(const float* soft, const uint8_t* gt, const uint8_t* colormap, int32_t* counts, uint8_t* labels, uint8_t* rgb, int B, int C, int64_t S,
                           float T, void* stream);
+/* The evaluation tail of an n-hot 2-D task (fundus: bg / disc / cup, polyp: bg / polyp) in one pass over the DESTINATION grid [H][W] -- the ground truth's size or
+ * the export size -- (test_util2d.py:241-265 calc_batch_metric with the vCDR extents of utils/losses.py:76-127, test_util2d.py:93-106 the export): the n-hot
+ * counterpart of segx_onehot_case_tail, with its counting scheme, workgroup size, grid cap and alignment rule (SEGX_CASE_TAIL_*), one grid row per image.
+ *   soft [B][C][h][w] as segx_window_merge leaves it; T the hardening threshold.  Per destination pixel the C prediction values are soft itself when
+ *     (h, w) == (H, W), else the bilinear resample (align_corners = false) that segx_interp_linear_fwd writes, the same inline expression, bit for bit; they are
+ *     hardened as segx_harden_segmap does in mode 0: class c >= 1 is on where the value >= T (a NaN is off), class 0 where no other class is.
+ *   gt, read in the form gt_map names:  0: n-hot float32 [B][C][H][W], class c on where the value >= 0.5;  1 / 2: the raw fundus mask uint8 [B][gt_channels >= 2][H][W]
+ *     mapped as fundus_map_mask(exclusive = false / true) (datasets2d.py:90-142; C == 3): disc = ch0 >= 1 (exclusive: and ch1 == 0), cup = ch1 >= 1;  3: the raw polyp
+ *     mask uint8 [B][gt_channels >= 1][H][W] mapped as polyp_map_mask (datasets2d.py:200-223; C == 2): polyp = ch0 > 0.  gt_channels is not read with gt_map 0.
+ *   counts [B][C-1][3] (int32, initialised here): {sum pred * gt, sum pred, sum gt} for c = 1..C-1.  Vector integer atomic adds, one per counter per workgroup.
+ *   ext [B][2][2][2] (int32, initialised here): for {prediction, ground truth} x {class 1, class 2} the lowest and the highest row that holds the class, (H, -1)
+ *     for an empty class -- segx_row_extent's convention; with C == 2 the class-2 entries stay empty.  Integer atomicMin / atomicMax, one per extent per
+ *     workgroup after a reduction inside it.
+ *   labels [B][H][W] (uint8): 0, then values[c] (int32 [C] in device memory) for ascending c where class c is on -- segx_nhot_to_values of the hardened map.
+ *   hard [B][C][H][W] (float32): the hardened map at the destination size.
+ * Every result is an integer or a 0 / 1 float: exact and independent of the order of execution.  Each output may be NULL, but not all four; counts and ext need gt,
+ * labels need values.  1 <= B <= 65535, 2 <= C <= SEGX_MAX_CLASSES, h, w > 0, 0 < H * W < 2^31, gt_map in 0..3 with the class count it implies.  Wide accesses
+ * (16-byte for soft on the no-resample path, the float gt and hard; dword for the mask bytes and labels) when H * W % 4 == 0 and those operands are aligned for them,
+ * else dword loads and byte accesses for the whole call.  No copy to the host, no synchronisation: the call can be captured. */
+int segx_nhot_case_tail(const float* soft, const void* gt, int gt_map, int gt_channels, const int32_t* values, int32_t* counts, int32_t* ext, uint8_t* labels,
+                        float* hard, int B, int C, int h, int w, int H, int W, float T, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Tail of the 2-D evaluation (components.hip): connected components, fragment removal (test_util2d.py:267-289), row extents for the vertical cup/disc ratio

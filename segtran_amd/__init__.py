@@ -23,4 +23,7 @@ def __getattr__(name):
     if name == 'GraphedSlidingWindow3d':        # infer3d.GraphedSlidingWindow3d: the same for one volume shape, with the BraTS case tail (label volume, metric counts)
         from .infer3d import GraphedSlidingWindow3d
         return GraphedSlidingWindow3d
+    if name == 'GraphedBatchEvaluation':        # infer2d.GraphedBatchEvaluation: GraphedSlidingWindow with the n-hot tasks' tail (metric counts, row extents, label images)
+        from .infer2d import GraphedBatchEvaluation
+        return GraphedBatchEvaluation
     raise AttributeError('module %r has no attribute %r' % (__name__, name))

@@ -8,7 +8,9 @@
 // And the tail of one BraTS case (test_util3d.py:36-38, 67, 82-85) in one pass over the voxels:
 //   brats_case_tail  counts[c-1] = {sum pred * gt, sum pred, sum gt} for the three foreground classes, the ground truth mapped from the raw labels in registers, and
 //                    labels = argmax(brats_inv_map_label(soft)) with 3 written as 4.  int32 counts through integer atomic adds: exact, order-independent.
-#include "common.h"
+// The one-hot tasks' tail (onehot_case_tail) and the n-hot 2-D tasks' (nhot_case_tail: fundus, polyp) follow the same scheme, one grid row per image.
+#include "resample.h"
+#include "harden.h"
 
 namespace segx {
 
@@ -347,6 +349,245 @@ __global__ __launch_bounds__(CT_THREADS) void onehot_case_tail_kernel(const floa
     }
 }
 
+// ---- n-hot 2-D tasks (fundus: bg / disc / cup, polyp: bg / polyp; test_util2d.py:241-265, datasets2d.py:90-171, utils/losses.py:76-127) ----
+struct NhotTail { int C, Cm, gt_map, same; float T; };   // Cm: channels of the raw mask (gt_map 1..3); same: (h, w) == (H, W), soft is read as it is
+
+// counts[0 .. ncounts) = 0 and every (lowest, highest) pair of ext = (H, -1), segx_row_extent's empty extent; either may be NULL
+__global__ __launch_bounds__(256) void nhot_tail_init_kernel(int* __restrict__ counts, int ncounts, int* __restrict__ ext, int npairs, int H) {
+    const int n = ncounts > npairs ? ncounts : npairs;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        if (counts && i < ncounts) counts[i] = 0;
+        if (ext && i < npairs) { ext[2 * i] = H; ext[2 * i + 1] = -1; }
+    }
+}
+
+__device__ __forceinline__ int wave_min_int(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ int wave_max_int(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
+    return v;
+}
+
+// harden_cell in mode 0 on one pixel's C values, its 0 / 1 planes as bits: bit c = class c is on (bit 0: no other class is)
+template <int MAXC>
+__device__ __forceinline__ unsigned harden_bits(float* p, int C, float T) {
+    float hd[MAXC];
+    harden_cell<MAXC>(p, C, 0, T, nullptr, hd, 1);
+    unsigned bits = 0;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c)
+        if (c < C && hd[c] == 1.0f) bits |= 1u << c;
+    return bits;
+}
+
+// The evaluation tail of an n-hot 2-D task: one pass over the DESTINATION grid [H][W] of image blockIdx.y, the scheme of onehot_case_tail_kernel (a thread owns four
+// consecutive pixels per trip of the grid-stride loop; VEC: H * W % 4 == 0 and every operand aligned, so a plane's quad is one 16-byte access and four bytes one dword).
+// Per pixel: the C prediction values -- soft itself (t.same) or interp_at of the [h][w] plane, the expression of interp_fwd_kernel, hence SF.interp_linear's bits --
+// hardened by harden_cell (mode 0) into bits; the ground truth's bits from the n-hot floats (gt_map 0: >= 0.5) or from the raw fundus / polyp mask bytes (1..3),
+// mapped in registers.  From the two bit sets: counts (as onehot_case_tail_kernel), the row extents of classes 1 and 2 of both (per thread min / max of the rows it
+// saw, wave shuffles, LDS, one atomicMin / atomicMax per extent per workgroup), the label bytes (values[c] of the last class on) and the hardened floats.
+// counts / ext / labels / hard == NULL: not formed; gt == NULL: not read (all uniform over the grid).
+template <int MAXC, bool VEC>
+__global__ __launch_bounds__(CT_THREADS) void nhot_case_tail_kernel(const float* __restrict__ soft, const void* __restrict__ gt, const int* __restrict__ values,
+                                                                    int* __restrict__ counts, int* __restrict__ ext, uint8_t* __restrict__ labels,
+                                                                    float* __restrict__ hard, InterpDims q, NhotTail t) {
+    __shared__ int red[CT_WAVES][3 * (MAXC - 1)];
+    __shared__ int redx[CT_WAVES][8];
+    const int C = t.C, W = q.W;
+    const int64_t b = blockIdx.y, S = (int64_t)q.H * q.W, ssz = (int64_t)q.h * q.w;
+    soft += b * C * ssz;
+    const float* gtf = gt && t.gt_map == 0 ? reinterpret_cast<const float*>(gt) + b * C * S : nullptr;
+    const uint8_t* gtb = gt && t.gt_map != 0 ? reinterpret_cast<const uint8_t*>(gt) + b * t.Cm * S : nullptr;
+    int vals[MAXC];
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) vals[c] = (labels && c < C) ? values[c] : 0;
+    int ci[MAXC - 1], cp[MAXC - 1], cg[MAXC - 1];
+#pragma unroll
+    for (int c = 0; c < MAXC - 1; ++c) { ci[c] = 0; cp[c] = 0; cg[c] = 0; }
+    int lo[4], hi[4];                                                           // {prediction, ground truth} x {class 1, class 2}
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { lo[k] = q.H; hi[k] = -1; }
+    const int64_t quads = (S + 3) >> 2;
+    for (int64_t qd = (int64_t)blockIdx.x * CT_THREADS + threadIdx.x; qd < quads; qd += (int64_t)gridDim.x * CT_THREADS) {
+        const int64_t s = qd << 2;
+        const int n = VEC ? 4 : (int)i64min(4, S - s);
+        int yj[4], xj[4];                                                       // the four pixels' rows and columns
+        yj[0] = (int)(s / W); xj[0] = (int)(s - (int64_t)yj[0] * W);
+#pragma unroll
+        for (int j = 1; j < 4; ++j) {
+            const bool wrap = xj[j - 1] + 1 == W;
+            xj[j] = wrap ? 0 : xj[j - 1] + 1; yj[j] = yj[j - 1] + (wrap ? 1 : 0);
+        }
+        unsigned pb[4] = {0, 0, 0, 0}, gb[4] = {0, 0, 0, 0};                    // a cut quad's missing pixels have no bit: they count nowhere
+        if (t.same) {
+            float v[MAXC][4];
+#pragma unroll
+            for (int c = 0; c < MAXC; ++c) {
+                v[c][0] = v[c][1] = v[c][2] = v[c][3] = 0.0f;
+                if (c < C) {
+                    if (VEC) {
+                        const float4 a = *reinterpret_cast<const float4*>(soft + c * S + s);
+                        v[c][0] = a.x; v[c][1] = a.y; v[c][2] = a.z; v[c][3] = a.w;
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            if (j < n) v[c][j] = soft[c * S + s + j];
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (j < n) {
+                    float p[MAXC];
+#pragma unroll
+                    for (int c = 0; c < MAXC; ++c) p[c] = v[c][j];
+                    pb[j] = harden_bits<MAXC>(p, C, t.T);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (j < n) {
+                    float p[MAXC];
+#pragma unroll
+                    for (int c = 0; c < MAXC; ++c) {
+                        p[c] = 0.0f;
+                        if (c < C) p[c] = interp_at(soft + c * ssz, q, 0, yj[j], xj[j]);
+                    }
+                    pb[j] = harden_bits<MAXC>(p, C, t.T);
+                }
+            }
+        }
+        if (gtf) {                                                              // n-hot floats: class c is on where the value is >= 0.5
+#pragma unroll
+            for (int c = 1; c < MAXC; ++c) {
+                if (c < C) {
+                    float g[4] = {0.f, 0.f, 0.f, 0.f};
+                    if (VEC) {
+                        const float4 a = *reinterpret_cast<const float4*>(gtf + c * S + s);
+                        g[0] = a.x; g[1] = a.y; g[2] = a.z; g[3] = a.w;
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            if (j < n) g[j] = gtf[c * S + s + j];
+                    }
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (g[j] >= 0.5f) gb[j] |= 1u << c;
+                }
+            }
+        } else if (gtb) {                                                       // raw mask bytes: fundus_map_mask / polyp_map_mask (datasets2d.py:90-142, 200-223)
+            unsigned m0[4] = {0, 0, 0, 0}, m1[4] = {0, 0, 0, 0};
+            const bool two = t.gt_map != 3;
+            if (VEC) {
+                const uint32_t l0 = *reinterpret_cast<const uint32_t*>(gtb + s), l1 = two ? *reinterpret_cast<const uint32_t*>(gtb + S + s) : 0u;
+                m0[0] = l0 & 255; m0[1] = (l0 >> 8) & 255; m0[2] = (l0 >> 16) & 255; m0[3] = l0 >> 24;
+                m1[0] = l1 & 255; m1[1] = (l1 >> 8) & 255; m1[2] = (l1 >> 16) & 255; m1[3] = l1 >> 24;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (j < n) { m0[j] = gtb[s + j]; if (two) m1[j] = gtb[S + s + j]; }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const unsigned disc = m0[j] >= 1, cup = m1[j] >= 1;             // polyp: `disc` is the polyp class, m1 stays 0
+                gb[j] = ((t.gt_map == 2 ? disc & (cup ^ 1u) : disc) << 1) | (cup << 2);
+            }
+        }
+        if (counts) {
+#pragma unroll
+            for (int c = 1; c < MAXC; ++c) {
+                if (c < C) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int on = (pb[j] >> c) & 1, hit = (gb[j] >> c) & 1;
+                        ci[c - 1] += on & hit; cp[c - 1] += on; cg[c - 1] += hit;
+                    }
+                }
+            }
+        }
+        if (ext) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (pb[j] & 2u) { lo[0] = min(lo[0], yj[j]); hi[0] = max(hi[0], yj[j]); }
+                if (pb[j] & 4u) { lo[1] = min(lo[1], yj[j]); hi[1] = max(hi[1], yj[j]); }
+                if (gb[j] & 2u) { lo[2] = min(lo[2], yj[j]); hi[2] = max(hi[2], yj[j]); }
+                if (gb[j] & 4u) { lo[3] = min(lo[3], yj[j]); hi[3] = max(hi[3], yj[j]); }
+            }
+        }
+        if (labels) {                                                           // nhot_to_values: ascending, a later class wins; 0 where none is on
+            unsigned lab[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                int val = 0;
+#pragma unroll
+                for (int c = 0; c < MAXC; ++c)
+                    if (c < C && ((pb[j] >> c) & 1)) val = vals[c];
+                lab[j] = (unsigned)(uint8_t)val;
+            }
+            if (VEC) {
+                *reinterpret_cast<uint32_t*>(labels + b * S + s) = lab[0] | (lab[1] << 8) | (lab[2] << 16) | (lab[3] << 24);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (j < n) labels[b * S + s + j] = (uint8_t)lab[j];
+            }
+        }
+        if (hard) {
+            float* hb = hard + b * C * S + s;
+#pragma unroll
+            for (int c = 0; c < MAXC; ++c) {
+                if (c < C) {
+                    if (VEC) {
+                        *reinterpret_cast<float4*>(hb + c * S) = make_float4((pb[0] >> c) & 1 ? 1.0f : 0.0f, (pb[1] >> c) & 1 ? 1.0f : 0.0f,
+                                                                             (pb[2] >> c) & 1 ? 1.0f : 0.0f, (pb[3] >> c) & 1 ? 1.0f : 0.0f);
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            if (j < n) hb[c * S + j] = (pb[j] >> c) & 1 ? 1.0f : 0.0f;
+                    }
+                }
+            }
+        }
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (counts) {                                                               // wave -> LDS -> one atomic add per counter per workgroup
+#pragma unroll
+        for (int c = 0; c < MAXC - 1; ++c) {
+            if (c < C - 1) {
+                const int a = wave_sum_int(ci[c]), p = wave_sum_int(cp[c]), h = wave_sum_int(cg[c]);
+                if (lane == 0) { red[wave][3 * c] = a; red[wave][3 * c + 1] = p; red[wave][3 * c + 2] = h; }
+            }
+        }
+    }
+    if (ext) {                                                                  // wave -> LDS -> one atomicMin / atomicMax per extent per workgroup
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int l = wave_min_int(lo[k]), h = wave_max_int(hi[k]);
+            if (lane == 0) { redx[wave][2 * k] = l; redx[wave][2 * k + 1] = h; }
+        }
+    }
+    __syncthreads();
+    if (counts && (int)threadIdx.x < 3 * (C - 1)) {
+        int tot = 0;
+#pragma unroll
+        for (int w = 0; w < CT_WAVES; ++w) tot += red[w][threadIdx.x];
+        if (tot) atomicAdd(counts + b * 3 * (C - 1) + threadIdx.x, tot);
+    }
+    if (ext && threadIdx.x < 8) {                                               // ext[b][which][class][lowest, highest]: even entries are minima, odd ones maxima
+        const bool is_max = threadIdx.x & 1;
+        int e = redx[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < CT_WAVES; ++w) e = is_max ? max(e, redx[w][threadIdx.x]) : min(e, redx[w][threadIdx.x]);
+        if (is_max) { if (e >= 0) atomicMax(ext + b * 8 + threadIdx.x, e); }
+        else if (e < q.H) atomicMin(ext + b * 8 + threadIdx.x, e);
+    }
+}
+
 }  // namespace segx
 
 using namespace segx;
@@ -451,4 +692,44 @@ extern "C" int segx_onehot_case_tail(const float* soft, const uint8_t* gt, const
     if (C <= 8) launch_onehot_case_tail<8>(vec, grid, stream, soft, gt, colormap, counts, labels, rgb, C, S, T);
     else launch_onehot_case_tail<SEGX_MAX_CLASSES>(vec, grid, stream, soft, gt, colormap, counts, labels, rgb, C, S, T);
     return check_launch("segx_onehot_case_tail");
+}
+
+template <int MAXC>
+static void launch_nhot_case_tail(bool vec, dim3 grid, hipStream_t stream, const float* soft, const void* gt, const int32_t* values, int32_t* counts, int32_t* ext,
+                                  uint8_t* labels, float* hard, InterpDims q, NhotTail t) {
+    if (vec) hipLaunchKernelGGL((nhot_case_tail_kernel<MAXC, true>), grid, dim3(CT_THREADS), 0, stream, soft, gt, values, counts, ext, labels, hard, q, t);
+    else hipLaunchKernelGGL((nhot_case_tail_kernel<MAXC, false>), grid, dim3(CT_THREADS), 0, stream, soft, gt, values, counts, ext, labels, hard, q, t);
+}
+
+extern "C" int segx_nhot_case_tail(const float* soft, const void* gt, int gt_map, int gt_channels, const int32_t* values, int32_t* counts, int32_t* ext,
+                                   uint8_t* labels, float* hard, int B, int C, int h, int w, int H, int W, float T, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(soft, "segx_nhot_case_tail: null soft");
+    SEGX_REQUIRE(counts || ext || labels || hard, "segx_nhot_case_tail: none of counts, ext, labels and hard asked for");
+    SEGX_REQUIRE(!counts || gt, "segx_nhot_case_tail: counts need the ground truth");
+    SEGX_REQUIRE(!ext || gt, "segx_nhot_case_tail: the ground-truth extents need the ground truth");
+    SEGX_REQUIRE(!labels || values, "segx_nhot_case_tail: labels need the value table");
+    SEGX_REQUIRE(B > 0 && B <= 65535, "segx_nhot_case_tail: B = %d is not in 1 .. 65535", B);
+    SEGX_REQUIRE(C >= 2 && C <= SEGX_MAX_CLASSES, "segx_nhot_case_tail: C = %d is not in 2 .. %d", C, SEGX_MAX_CLASSES);
+    SEGX_REQUIRE(h > 0 && w > 0, "segx_nhot_case_tail: the source size %d x %d must be positive", h, w);
+    SEGX_REQUIRE(H > 0 && W > 0 && (int64_t)H * W < ((int64_t)1 << 31), "segx_nhot_case_tail: H * W = %lld is not in 1 .. 2^31 - 1", (long long)H * W);
+    SEGX_REQUIRE(gt_map >= 0 && gt_map <= 3, "segx_nhot_case_tail: gt_map %d is not 0 (n-hot), 1 / 2 (fundus, exclusive) or 3 (polyp)", gt_map);
+    if (gt && (gt_map == 1 || gt_map == 2))
+        SEGX_REQUIRE(C == 3 && gt_channels >= 2, "segx_nhot_case_tail: a fundus mask has >= 2 channels and maps to 3 classes, not %d and %d", gt_channels, C);
+    if (gt && gt_map == 3)
+        SEGX_REQUIRE(C == 2 && gt_channels >= 1, "segx_nhot_case_tail: a polyp mask has >= 1 channel and maps to 2 classes, not %d and %d", gt_channels, C);
+    if (counts || ext) {
+        const int ncounts = counts ? B * 3 * (C - 1) : 0, npairs = ext ? B * 4 : 0, n = ncounts > npairs ? ncounts : npairs;
+        hipLaunchKernelGGL(nhot_tail_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, counts, ncounts, ext, npairs, H);
+    }
+    const int64_t S = (int64_t)H * W;
+    NhotTail t; t.C = C; t.Cm = gt_map == 0 ? C : gt_channels; t.gt_map = gt_map; t.same = h == H && w == W; t.T = T;
+    // a plane starts a multiple of S elements into its tensor: wide accesses are legal only when S % 4 == 0.  soft is read wide only on the no-resample path.
+    const uintptr_t a16 = (t.same ? (uintptr_t)soft : 0) | (uintptr_t)hard | (gt && gt_map == 0 ? (uintptr_t)gt : 0);
+    const uintptr_t a4 = (uintptr_t)labels | (gt && gt_map != 0 ? (uintptr_t)gt : 0);
+    const bool vec = S % 4 == 0 && a16 % 16 == 0 && a4 % 4 == 0;
+    const dim3 grid((unsigned)i64min(SEGX_CASE_TAIL_MAX_BLOCKS, ((S + 3) / 4 + CT_THREADS - 1) / CT_THREADS), (unsigned)B);
+    const InterpDims q = make_dims(1, h, w, 1, H, W);
+    if (C <= 8) launch_nhot_case_tail<8>(vec, grid, stream, soft, gt, values, counts, ext, labels, hard, q, t);
+    else launch_nhot_case_tail<SEGX_MAX_CLASSES>(vec, grid, stream, soft, gt, values, counts, ext, labels, hard, q, t);
+    return check_launch("segx_nhot_case_tail");
 }

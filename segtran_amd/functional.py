@@ -2846,9 +2846,95 @@ def nhot_to_values(nhot, values):
     out = torch.empty((B,) + tuple(x.shape[2:]), dtype=torch.uint8, device=x.device)
     if out.numel() == 0:
         raise ValueError('nhot_to_values: empty tensor %s' % (tuple(nhot.shape),))
-    key = (values, x.device)
+    segx.lib().nhot_to_values(x, _value_table('nhot_to_values', values, C, x.device), out, B, C, out.numel() // B)
+    return out
+
+
+def _value_table(what, values, C, device):
+    """the int32 [C] device table of C pixel values 0..255, built once per device and kept (the cache nhot_to_values fills)"""
+    values = tuple(_uint8_value(what + ': values', v) for v in values)
+    if len(values) != C:
+        raise ValueError('%s: %d values for %d classes' % (what, len(values), C))
+    key = (values, device)
     table = _VALUE_TABLES.get(key)
     if table is None:
-        table = _VALUE_TABLES[key] = torch.tensor(values, dtype=torch.int32, device=x.device)
-    segx.lib().nhot_to_values(x, table, out, B, C, out.numel() // B)
-    return out
+        table = _VALUE_TABLES[key] = torch.tensor(values, dtype=torch.int32, device=device)
+    return table
+
+
+def _tail_output(what, name, given, want, shape, dtype, device):
+    """an output of a tail launch: the caller's tensor (checked), a new one when wanted, else None"""
+    if given is not None:
+        if given.dtype != dtype or tuple(given.shape) != tuple(shape) or not given.is_contiguous() or given.device != device:
+            raise ValueError('%s: %s is a contiguous %s %s tensor on %s' % (what, name, str(dtype).replace('torch.', ''), list(shape), device))
+        return given
+    return torch.empty(shape, dtype=dtype, device=device) if want else None
+
+
+def nhot_case_tail(soft, gt=None, size=None, gt_map='nhot', values=None, T=0.5, want_extents=False, want_hard=False, counts=None, ext=None, labels=None,
+                   hard=None):
+    """The evaluation tail of an n-hot 2-D task (fundus, polyp) in one launch (segx_nhot_case_tail), one pass over the destination grid `size` = (H, W) (default: the
+    ground truth's): soft float32 [B, C, h, w] as window_merge leaves it is resampled to it (interp_linear's values bit for bit; read as it is when the sizes agree)
+    and hardened (harden_segmap mode 0, threshold T).  gt, in the form gt_map names, or None:
+      'nhot': float32 [B, C, H, W] n-hot maps, class c on where the value >= 0.5 (what fundus_map_mask / polyp_map_mask return);
+      'fundus' / 'fundus_exclusive': the raw uint8 mask [B, >= 2, H, W], mapped in registers as fundus_map_mask(mask, exclusive=False / True) (C == 3);
+      'polyp': the raw uint8 mask [B, >= 1, H, W], mapped as polyp_map_mask (C == 2).
+    Returns (counts, ext, labels, hard), None for what was not asked for:
+      counts int32 [B, C - 1, 3] -- per image and foreground class {sum pred * gt, sum pred, sum gt}; formed whenever gt is given;
+      ext int32 [B, 2, 2, 2] -- for {prediction, ground truth} x {class 1, class 2} the (lowest, highest) row holding the class, (H, -1) when empty: row_extent of
+        the hardened and the ground-truth maps; with want_extents (needs gt);
+      labels uint8 [B, H, W] -- nhot_to_values(hard, values); whenever `values` (C ints 0..255; the device table is built once per device and kept) is given;
+      hard float32 [B, C, H, W] -- the hardened map at the destination size; with want_hard.
+    counts / ext / labels / hard: tensors to write into (a captured graph passes its static ones); passing one asks for it.  No copy to the host, no synchronisation.
+    Forward only."""
+    what = 'nhot_case_tail'
+    _no_grad_operands(what, soft, gt)
+    if soft.dim() != 4 or soft.dtype != torch.float32:
+        raise ValueError('%s: soft %s %s must be a float32 [B, C, h, w] tensor' % (what, soft.dtype, tuple(soft.shape)))
+    B, C, h, w = soft.shape
+    C = _class_count(what, C, low=2)
+    if gt_map not in segx.SegxLib.NHOT_GT_MAPS:
+        raise ValueError('%s: gt_map %r is not one of %s' % (what, gt_map, sorted(segx.SegxLib.NHOT_GT_MAPS)))
+    if size is None:
+        if gt is None:
+            raise ValueError('%s: no gt and no size: the destination grid is unknown' % what)
+        size = tuple(gt.shape[-2:])
+    H, W = (int(v) for v in size)
+    if B < 1 or h < 1 or w < 1 or H < 1 or W < 1:
+        raise ValueError('%s: empty operand: soft %s, size %s' % (what, tuple(soft.shape), (H, W)))
+    if H * W >= 1 << 31:
+        raise ValueError('%s: H * W = %d is not below 2^31' % (what, H * W))
+    soft = _c(soft.detach())
+    dev = soft.device
+    gt_channels = C
+    if gt is None:
+        if counts is not None or ext is not None or want_extents:
+            raise ValueError('%s: counts and extents need gt' % what)
+    else:
+        if gt.dim() != 4 or gt.shape[0] != B or tuple(gt.shape[2:]) != (H, W):
+            raise ValueError('%s: gt %s is no [%d, channels, %d, %d] tensor' % (what, tuple(gt.shape), B, H, W))
+        gt_channels = int(gt.shape[1])
+        if gt_map == 'nhot':
+            if gt_channels != C or not gt.is_floating_point():
+                raise ValueError('%s: an n-hot gt is a float [%d, %d, %d, %d] tensor, not %s %s' % (what, B, C, H, W, gt.dtype, tuple(gt.shape)))
+            gt = _c(gt.detach().float())
+        else:
+            need_c, need_m = (2, 1) if gt_map == 'polyp' else (3, 2)
+            if gt.dtype != torch.uint8 or gt_channels < need_m or C != need_c:
+                raise ValueError('%s: a raw %s mask is uint8 with >= %d channels for %d classes, not %s %s for %d' %
+                                 (what, gt_map, need_m, need_c, gt.dtype, tuple(gt.shape), C))
+            gt = _c(gt.detach())
+        counts = _tail_output(what, 'counts', counts, True, (B, C - 1, 3), torch.int32, dev)
+        ext = _tail_output(what, 'ext', ext, want_extents, (B, 2, 2, 2), torch.int32, dev)
+    table = None
+    if values is None:
+        if labels is not None:
+            raise ValueError('%s: labels need values' % what)
+    else:
+        table = _value_table(what, values, C, dev)
+        labels = _tail_output(what, 'labels', labels, True, (B, H, W), torch.uint8, dev)
+    hard = _tail_output(what, 'hard', hard, want_hard, (B, C, H, W), torch.float32, dev)
+    if counts is None and ext is None and labels is None and hard is None:
+        raise ValueError('%s: nothing to compute (no gt, no values and want_hard=False)' % what)
+    segx.lib().nhot_case_tail(soft, gt, segx.SegxLib.NHOT_GT_MAPS[gt_map], gt_channels, table, counts, ext, labels, hard, B, C, h, w, H, W, T)
+    return counts, ext, labels, hard

@@ -4,7 +4,9 @@
 test_util2d.py mirrors the reference's file of that name and keeps the reference's signatures; the switch lives here.  So does the tail of the evaluation after
 preds_soft: calc_vcdr, calc_batch_metric with the vCDR-error column, remove_fragmentary_segs, export_masks; and the one-hot tasks' form of it
 (DESIGN.md 5t): calc_batch_metric_onehot and test_all_cases(gt_is_index=True), which work from index masks through one tail launch.  fold_bn=True folds the (eval-mode) net for
-the call if it is not folded already (Segtran2d.fold_batchnorm) and unfolds it afterwards; a net the caller folded stays folded."""
+the call if it is not folded already (Segtran2d.fold_batchnorm) and unfolds it afterwards; a net the caller folded stays folded.  The n-hot tasks (fundus, polyp)
+have the tail as one launch as well: SF.nhot_case_tail behind calc_batch_metric(fused=True), test_all_cases(device_tail=True) and
+export_masks(fused=True), and captured with the forward in GraphedBatchEvaluation."""
 import math
 
 import torch
@@ -12,7 +14,7 @@ import torch
 from . import functional as SF
 from . import test_util2d as _T2
 from .test_util2d import calc_dice          # noqa: F401  (same module surface)
-from .dataloaders.datasets2d import harden_segmap2d
+from .dataloaders.datasets2d import fundus_inv_map_mask, harden_segmap2d, polyp_inv_map_mask
 from .infer_common import PRECISIONS, GraphedEvaluation, _precision, folded, inference_precision, run_chunks      # noqa: F401  (same module surface)
 
 
@@ -117,10 +119,64 @@ def calc_vcdr(mask_nhot_soft, thres=0.5, delta=1):
     return torch.where(ext[0, 1] < 0, -1., vcdr)            # no disc (tested first in the reference)
 
 
-def calc_batch_metric(BC_pred_soft, BC_gt, num_classes, do_calc_vcdr_error=False):
+def vcdr_from_extents(ext, delta=1):
+    """calc_vcdr's [C, H, W] branch from row extents, for a batch: ext int32 [B, 2, 2, 2] as SF.nhot_case_tail returns it ({prediction, ground truth} x {disc, cup} x
+    (lowest, highest) row; (H, -1) when empty) -> (vcdr of the predictions, vcdr of the ground truths), float32 [B] tensors on the device; ext [B, 2, 2] (one of the
+    halves) -> one such tensor.  The operations and dtypes are calc_vcdr's (int64 lengths, float32 quotient with + 0.0001, 0. without a cup, then -1. without a
+    disc), elementwise: entry i is calc_vcdr(map_i) bit for bit.  No copy to the host."""
+    if ext.dim() not in (3, 4) or tuple(ext.shape[-2:]) != (2, 2) or (ext.dim() == 4 and ext.shape[1] != 2):
+        raise ValueError('vcdr_from_extents: row extents [B, 2, 2, 2] or [B, 2, 2], not %s' % (tuple(ext.shape),))
+    e = ext.long()
+    length = e[..., 1] - e[..., 0] - delta                    # [..., class]
+    vcdr = length[..., 1] / (length[..., 0] + 0.0001)
+    vcdr = torch.where(e[..., 1, 1] < 0, 0., vcdr)            # no cup
+    vcdr = torch.where(e[..., 0, 1] < 0, -1., vcdr)           # no disc
+    return (vcdr[:, 0], vcdr[:, 1]) if ext.dim() == 4 else vcdr
+
+
+def _equal_runs(keys):
+    """[(i0, i1)]: the maximal runs of consecutive equal entries of keys"""
+    runs, i0 = [], 0
+    for i in range(1, len(keys) + 1):
+        if i == len(keys) or keys[i] != keys[i0]:
+            runs.append((i0, i))
+            i0 = i
+    return runs
+
+
+def _batched(items, i0, i1):
+    """items[i0:i1] as one [n, ...] tensor: a slice of a tensor, a stack of a list's entries"""
+    return items[i0:i1] if isinstance(items, torch.Tensor) else torch.stack(list(items[i0:i1]))
+
+
+def _nhot_metric_rows(preds_soft, gt, num_classes, do_calc_vcdr_error, gt_map='nhot'):
+    """float32 [B, num_classes - 1 (+ 1)] on the device: the rows of calc_batch_metric for one batch of equally sized masks from ONE tail launch -- Dice as calc_dice's
+    expression on the integer counts, then |vCDR(gt) - vCDR(pred)| from the row extents"""
+    if preds_soft.shape[1] != num_classes:
+        raise ValueError('preds_soft has %d classes, not %d' % (preds_soft.shape[1], num_classes))
+    counts, ext, _, _ = SF.nhot_case_tail(preds_soft.float(), gt, gt_map=gt_map, want_extents=do_calc_vcdr_error)
+    c, smooth = counts.float(), 1e-5
+    rows = (2 * c[..., 0] + smooth) / (c[..., 1] + c[..., 2] + smooth)                          # SF.dice_scores' expression on the same sums
+    if do_calc_vcdr_error:
+        vcdr_pred, vcdr_gt = vcdr_from_extents(ext)
+        rows = torch.cat([rows, (vcdr_gt - vcdr_pred).abs().unsqueeze(1)], dim=1)
+    return rows
+
+
+def calc_batch_metric(BC_pred_soft, BC_gt, num_classes, do_calc_vcdr_error=False, fused=False):
     """reference test_util2d.py:241-265.  The default is test_util2d.calc_batch_metric, unchanged (that function still refuses the flag); with do_calc_vcdr_error
     the table has one more column, |calc_vcdr(gt) - calc_vcdr(pred)| (:259-263, the fundus task's own metric): that function's loop -- resample, harden, Dice,
-    the same calls, so the Dice columns are the default's bit for bit -- with the column computed from the same hardened maps."""
+    the same calls, so the Dice columns are the default's bit for bit -- with the column computed from the same hardened maps.
+    fused: the table from ONE tail launch (SF.nhot_case_tail; one per run of equally sized masks when BC_gt is a list of differently sized maps) and ONE read: the
+    resampled and the hardened maps never exist.  Integer counts and extents, the same float32 expressions: the table equals the default's exactly while a plane has
+    fewer than 2^24 pixels (float32 holds the default's sums exactly up to there)."""
+    if fused:
+        with torch.no_grad():
+            keys = [(tuple(p.shape), tuple(g.shape)) for p, g in zip(BC_pred_soft, BC_gt)]
+            if len(keys) != len(BC_pred_soft) or len(keys) != len(BC_gt) or not keys:
+                raise ValueError('calc_batch_metric: %d predictions for %d masks' % (len(BC_pred_soft), len(BC_gt)))
+            rows = [_nhot_metric_rows(_batched(BC_pred_soft, i0, i1), _batched(BC_gt, i0, i1), num_classes, do_calc_vcdr_error) for i0, i1 in _equal_runs(keys)]
+            return torch.cat(rows).cpu().numpy().astype(_T2.np.float64)                         # the one read
     if not do_calc_vcdr_error:
         return _T2.calc_batch_metric(BC_pred_soft, BC_gt, num_classes)
     out = _T2.np.zeros((len(BC_pred_soft), num_classes))
@@ -183,17 +239,26 @@ def calc_batch_metric_onehot(preds_soft, gt_index, num_classes):
 
 
 def test_all_cases(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, mask_prepred_mapping_func=None, fold_bn=False, fused=False,
-                   window_batch=None, precision='fp32', do_calc_vcdr_error=False, gt_is_index=False):
+                   window_batch=None, precision='fp32', do_calc_vcdr_error=False, gt_is_index=False, device_tail=False, gt_map='nhot'):
     """test_util2d.test_all_cases; fold_bn: ONE fold for all the batches; fused / window_batch / precision: as test_single_batch; do_calc_vcdr_error: the vCDR
     error as one more entry (both returned vectors then have num_classes entries, as in the reference).
     gt_is_index (one-hot tasks: oct): the masks are index masks [B, H, W] / [B, 1, H, W] and stay so -- no mapping function, no one-hot mask, no hardened map; each
     batch's Dice rows are formed on the device from the integer counts of SF.onehot_case_tail (calc_dice's expression in float32) and stay there; they are read
-    ONCE after the last batch and summed as the default path sums its tables."""
-    if gt_is_index and (do_calc_vcdr_error or mask_prepred_mapping_func is not None):
-        raise ValueError('test_all_cases: gt_is_index takes the index masks as they are (no mask_prepred_mapping_func) and has no vCDR column')
+    ONCE after the last batch and summed as the default path sums its tables.
+    device_tail (n-hot tasks: fundus, polyp): the same for n-hot masks -- ONE tail launch per batch (SF.nhot_case_tail) forms the Dice rows and, with
+    do_calc_vcdr_error, the vCDR-error column on the device; they are read ONCE after the last batch and summed in the default path's order, so (mean, count)
+    equals the default's.  gt_map ('fundus', 'fundus_exclusive', 'polyp'; needs device_tail): the batches hold the RAW uint8 masks, mapped inside the tail launch
+    -- the n-hot mask never exists; it excludes mask_prepred_mapping_func."""
+    if gt_is_index and (do_calc_vcdr_error or mask_prepred_mapping_func is not None or device_tail):
+        raise ValueError('test_all_cases: gt_is_index takes the index masks as they are (no mask_prepred_mapping_func, no device_tail) and has no vCDR column')
+    if gt_map != 'nhot' and (not device_tail or mask_prepred_mapping_func is not None):
+        raise ValueError('test_all_cases: gt_map=%r reads the raw masks in the tail launch: it needs device_tail=True and excludes mask_prepred_mapping_func' % (gt_map,))
     with _precision(precision), _folded(net, fold_bn):
         if gt_is_index:
             return _test_all_cases_index(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, fused, window_batch)
+        if device_tail:
+            return _test_all_cases_tail(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, mask_prepred_mapping_func, fused, window_batch,
+                                        do_calc_vcdr_error, gt_map)
         if not fused and not do_calc_vcdr_error:
             return _T2.test_all_cases(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, mask_prepred_mapping_func)
         np = _T2.np
@@ -204,6 +269,30 @@ def test_all_cases(net, batches, task_name, num_classes, orig_input_size, patch_
             m = calc_batch_metric(preds_soft, gt, num_classes, do_calc_vcdr_error=do_calc_vcdr_error)
             total += m.sum(axis=0); count += len(m)
         return total / np.maximum(count, 1), count
+
+
+def _sum_tables(rows, ncols, count):
+    """the ONE read of the per-batch device tables `rows` and their sum in the order the default path adds its per-batch tables; count: the default's 0 (or zeros)"""
+    np = _T2.np
+    total = np.zeros(ncols)
+    if rows:
+        sizes = [len(r) for r in rows]
+        table = torch.cat(rows).cpu().numpy().astype(np.float64)                                # the one read
+        for m in np.split(table, np.cumsum(sizes)[:-1]):
+            total += m.sum(axis=0); count += len(m)
+    return total / np.maximum(count, 1), count
+
+
+def _test_all_cases_tail(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, mask_prepred_mapping_func, fused, window_batch,
+                         do_calc_vcdr_error, gt_map):
+    rows = []
+    for image_batch, mask_batch in batches:
+        gt = mask_prepred_mapping_func(mask_batch) if mask_prepred_mapping_func else mask_batch
+        _, preds_soft = test_single_batch(net, image_batch, orig_input_size, patch_size, stride, task_name, num_classes, fused=fused, window_batch=window_batch)
+        with torch.no_grad():
+            rows.append(_nhot_metric_rows(preds_soft, gt, num_classes, do_calc_vcdr_error, gt_map))
+    np = _T2.np
+    return _sum_tables(rows, num_classes, np.zeros(num_classes)) if do_calc_vcdr_error else _sum_tables(rows, num_classes - 1, 0)
 
 
 def _test_all_cases_index(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, fused, window_batch):
@@ -223,16 +312,32 @@ def _test_all_cases_index(net, batches, task_name, num_classes, orig_input_size,
     return total / max(count, 1), count
 
 
-def export_masks(preds_soft, unscaled_sizes, inv_map, remove_frag=False, bg_value=255):
+_INV_MAP_VALUES = {fundus_inv_map_mask: (255, 128, 0), polyp_inv_map_mask: (0, 255)}      # the value tables of the inverse maps the tail launch can stand in for
+
+
+def export_masks(preds_soft, unscaled_sizes, inv_map, remove_frag=False, bg_value=255, fused=False, values=None):
     """The arithmetic of the reference's save loop (test_util2d.py:93-106, and test2d.py's --removefrag) without the files: per image i, preds_soft[i] [C, H, W] is
     resampled to unscaled_sizes[i] = (H0, W0) (interp_linear), hardened (harden_segmap2d), mapped to pixel values by inv_map (fundus_inv_map_mask /
     polyp_inv_map_mask of dataloaders.datasets2d, or functools.partial(onehot_inv_map, colormap=...) for a one-hot task: test2d.py:640-649) and, with remove_frag,
     cleaned by remove_fragmentary_segs(., bg_value).  Returns the list of uint8 [H0, W0] device tensors ([H0, W0, 3] from onehot_inv_map; fragment removal is
-    defined on single-channel label images and refuses those); writing them in an image format is the caller's."""
+    defined on single-channel label images and refuses those); writing them in an image format is the caller's.
+    fused: the label images come from the tail launch (SF.nhot_case_tail with size = unscaled_sizes[i]), one launch per run of equal sizes -- no resampled and no
+    hardened map; the value table is `values` (C ints 0..255; inv_map may then be None) or that of inv_map when it IS fundus_inv_map_mask or polyp_inv_map_mask.
+    Any other inv_map (a partial of onehot_inv_map) keeps the default path."""
     if len(unscaled_sizes) != len(preds_soft):
         raise ValueError('export_masks: %d sizes for %d predictions' % (len(unscaled_sizes), len(preds_soft)))
+    if values is not None and not fused:
+        raise ValueError('export_masks: values= is the table of the fused form (fused=True)')
+    table = values if values is not None else (_INV_MAP_VALUES.get(inv_map) if fused else None)
     out = []
     with torch.no_grad():
+        if fused and table is not None:
+            keys = [(tuple(soft.shape), tuple(int(v) for v in size)) for soft, size in zip(preds_soft, unscaled_sizes)]
+            for i0, i1 in _equal_runs(keys):
+                soft = _batched(preds_soft, i0, i1).float()
+                labels = SF.nhot_case_tail(soft, size=keys[i0][1], values=table)[2]
+                out.extend((remove_fragmentary_segs(labels, bg_value) if remove_frag else labels).unbind(0))
+            return out
         for soft, size in zip(preds_soft, unscaled_sizes):
             H0, W0 = (int(v) for v in size)
             soft = soft.unsqueeze(0).contiguous()
@@ -273,6 +378,59 @@ class GraphedSlidingWindow(GraphedEvaluation):
         self._check(image_batch)
         self._replay(image_batch)
         return self.preds_hard, self.preds_soft
+
+
+
+class GraphedBatchEvaluation(GraphedSlidingWindow):
+    """GraphedSlidingWindow with the n-hot tasks' evaluation tail in the capture: gather, the forward(s), merge and ONE SF.nhot_case_tail launch are one graph.
+
+    mask_size (H, W): the ground truth's size (default: the image's); gt_map: the form of the mask the object takes -- 'nhot' (float32 [B, num_classes, H, W], what
+    fundus_map_mask / polyp_map_mask return) or the raw uint8 [B, 3, H, W] mask of 'fundus' / 'fundus_exclusive' / 'polyp', mapped inside the launch; values: the
+    pixel values of the classes for the label images (e.g. (255, 128, 0) for fundus), None for none; with_extents: the row extents vcdr_from_extents reads.
+    __call__(image_batch, mask) copies both into static buffers, replays and returns (preds_hard, preds_soft, counts, ext, labels): counts int32
+    [B, num_classes - 1, 3], ext int32 [B, 2, 2, 2] or None, labels uint8 [B, H, W] or None -- STATIC tensors that the next call overwrites, nothing is read from the
+    device.  A mask of another shape or dtype raises ValueError; the other guards are GraphedSlidingWindow's."""
+
+    def __init__(self, net, image_shape, orig_input_size, patch_size, stride, num_classes, fold_bn=True, window_batch=None, warmup=2, precision='fp32',
+                 mask_size=None, gt_map='nhot', values=None, with_extents=False):
+        from .segx import SegxLib
+        if gt_map not in SegxLib.NHOT_GT_MAPS:
+            raise ValueError('GraphedBatchEvaluation: gt_map %r is not one of %s' % (gt_map, sorted(SegxLib.NHOT_GT_MAPS)))
+        self.mask_size = None if mask_size is None else tuple(int(v) for v in mask_size)
+        self.gt_map, self.values, self.with_extents = gt_map, (None if values is None else tuple(values)), bool(with_extents)
+        super().__init__(net, image_shape, orig_input_size, patch_size, stride, num_classes, fold_bn, window_batch, warmup, precision)
+
+    def _build(self, device, *plan_args):
+        super()._build(device, *plan_args)
+        B, C = self.plan.shape[0], self.num_classes
+        H, W = self.mask_size = self.mask_size or self.plan.shape[2:]
+        self.mask = torch.zeros((B, C, H, W), dtype=torch.float32, device=device) if self.gt_map == 'nhot' else torch.zeros((B, 3, H, W), dtype=torch.uint8, device=device)
+        self.counts = torch.zeros(B, C - 1, 3, dtype=torch.int32, device=device)
+        self.ext = torch.zeros(B, 2, 2, 2, dtype=torch.int32, device=device) if self.with_extents else None
+        self.labels = None
+        if self.values is not None:
+            SF._value_table('GraphedBatchEvaluation', self.values, C, device)                   # the table's one host copy happens here, not inside the capture
+            self.labels = torch.zeros(B, H, W, dtype=torch.uint8, device=device)
+
+    def _sequence(self):
+        hard, soft = self.plan.run(self.net, self.image)
+        SF.nhot_case_tail(soft, self.mask, gt_map=self.gt_map, values=self.values, counts=self.counts, ext=self.ext, labels=self.labels)
+        return hard, soft
+
+    def __call__(self, image_batch, mask):
+        self._check(image_batch)
+        if not isinstance(mask, torch.Tensor) or tuple(mask.shape) != tuple(self.mask.shape) or mask.dtype != self.mask.dtype:
+            raise ValueError('GraphedBatchEvaluation: captured for %s masks %r (gt_map=%r), got %s %r' %
+                             (self.mask.dtype, tuple(self.mask.shape), self.gt_map, getattr(mask, 'dtype', None), tuple(getattr(mask, 'shape', ()))))
+        if mask is not self.mask:
+            self.mask.copy_(mask, non_blocking=True)
+        self._replay(image_batch)
+        return self.preds_hard, self.preds_soft, self.counts, self.ext, self.labels
+
+    def close(self):
+        """GraphedEvaluation.close(), and drop the tail's static buffers as well"""
+        super().close()
+        self.mask = self.counts = self.ext = self.labels = None
 
 
 # reference function names; not pytest tests

@@ -647,6 +647,12 @@ class SegxLib:
         ref = next(t for t in (soft, counts, labels, rgb, gt, colormap) if t is not None)     # a NULL operand is the library's to refuse
         self._call('segx_onehot_case_tail', ref, soft, gt, colormap, counts, labels, rgb, B, C, S, float(T))
 
+    NHOT_GT_MAPS = {'nhot': 0, 'fundus': 1, 'fundus_exclusive': 2, 'polyp': 3}        # gt_map of segx_nhot_case_tail
+
+    def nhot_case_tail(self, soft, gt, gt_map, gt_channels, values, counts, ext, labels, hard, B, C, h, w, H, W, T=0.5):
+        ref = next(t for t in (soft, counts, ext, labels, hard, gt, values) if t is not None)     # a NULL operand is the library's to refuse
+        self._call('segx_nhot_case_tail', ref, soft, gt, int(gt_map), int(gt_channels), values, counts, ext, labels, hard, B, C, h, w, H, W, float(T))
+
     # ---- components, fragment removal, row extents, n-hot -> values (components.hip) --------------------
     CCL_TILE, CCL_MAX_PLANE = (32, 64), 1 << 30          # SEGX_CCL_TILE_H / _W, SEGX_CCL_MAX_PLANE of include/segx.h
 
@@ -862,7 +868,7 @@ _SIGS = {
     'segx_x6_presplit_elems': 'iiii', 'segx_x6_presplit': 'piilliillpp',
     'segx_tune': 'ii', 'segx_tune_get': 'i', 'segx_x3_launches': '', 'segx_gemm_route': 'pppp', 'segx_set_rng_base': 'p', 'segx_rng_advance': 'pup', 'segx_resized_crop3d': 'pplpp', 'segx_stem_compose_fwd': 'ppppiiiiip', 'segx_stem_compose_bwd': 'pppppppiiiiip', 'segx_bridge_input': 'ppiiiiiip', 'segx_stem_s2d_input': 'ppiiiiiip', 'segx_conv2d_stem_fwd': 'pppiiiiiiiiiiip', 'segx_conv2d_stem_im2col': 'ppiiiiiiiiiiip', 'segx_dropout': 'pplfuup', 'segx_avgpool2_fwd': 'ppliip', 'segx_avgpool2_bwd': 'ppliip', 'segx_transpose': 'ppliip', 'segx_interp_linear_fwd_axis': 'pppliilfp', 'segx_window_accum': 'pppiipp', 'segx_harden_segmap': 'ppppiilifp', 'segx_window_gather': 'ppppiiipp', 'segx_window_merge': 'pppppiiipifp', 'segx_dice_ws_floats': 'll', 'segx_dice_sums': 'pppllp',
     'segx_surface_border': 'ppliiiip', 'segx_edt_sq': 'ppliiip', 'segx_surface_hist': 'pppliiiip', 'segx_brats_case_tail': 'ppppplp',
-    'segx_index_onehot': 'piplilp', 'segx_onehot_colormap': 'ppplilp', 'segx_onehot_case_tail': 'ppppppiilfp',
+    'segx_index_onehot': 'piplilp', 'segx_onehot_colormap': 'ppplilp', 'segx_onehot_case_tail': 'ppppppiilfp', 'segx_nhot_case_tail': 'ppiipppppiiiiiifp',
     'segx_ccl2d': 'pippliip', 'segx_frag_keep2': 'ppliip', 'segx_frag_apply': 'ppppliiip', 'segx_row_extent': 'ppliifp', 'segx_nhot_to_values': 'ppplilp',
     'segx_conv3d_fwd': 'pppiipipp', 'segx_conv3d_fwd_packed': 'pppiipipp', 'segx_conv3d_fwd_packed_bs': 'pppiipipllp', 'segx_conv3d_bwd_weight_packed_bs': 'pppiipipllp', 'segx_conv3d_pack_weights': 'ppiiiip', 'segx_conv3d_splitk': 'iipi', 'segx_conv3d_route': 'iipiiiip', 'segx_conv3d_fwd_terms': 'iipiii', 'segx_conv3d_flip_weights': 'ppiiip', 'segx_conv3d_bwd_weight': 'pppiipipp', 'segx_conv3d_bwd_weight_packed': 'pppiipipp', 'segx_conv3d_unpack_wgrad': 'ppiiip',
     'segx_conv3d_halo_ok': 'iip', 'segx_conv3d_halo_wq_floats': 'ii', 'segx_conv3d_halo_pack': 'ppiiip', 'segx_conv3d_halo_fwd': 'pppiipllip', 'segx_conv3d_halo_bias_act_fwd': 'ppppiiplliip', 'segx_conv3d_fwd_bias_act': 'ppppiipipillip', 'segx_bias_map_relu': 'ppilp', 'segx_conv3d_halo_wgrad_ok': 'iip', 'segx_conv3d_halo_wgrad_ws_floats': 'iip', 'segx_conv3d_halo_wgrad': 'ppppiipllp',
