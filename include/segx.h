@@ -338,6 +338,26 @@ int segx_mbconv_mid_bwd(const float* dY, const float* dpool, const float* D, con
                         const float* var1, const float* w0, const float* b0, const float* w1, const float* b1, const float* Wdw,
                         float* dE, float* dw0, float* db0, float* dw1, float* db1, float* dWdw, float inv_S, float eps0, float eps1,
                         int B, int C, int H, int W, int k, void* stream);
+/* The ENTRY of a stride-2 MBConv block in training mode (efficientnet/model.py:96-100; backbone.hip: bn_dw_s2_{fwd,bwd}_team_kernel): BatchNorm0 + swish and the k x k stride-2
+ * depthwise convolution in ONE team launch per direction (the team form of segx_bn_act_fwd2 / segx_bn_act_bwd2 with the convolution between the exchange and the stores).
+ * swish(BatchNorm0(E)) and the gradient w.r.t. it are never written.
+ * segx_bn_dw_s2_ok: 1 where the pair serves the shape, else 0 -- the callers then keep segx_bn_act_fwd2 / segx_dwconv2d_fwd and their backwards.  Served: stride 2, k in {3, 5},
+ *      H even, W a power of two in 16..512 (so W % 4 == 0 and a team member's chunk is a run of whole row pairs), begin pads pad_t == pad_l in {(k - 2) / 2, k / 2} -- the
+ *      pads under which OH = H / 2 and OW = W / 2 --, B * C <= 65535, and planes for which segx_bn_act_fwd2 / segx_bn_act_bwd2 themselves take the team form with 4, 16 or
+ *      32 float4 per lane under the current SEGX_KNOB_BN_PATH (by default: planes of >= 16384 floats; the pair chunks the planes as those launches do).
+ * segx_bn_dw_s2_ws_floats: floats of the exchange scratch `ws` of one call (backward != 0: of segx_bn_dw_s2_bwd); segx_bn_dw_s2_rows: rows of the backward's `part`.  Both depend
+ *      on SEGX_KNOB_BN_PATH; the calls re-derive them and refuse a buffer that is too small.
+ * fwd: E [B,C,H,W] -> D [B,C,H/2,W/2]; mean / var [C] (biased variance) and the running statistics (unbiased; NULL pair: no update) are bit-identical to segx_bn_act_fwd2's.
+ * bwd: dD = gradient w.r.t. D.  Writes dE, the BatchNorm parameter gradients dw0 / db0 [C] and part [rows][C][k*k]: the filter gradient is segx_colsum(part) over its rows.
+ * E, D, dD, dE 16-byte aligned. */
+int segx_bn_dw_s2_ok(int B, int C, int H, int W, int k, int stride, int pad_t, int pad_l);
+int64_t segx_bn_dw_s2_ws_floats(int B, int C, int H, int W, int backward);
+int64_t segx_bn_dw_s2_rows(int B, int H, int W);
+int segx_bn_dw_s2_fwd(const float* E, const float* w0, const float* b0, float* run_mean, float* run_var, const float* Wdw, float* D, float* mean, float* var,
+                      float* ws, float momentum, float eps, int B, int C, int H, int W, int k, int pad_t, int pad_l, int64_t ws_floats, void* stream);
+int segx_bn_dw_s2_bwd(const float* dD, const float* E, const float* mean, const float* var, const float* w0, const float* b0, const float* Wdw,
+                      float* dE, float* dw0, float* db0, float* part, float* ws, float eps, int B, int C, int H, int W, int k, int pad_t, int pad_l,
+                      int64_t part_rows, int64_t ws_floats, void* stream);
 /* r04: the weight gradient dW [C][k*k] in ONE launch where a channel's B planes are one workgroup's work (B <= 8, <= 8192 outputs per plane, the float4
  * layout): returns 1 when done, 0 when the shape needs the two-stage form above (nothing launched), < 0 on error */
 int segx_dwconv2d_bwd_weight_direct(const float* dY, const float* X, float* dW, int B, int C, int H, int Wd, int OH, int OW, int k,

@@ -747,6 +747,316 @@ static int bn_team_launch_bwd(const BnBwdArgs& g, const BnTeam& t, dim3 grid, hi
 #undef SEGX_BN_TB
     return check_launch("segx_bn_act_bwd2/team");
 }
+// =================================================================================================
+// r08: the ENTRY of a stride-2 MBConv block in training mode (efficientnet/model.py:96-100): e --BatchNorm0 + swish--> e' --k x k stride-2 depthwise convolution--> d
+// as ONE team launch per direction.  The stride-2 blocks expand at the input resolution, so e is the largest tensor of its stage; e' and the gradient w.r.t. e' were
+// written once and read once (twice) by the neighbouring launch.  Here neither exists:
+//   forward : read e, write d                       (1 + 1/4 passes over e;  bn_act_fwd_team_kernel -> dwconv_rows4_kernel<K, 2, P>: 3 + 1/4)
+//   backward: read e and g_d, write g_e             (2 + 1/4;  dwconv_bwd4s2 -> dwconv_wgrad4 -> bn_act_bwd_team_kernel: 5 + 1/2)
+// Both are bn_act_{fwd,bwd}_team_kernel (chunking, lane <-> element mapping, statistics, exchange: unchanged, so mean / var / running statistics keep their bits) with
+// the convolution between the exchange and the stores.  Geometry: H even, W a power of two in 16..512, OH = H / 2, OW = W / 2, so
+//   * a lane's float4 k sits at row tr + k * rpk, column tc of its chunk (rpk = 256 / (W / 4) rows per k index, (tr, tc) = thread / (W / 4), thread % (W / 4)): rows and
+//     columns step by compile-time multiples, every element of a thread has the row parity of tr;
+//   * a chunk (and a forward band of S2_BAND k indices) is an even number of whole rows and yields whole output rows.
+// LDS images use the guarded layout of mbconv_mid.hip: one zero float4 in front of every row, so the columns left of a row's first and right of its last element read zeros.
+// =================================================================================================
+constexpr int S2_BAND = 4;                 // float4 per lane of one forward band: 1024 float4 of e' = 4096 / W rows -> 256 float4 of d, one per thread
+constexpr int S2_IMG = 1440;               // float4 per forward image: (4096 / W + K - 2) rows of (W / 4 + 1); largest at W = 512, K = 5: 11 * 129 + 1
+constexpr int S2_GIMG = 1600;              // float4 of the backward's image of g_d: (KP * 512 / W + (K + 1) / 2) rows of (W / 8 + 1); largest at KP = 16, W = 16: 515 * 3 + 1
+struct BnDwS2Args {
+    const float* E; const float* w; const float* b; const float* Wdw; float* mean; float* var;     // mean / var: written forward, read backward
+    float* D; float* run_mean; float* run_var; float momentum;                                     // forward
+    const float* dD; float* dE; float* dw; float* db; float* part;                                  // backward; part [team members][C][K * K]
+    float eps; int C, H, W4, pt;                                                                   // W4 = W / 4; pt = zero rows above the plane (the template's PL: columns left of it)
+};
+// Forward.  After the exchange the chunk goes through LDS in bands of S2_BAND k indices (two images in turn: one barrier per band): every thread writes swish(sc * e + sh)
+// of the band's registers and of the rows the windows reach above and below it -- from the neighbouring k index (the same registers), or, at the ends of the chunk, from
+// K - 2 rows of e read again (requested before the exchange; rows outside the plane are zeros) -- then convolves at its own output float4 with dwconv_rows4_kernel's tap
+// order (ky outer, kx inner, one chain of scalar FMAs per output starting from zero).
+template <int KP, int K, int PL>
+__global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(KP <= 16 ? 3 : 2) void bn_dw_s2_fwd_team_kernel(BnDwS2Args g, BnTeam t) {
+    static_assert(KP % S2_BAND == 0 && PL <= 4 && 4 + 3 * 2 + K - 1 - PL < 16, "window does not fit the four float4 read per row");
+    constexpr int NB = KP / S2_BAND;
+    __shared__ float red[4];
+    __shared__ f32x4 img[NB > 1 ? 2 : 1][S2_IMG];
+    const int TS = t.B * t.cpp, tl = threadIdx.x;
+    const int c = blockIdx.x / TS, r = blockIdx.x - c * TS, b = r / t.cpp, ch = r - b * t.cpp;
+    const int C = g.C, W4 = g.W4, S4 = g.H * W4, j0 = ch * 256 * KP;
+    const int64_t S = 4 * (int64_t)S4, plane = ((int64_t)b * C + c) * S;
+    auto offk = [&](int k) { const int j = j0 + tl + 256 * k; return 16u * (unsigned)(j < S4 ? j : S4 - 1); };
+    f32x4 v[KP];
+    const ws_gptr xb = ws_uniform_base(g.E + plane);
+#pragma unroll
+    for (int k = 0; k < KP; ++k) v[k] = ws_load<f32x4>(xb, offk(k));
+    // the K - 2 rows above / below the chunk: thread (tr, tc) takes column tc of halo row tr (+ rpk); rows 0 .. pt - 1 lie above, the others below
+    const int rpk = 256 / W4, tr = tl / W4, tc = tl - tr * W4, HT = g.pt, LS = W4 + 1, IR = S2_BAND * rpk + K - 2;
+    f32x4 hv[2]; bool hok[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const int hr = tr + q * rpk;
+        const int jh = (hr < HT ? j0 - (HT - hr) * W4 : j0 + 256 * KP + (hr - HT) * W4) + tc;
+        hok[q] = hr < K - 2 && jh >= 0 && jh < S4;
+        hv[q] = ws_load<f32x4>(xb, 16u * (unsigned)(hok[q] ? jh : 0));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    for (int i = tl; i <= IR; i += 256) {                       // guards (visible after the barriers of the first block_sum)
+        img[0][i * LS] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (NB > 1) img[NB > 1 ? 1 : 0][i * LS] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    float w[K * K];
+#pragma unroll
+    for (int i = 0; i < K * K; ++i) w[i] = g.Wdw[(int64_t)c * K * K + i];
+    // statistics, exchange, running statistics: bn_act_fwd_team_kernel's expressions
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+        if (!(j0 + tl + 256 * k < S4)) v[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+        s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
+    }
+    const int left4 = S4 - j0;
+    const float n = 4.0f * (float)(left4 < 256 * KP ? left4 : 256 * KP);
+    const float m = block_sum<4>(s, red) / n;
+    float q = 0.f;
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+        const float d0 = v[k].x - m, d1 = v[k].y - m, d2 = v[k].z - m, d3 = v[k].w - m;
+        q += (j0 + tl + 256 * k < S4) ? (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3) : 0.f;
+    }
+    q = block_sum<4>(q, red);
+    const TeamBufs tb{t.slots + (int64_t)c * TS * TEAM_SLOT, t.mbox + (int64_t)c * TS * TEAM_MBOX, t.tag_lo, t.tag_hi, t.err, t.spin};
+    if (tl == 0) { float* pp = tb.slots + r * TEAM_SLOT; team_store(pp, n); team_store(pp + 1, m); team_store(pp + 2, q); }
+    float res[3];
+    team_exchange(tb, r, TS, res, [](const float* slots, int members, float (&o)[3]) { const BnPart f = bn_fold_team(slots, members); o[0] = f.n; o[1] = f.mean; o[2] = f.m2; });
+    BnPart st; st.n = res[0]; st.mean = res[1]; st.m2 = res[2];
+    const float mean = st.mean, var = st.n != st.n ? st.n : st.n > 0.f ? fmaxf(st.m2 / st.n, 0.f) : 0.f;
+    if (r == 0 && tl == 0) {
+        g.mean[c] = mean; g.var[c] = var;
+        if (g.run_mean && st.n == st.n) {
+            g.run_mean[c] = (1.0f - g.momentum) * g.run_mean[c] + g.momentum * mean;
+            g.run_var[c] = (1.0f - g.momentum) * g.run_var[c] + g.momentum * (st.m2 / fmaxf(st.n - 1.0f, 1.0f));
+        }
+    }
+    const float sc = rsqrtf(var + g.eps) * g.w[c], sh = g.b[c] - mean * sc;
+    auto act4 = [&](const f32x4& x, bool ok) {
+        f32x4 o;
+        o.x = act_fwd_c<ACT_SWISH>(x.x * sc + sh, ACT_SWISH); o.y = act_fwd_c<ACT_SWISH>(x.y * sc + sh, ACT_SWISH);
+        o.z = act_fwd_c<ACT_SWISH>(x.z * sc + sh, ACT_SWISH); o.w = act_fwd_c<ACT_SWISH>(x.w * sc + sh, ACT_SWISH);
+        return ok ? o : f32x4{0.f, 0.f, 0.f, 0.f};
+    };
+    const int OW4 = W4 >> 1, orow = tl / OW4, oc = tl - orow * OW4, D4 = S4 >> 2;
+    const int rpos = (2 * orow) * LS + 2 * oc + 1;               // image position of the float4 at (row 2 orow, column 8 oc): the window's rows start there
+    const ws_gptr_w db_ = ws_uniform_base_w(g.D + ((int64_t)b * C + c) * (S >> 2));
+#pragma unroll
+    for (int bd = 0; bd < NB; ++bd) {
+        constexpr int KB = S2_BAND;
+        const int k0 = bd * KB;
+        f32x4* im = img[bd & (NB > 1 ? 1 : 0)];
+        // image row of this thread's float4 kk: tr + (kk - k0) * rpk + HT; the band's own are all inside, of the neighbours' the last HT / first K - 2 - HT rows
+#pragma unroll
+        for (int kk = k0 - 1; kk <= k0 + KB; ++kk) {
+            if (kk < 0 || kk >= KP) continue;                    // compile-time: the chunk's ends take the rows read again (below)
+            const int ir = tr + (kk - k0) * rpk + HT;
+            if (kk < k0 ? ir >= 0 : kk < k0 + KB || ir < IR) im[ir * LS + 1 + tc] = act4(v[kk], j0 + tl + 256 * kk < S4);
+        }
+        if (bd == 0 || bd == NB - 1) {
+#pragma unroll
+            for (int q2 = 0; q2 < 2; ++q2) {
+                const int hr = tr + q2 * rpk;
+                if (hr < K - 2 && (hr < HT ? bd == 0 : bd == NB - 1)) im[(hr < HT ? hr : KB * rpk + hr) * LS + 1 + tc] = act4(hv[q2], hok[q2]);
+            }
+        }
+        __syncthreads();
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ky = 0; ky < K; ++ky) {
+            const f32x4* p = im + rpos + ky * LS;
+            const f32x4 e0 = p[-1], e1 = p[0], e2 = p[1], e3 = p[2];
+            const float e[16] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w, e2.x, e2.y, e2.z, e2.w, e3.x, e3.y, e3.z, e3.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int kx = 0; kx < K; ++kx) acc[j] += w[ky * K + kx] * e[4 + j * 2 + kx - PL];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) SEGX_PIN(acc[j]);        // as dwconv_rows4_kernel: the chain stays a chain of scalar FMAs
+        }
+        const int dj = ((j0 + 256 * k0) >> 2) + tl;
+        if (dj < D4) ws_store<f32x4>(db_, 16u * (unsigned)dj, f32x4{acc[0], acc[1], acc[2], acc[3]});
+        __builtin_amdgcn_sched_barrier(0);                       // one band at a time
+    }
+}
+// Backward.  Load stage: the chunk of e into registers, the rows of g_d its windows reach (R / 2 + (K + 1) / 2 rows of W / 2 for a chunk of R rows) into LDS.  Element
+// (iy, ix) receives g_d[oy][ox] through tap (ky, kx) = (iy + pt - 2 oy, ix + pl - 2 ox): ky has the parity py of iy + pt -- one value per thread (see above), so a thread
+// keeps the (K + 1) / 2 filter rows of ITS parity (wsel) and as many rows of filter-gradient sums (dwa), and walks oy = (iy + pt) / 2 - a; kx has the parity of
+// ix + pl -- compile-time per float4 component.  A row of the walk reads g_d[2 tc - 2 .. 2 tc + 3] as three 8-byte LDS reads.  e' = swish(sc * e + sh) as the forward formed it.
+// The gradient w.r.t. e' is accumulated in dwconv_bwd4s2_kernel's order and the activation's slope taken as bn_act_bwd_team_kernel takes it, so xhat and du are the
+// three launches' to the last bit; the two BatchNorm sums are then added in that kernel's order too (same chunking, same lanes, fp32), which makes dw0, db0 and g_e its
+// bits as well -- no other order of these long sums can be relied on to stay within twice ITS rounding draw.  The K x K filter-gradient sums (another partition than
+// dwconv_wgrad4_kernel's either way) are added in double across lanes, waves and the workgroup and leave as one row of partials per member (segx_colsum adds them in
+// member order).
+template <int KP, int K, int PL>
+__global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(2) void bn_dw_s2_bwd_team_kernel(BnDwS2Args g, BnTeam t) {
+    constexpr int A = (K + 1) / 2, KK = K * K, NGV = KP / 4 + 1;
+    __shared__ float red[4];
+    __shared__ double wred[4][KK];
+    __shared__ f32x4 gim[S2_GIMG];
+    const int TS = t.B * t.cpp, tl = threadIdx.x;
+    const int c = blockIdx.x / TS, r = blockIdx.x - c * TS, b = r / t.cpp, ch = r - b * t.cpp;
+    const int C = g.C, W4 = g.W4, S4 = g.H * W4, j0 = ch * 256 * KP, pt = g.pt;
+    const int64_t S = 4 * (int64_t)S4, plane = ((int64_t)b * C + c) * S;
+    auto offk = [&](int k) { const int j = j0 + tl + 256 * k; return 16u * (unsigned)(j < S4 ? j : S4 - 1); };
+    f32x4 h[KP], d[KP];                              // e as loaded -> xhat; du
+    const ws_gptr xb = ws_uniform_base(g.E + plane);
+#pragma unroll
+    for (int k = 0; k < KP; ++k) h[k] = ws_load<f32x4>(xb, offk(k));
+    // g_d: image row gi holds output row oy_lo + gi (zeros outside the plane); thread (gr, gc) takes column gc of rows gr + i * gpr
+    const int rpk = 256 / W4, tr = tl / W4, tc = tl - tr * W4, OW4 = W4 >> 1, OH = g.H >> 1, GS = OW4 + 1, NG = KP * (rpk >> 1) + A;
+    const int gpr = 256 / OW4, gr = tl / OW4, gc = tl - gr * OW4, oy_lo = ((j0 / W4) >> 1) + (pt >> 1) - (A - 1);
+    {
+        const ws_gptr gb = ws_uniform_base(g.dD + ((int64_t)b * C + c) * (S >> 2));
+        f32x4 gv[NGV];
+#pragma unroll
+        for (int i = 0; i < NGV; ++i) {
+            const int oy = oy_lo + gr + i * gpr;
+            gv[i] = ws_load<f32x4>(gb, 16u * (unsigned)(gr + i * gpr < NG && oy >= 0 && oy < OH ? oy * OW4 + gc : 0));
+        }
+        for (int i = tl; i <= NG; i += 256) gim[i * GS] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < NGV; ++i) {
+            const int gi = gr + i * gpr, oy = oy_lo + gi;
+            if (gi < NG) gim[gi * GS + 1 + gc] = oy >= 0 && oy < OH ? gv[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    }
+    __syncthreads();
+    __builtin_amdgcn_sched_barrier(0);
+    const float rstd = rsqrtf(g.var[c] + g.eps), m = g.mean[c], wc = g.w[c], bc_ = g.b[c], sc = rstd * wc, sh = bc_ - m * sc;       // sc, sh: the forward's bits
+    const int py = (tr + pt) & 1;
+    float wsel[A][K], dwa[A][K];
+#pragma unroll
+    for (int a = 0; a < A; ++a)
+#pragma unroll
+        for (int kx = 0; kx < K; ++kx) {
+            const float we = g.Wdw[(int64_t)c * KK + (2 * a) * K + kx], wo = 2 * a + 1 < K ? g.Wdw[(int64_t)c * KK + (2 * a + 1) * K + kx] : 0.f;
+            wsel[a][kx] = py ? wo : we; dwa[a][kx] = 0.f;
+        }
+    // float (row gi, column ox) of the image sits at gi * 4 GS + 4 + ox; this thread's reads start at ox = 2 tc - 2
+    const float* gf = reinterpret_cast<const float*>(gim) + (((tr + pt) >> 1) - (pt >> 1) + A - 1) * (4 * GS) + 2 * tc + 2;
+    float sa = 0.f, sq = 0.f;
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+        const bool ok = j0 + tl + 256 * k < S4;
+        const f32x4 xv = h[k];
+        const float u[4] = {xv.x * sc + sh, xv.y * sc + sh, xv.z * sc + sh, xv.w * sc + sh};
+        float ep[4], de[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ep[i] = ok ? act_fwd_c<ACT_SWISH>(u[i], ACT_SWISH) : 0.f;
+#pragma unroll
+        for (int a = A - 1; a >= 0; --a) {                       // output rows in ascending order, kx ascending: dwconv_bwd4s2_kernel's order of the chain -- and its bits
+            const float* gp = gf + (k * (rpk >> 1) - a) * (4 * GS);
+            const float2 g0 = *reinterpret_cast<const float2*>(gp), g1 = *reinterpret_cast<const float2*>(gp + 2), g2 = *reinterpret_cast<const float2*>(gp + 4);
+            const float G[6] = {g0.x, g0.y, g1.x, g1.y, g2.x, g2.y};
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int kx = 0; kx < K; ++kx) {
+                    if ((i + PL - kx) & 1) continue;             // compile-time: tap kx reaches component i from ox = (4 tc + i + PL - kx) / 2 = 2 tc - 2 + nn
+                    const int nn = (i + PL - kx + 4) / 2;
+                    de[i] = __builtin_fmaf(wsel[a][kx], G[nn], de[i]); dwa[a][kx] = __builtin_fmaf(ep[i], G[nn], dwa[a][kx]);
+                    SEGX_PIN(de[i]); SEGX_PIN(dwa[a][kx]);       // scalar FMAs (mbconv_mid.hip: paired into v_pk_fma_f32 the chains spilled)
+                }
+            __builtin_amdgcn_sched_barrier(0);                   // one row of the walk at a time
+        }
+        // e' above is the forward's (u = sc * e + sh: what the convolution saw); the activation's slope is taken at xhat * w + b as bn_act_bwd_team_kernel takes it --
+        // free of the cancellation sc * e + sh suffers where |mean| >> sigma
+        f32x4 hh, dd;
+        hh.x = (xv.x - m) * rstd; hh.y = (xv.y - m) * rstd; hh.z = (xv.z - m) * rstd; hh.w = (xv.w - m) * rstd;
+        dd.x = de[0] * act_grad_c<ACT_SWISH>(hh.x * wc + bc_, ACT_SWISH); dd.y = de[1] * act_grad_c<ACT_SWISH>(hh.y * wc + bc_, ACT_SWISH);
+        dd.z = de[2] * act_grad_c<ACT_SWISH>(hh.z * wc + bc_, ACT_SWISH); dd.w = de[3] * act_grad_c<ACT_SWISH>(hh.w * wc + bc_, ACT_SWISH);
+        if (!ok) { dd = f32x4{0.f, 0.f, 0.f, 0.f}; hh = dd; }
+        h[k] = hh; d[k] = dd;
+        sa += (dd.x + dd.y) + (dd.z + dd.w); sq += (dd.x * hh.x + dd.y * hh.y) + (dd.z * hh.z + dd.w * hh.w);
+    }
+    sa = block_sum<4>(sa, red); sq = block_sum<4>(sq, red);
+    const TeamBufs tb{t.slots + (int64_t)c * TS * TEAM_SLOT, t.mbox + (int64_t)c * TS * TEAM_MBOX, t.tag_lo, t.tag_hi, t.err, t.spin};
+    if (tl == 0) { float* pp = tb.slots + r * TEAM_SLOT; team_store(pp, sa); team_store(pp + 1, sq); }
+    float res[3];
+    // the team's sums as bn_act_bwd_team_kernel forms them: members l, l + 64 per lane, then a symmetric butterfly
+    team_exchange(tb, r, TS, res, [](const float* parts, int members, float (&o)[3]) {
+        const int lane = threadIdx.x & 63;
+        const bool h0 = lane < members, h1 = lane + 64 < members;
+        const float a0 = team_load(parts + TEAM_SLOT * (h0 ? lane : 0)), q0 = team_load(parts + TEAM_SLOT * (h0 ? lane : 0) + 1);
+        const float a1 = team_load(parts + TEAM_SLOT * (h1 ? lane + 64 : 0)), q1 = team_load(parts + TEAM_SLOT * (h1 ? lane + 64 : 0) + 1);
+        float As = (h0 ? a0 : 0.f) + (h1 ? a1 : 0.f), Qs = (h0 ? q0 : 0.f) + (h1 ? q1 : 0.f);
+#pragma unroll
+        for (int o2 = 1; o2 < 64; o2 <<= 1) { As += __shfl_xor(As, o2); Qs += __shfl_xor(Qs, o2); }
+        o[0] = As; o[1] = Qs; o[2] = 0.f;
+    });
+    const float As = res[0], Qs = res[1];
+    if (r == 0 && tl == 0) { g.db[c] = As; g.dw[c] = Qs; }
+    const float inv_n = 1.0f / ((float)t.B * (float)S), k1 = As * inv_n, k2 = Qs * inv_n;
+    const ws_gptr_w ob = ws_uniform_base_w(g.dE + plane);
+    // the store phase recomputes its offsets from an opaque copy of the lane index (bn_act_fwd_team_kernel: shared with the load phase's, KP addresses stay alive -- spilled)
+    int tl2 = tl;
+    SEGX_PIN(tl2);
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+        const int j = j0 + tl2 + 256 * k;
+        if (j < S4) {
+            f32x4 o;
+            o.x = sc * (d[k].x - k1 - h[k].x * k2); o.y = sc * (d[k].y - k1 - h[k].y * k2);
+            o.z = sc * (d[k].z - k1 - h[k].z * k2); o.w = sc * (d[k].w - k1 - h[k].w * k2);
+            ws_store<f32x4>(ob, 16u * (unsigned)j, o);
+        }
+    }
+    // this member's share of the filter gradient: the lanes of row parity p hold the sums of filter rows 2 a + p
+#pragma unroll
+    for (int a = 0; a < A; ++a)
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            if (2 * a + p >= K) continue;
+#pragma unroll
+            for (int kx = 0; kx < K; ++kx) {
+                const double sw = wave_sum_d(py == p ? (double)dwa[a][kx] : 0.0);
+                if ((tl & 63) == 0) wred[tl >> 6][(2 * a + p) * K + kx] = sw;
+            }
+        }
+    __syncthreads();
+    if (tl < KK) g.part[((int64_t)r * C + c) * KK + tl] = (float)((wred[0][tl] + wred[1][tl]) + (wred[2][tl] + wred[3][tl]));
+}
+static inline bool s2_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+// float4 per lane of the pair's team form, 0 = not served.  The pair serves where training BatchNorm itself takes the team form (bn_auto_form: knob 3 included) and chunks
+// the planes as that launch does -- the forward statistics then are its statistics to the last bit.  Instantiated: 4, 16 and (forward) 32 float4 per lane.
+static inline int s2_kp(int B, int64_t S, bool backward) {
+    int kp = 0;
+    if (B < 1 || S < 4 || bn_auto_form(B, S, backward, &kp) != 1) return 0;
+    return kp == 4 || kp == 16 || (kp == 32 && !backward) ? kp : 0;
+}
+static inline bool s2_serves(int B, int C, int H, int W, int k, int stride, int pt, int pl) {
+    if (!(stride == 2 && (k == 3 || k == 5) && B >= 1 && C >= 1 && H >= 2 && (H & 1) == 0 && W >= 16 && W <= 512 && s2_pow2(W))) return false;
+    // the begin pads that give OH = H / 2 (k 3: 0 | 1, k 5: 1 | 2), the same on both axes: what dwconv_bwd4s2_kernel serves -- the backward reproduces ITS chain
+    if (!(pt == pl && pt >= (k - 2) / 2 && pt <= k / 2)) return false;
+    const int64_t S = (int64_t)H * W;
+    if (S > (int64_t)1 << 26 || (int64_t)B * C > 65535) return false;
+    const int kf = s2_kp(B, S, false), kb = s2_kp(B, S, true);
+    if (!kf || !kb || (1024 * kf) % (2 * W) || (1024 * kb) % (2 * W)) return false;                 // a chunk is a run of whole row pairs
+    const int W4 = W / 4, rpk = 256 / W4;
+    return (S2_BAND * rpk + k - 2) * (W4 + 1) + 1 <= S2_IMG && (kb * (rpk / 2) + (k + 1) / 2) * (W4 / 2 + 1) + 1 <= S2_GIMG;
+}
+template <int KP, int K>
+static int s2_launch_fwd(const BnDwS2Args& g, const BnTeam& t, dim3 grid, hipStream_t stream, int pl) {
+#define SEGX_S2F(P) do { if (int rc = team_occupancy_ok((const void*)bn_dw_s2_fwd_team_kernel<KP, K, P>, "segx_bn_dw_s2_fwd")) return rc; \
+                         hipLaunchKernelGGL((bn_dw_s2_fwd_team_kernel<KP, K, P>), grid, dim3(256), 0, stream, g, t); } while (0)
+    if (pl == (K - 2) / 2) SEGX_S2F((K - 2) / 2); else SEGX_S2F(K / 2);
+#undef SEGX_S2F
+    return check_launch("segx_bn_dw_s2_fwd");
+}
+template <int KP, int K>
+static int s2_launch_bwd(const BnDwS2Args& g, const BnTeam& t, dim3 grid, hipStream_t stream, int pl) {
+#define SEGX_S2B(P) do { if (int rc = team_occupancy_ok((const void*)bn_dw_s2_bwd_team_kernel<KP, K, P>, "segx_bn_dw_s2_bwd")) return rc; \
+                         hipLaunchKernelGGL((bn_dw_s2_bwd_team_kernel<KP, K, P>), grid, dim3(256), 0, stream, g, t); } while (0)
+    if (pl == (K - 2) / 2) SEGX_S2B((K - 2) / 2); else SEGX_S2B(K / 2);
+#undef SEGX_S2B
+    return check_launch("segx_bn_dw_s2_bwd");
+}
 // The resident kernels exist per (activation, pooling, skip) combination the backbones use -- swish (+ pooling), none (+ skip), relu -- and once with
 // the run-time values for everything else.
 template <int T, int K, int BM>
@@ -1986,4 +2296,61 @@ extern "C" int segx_plane_dot(const float* A, const float* Bm, float* out, int64
     SEGX_STREAM; SEGX_REQUIRE(A && Bm && out && planes > 0 && S > 0 && planes < 2147483647LL, "segx_plane_dot: bad args");
     hipLaunchKernelGGL(plane_dot_kernel, dim3((unsigned)planes), dim3(256), 0, stream, A, Bm, out, S);
     return check_launch("segx_plane_dot");
+}
+// ---- r08: BatchNorm0 + swish + stride-2 depthwise convolution of an MBConv block's entry, one team launch per direction (bn_dw_s2_{fwd,bwd}_team_kernel) ----
+extern "C" int segx_bn_dw_s2_ok(int B, int C, int H, int W, int k, int stride, int pad_t, int pad_l) { return s2_serves(B, C, H, W, k, stride, pad_t, pad_l) ? 1 : 0; }
+/* floats of the exchange scratch of one call (slots + mailboxes of every team), 0 where the pair does not serve */
+extern "C" int64_t segx_bn_dw_s2_ws_floats(int B, int C, int H, int W, int backward) {
+    const int kp = H > 0 && W > 0 ? s2_kp(B, (int64_t)H * W, backward != 0) : 0;
+    return kp ? (int64_t)C * B * bn_team_chunks((int64_t)H * W, kp) * (TEAM_SLOT + TEAM_MBOX) : 0;
+}
+/* rows of the backward's filter-gradient partials: part [rows][C][k * k] (one per team member) */
+extern "C" int64_t segx_bn_dw_s2_rows(int B, int H, int W) {
+    const int kp = H > 0 && W > 0 ? s2_kp(B, (int64_t)H * W, true) : 0;
+    return kp ? (int64_t)B * bn_team_chunks((int64_t)H * W, kp) : 0;
+}
+static int s2_team(BnTeam& t, float* ws, int64_t ws_floats, int B, int C, int64_t S, int kp, const char* what) {
+    t.B = B; t.cpp = bn_team_chunks(S, kp); t.slots = ws; t.mbox = ws + (int64_t)C * B * t.cpp * TEAM_SLOT;
+    team_fill(t);
+    SEGX_REQUIRE(B * t.cpp <= team_cap() && (int64_t)C * B * t.cpp < 2147483647LL, "%s: team of %d workgroups", what, B * t.cpp);
+    const int64_t need = (int64_t)C * B * t.cpp * (TEAM_SLOT + TEAM_MBOX);
+    SEGX_REQUIRE(ws_floats >= need, "%s: the scratch holds %lld floats, this call needs %lld (segx_bn_dw_s2_ws_floats under the current knob 3)", what, (long long)ws_floats, (long long)need);
+    return 0;
+}
+extern "C" int segx_bn_dw_s2_fwd(const float* E, const float* w0, const float* b0, float* run_mean, float* run_var, const float* Wdw, float* D, float* mean, float* var,
+                                 float* ws, float momentum, float eps, int B, int C, int H, int W, int k, int pad_t, int pad_l, int64_t ws_floats, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(E && w0 && b0 && Wdw && D && mean && var && ws && (!run_mean == !run_var), "segx_bn_dw_s2_fwd: bad args");
+    SEGX_REQUIRE(s2_serves(B, C, H, W, k, 2, pad_t, pad_l), "segx_bn_dw_s2_fwd: shape not served (segx_bn_dw_s2_ok == 0)");
+    SEGX_REQUIRE(((reinterpret_cast<uintptr_t>(E) | reinterpret_cast<uintptr_t>(D)) & 15) == 0, "segx_bn_dw_s2_fwd: tensors must be 16-byte aligned");
+    const int64_t S = (int64_t)H * W;
+    const int kp = s2_kp(B, S, false);
+    BnTeam t;
+    if (int rc = s2_team(t, ws, ws_floats, B, C, S, kp, "segx_bn_dw_s2_fwd")) return rc;
+    BnDwS2Args g; memset(&g, 0, sizeof(g));
+    g.E = E; g.w = w0; g.b = b0; g.Wdw = Wdw; g.mean = mean; g.var = var; g.D = D; g.run_mean = run_mean; g.run_var = run_var; g.momentum = momentum;
+    g.eps = eps; g.C = C; g.H = H; g.W4 = W / 4; g.pt = pad_t;
+    const dim3 tg = team_grid((int64_t)C * B * t.cpp);
+#define SEGX_S2(KP) (k == 3 ? s2_launch_fwd<KP, 3>(g, t, tg, stream, pad_l) : s2_launch_fwd<KP, 5>(g, t, tg, stream, pad_l))
+    return kp == 4 ? SEGX_S2(4) : kp == 16 ? SEGX_S2(16) : SEGX_S2(32);
+#undef SEGX_S2
+}
+extern "C" int segx_bn_dw_s2_bwd(const float* dD, const float* E, const float* mean, const float* var, const float* w0, const float* b0, const float* Wdw,
+                                 float* dE, float* dw0, float* db0, float* part, float* ws, float eps, int B, int C, int H, int W, int k, int pad_t, int pad_l,
+                                 int64_t part_rows, int64_t ws_floats, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(dD && E && mean && var && w0 && b0 && Wdw && dE && dw0 && db0 && part && ws, "segx_bn_dw_s2_bwd: bad args");
+    SEGX_REQUIRE(s2_serves(B, C, H, W, k, 2, pad_t, pad_l), "segx_bn_dw_s2_bwd: shape not served (segx_bn_dw_s2_ok == 0)");
+    SEGX_REQUIRE(((reinterpret_cast<uintptr_t>(E) | reinterpret_cast<uintptr_t>(dD) | reinterpret_cast<uintptr_t>(dE)) & 15) == 0, "segx_bn_dw_s2_bwd: tensors must be 16-byte aligned");
+    const int64_t S = (int64_t)H * W;
+    const int kp = s2_kp(B, S, true);
+    BnTeam t;
+    if (int rc = s2_team(t, ws, ws_floats, B, C, S, kp, "segx_bn_dw_s2_bwd")) return rc;
+    SEGX_REQUIRE(part_rows >= (int64_t)B * t.cpp, "segx_bn_dw_s2_bwd: the filter-gradient partials hold %lld rows, this call writes %d (segx_bn_dw_s2_rows under the current knob 3)",
+                 (long long)part_rows, B * t.cpp);
+    BnDwS2Args g; memset(&g, 0, sizeof(g));
+    g.E = E; g.w = w0; g.b = b0; g.Wdw = Wdw; g.mean = const_cast<float*>(mean); g.var = const_cast<float*>(var); g.dD = dD; g.dE = dE; g.dw = dw0; g.db = db0; g.part = part;
+    g.eps = eps; g.C = C; g.H = H; g.W4 = W / 4; g.pt = pad_t;
+    const dim3 tg = team_grid((int64_t)C * B * t.cpp);
+#define SEGX_S2(KP) (k == 3 ? s2_launch_bwd<KP, 3>(g, t, tg, stream, pad_l) : s2_launch_bwd<KP, 5>(g, t, tg, stream, pad_l))
+    return kp == 4 ? SEGX_S2(4) : SEGX_S2(16);
+#undef SEGX_S2
 }

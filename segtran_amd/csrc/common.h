@@ -206,6 +206,23 @@ template <int NW> __device__ __forceinline__ float block_max(float v, float* red
     return s;
 }
 
+// the same in double: the few long channel sums of the fused backward kernels (mbconv_mid.hip, backbone.hip: bn_dw_s2_bwd_team_kernel)
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+template <int NW> __device__ __forceinline__ double block_sum_d(double v, double* red) {
+    v = wave_sum_d(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) s += red[i];
+    return s;
+}
+
 // ---- activations of the backbone kernels (backbone.hip, mbconv_mid.hip) --------------------------
 enum { ACT_NONE = 0, ACT_SWISH = 1, ACT_RELU = 2, ACT_LEAKY = 3 /* nn.LeakyReLU(0.2): the domain discriminator, networks/discriminator.py:14-21 */ };
 

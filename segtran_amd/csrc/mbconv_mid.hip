@@ -156,23 +156,8 @@ __global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(KP == 1 ? 4 : 2) void 
 }
 
 // The backward channel sums run over B * H * W <= 24 576 products each; added in fp32 their rounding (~ eps * sqrt(sum of squares) per level of the tree) is as large as
-// the error the terms themselves carry.  They are few, so they are added in double: per thread, across the wave, across the workgroup.
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-template <int NW> __device__ __forceinline__ double block_sum_d(double v, double* red) {
-    v = wave_sum_d(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < NW; ++i) s += red[i];
-    return s;
-}
-
+// the error the terms themselves carry.  They are few, so they are added in double: per thread, across the wave, across the workgroup
+// (common.h: wave_sum_d, block_sum_d).
 struct MidBwdArgs {
     const float* dY; const float* dpool; const float* D; const float* E;
     const float* mean0; const float* var0; const float* mean1; const float* var1;

@@ -100,6 +100,18 @@ class MBConvBlock(nn.Module):
     fused_middle = True        # _bn0 + swish, the depthwise convolution and _bn1 + swish + pooling as ONE channel-resident launch per direction where the library serves the
                                # shape (stride-1 blocks with planes of 1024 / 4096 floats, batch <= 6: SF.mbconv_mid); False: the three ops everywhere (tools/ab_switch.py)
 
+    fused_entry = True         # _bn0 + swish and a stride-2 depthwise convolution as ONE team launch per direction where the library serves the shape (SF.bn_act_dwconv_s2);
+                               # False: the two ops (tools/ab_switch.py)
+
+    def _takes_fused_entry(self, x):
+        """training, one process, an expansion, a stride-2 depthwise convolution, a served shape (x: the block's input -- the expansion keeps its height and width)"""
+        if not (MBConvBlock.fused_entry and self.training and SF._bn_stats_sync is None and self.expand_ratio != 1):
+            return False
+        dw = self._depthwise_conv
+        if not (self._bn0.training and dw.stride == (2, 2) and dw.kernel_size[0] == dw.kernel_size[1] and x.dim() == 4 and x.dtype == torch.float32):
+            return False
+        return SF.bn_dw_s2_ok((x.shape[0], dw.in_channels, x.shape[2], x.shape[3]), dw.kernel_size[0], 2, dw.static_pad)
+
     def _takes_fused_middle(self, x):
         """training, one process (synchronised BatchNorm exchanges statistics between statistics and apply), an expansion, stride 1 with symmetric padding, a served shape"""
         if not (MBConvBlock.fused_middle and MBConvBlock.gate_in_weights and self.training and SF._bn_stats_sync is None and self.expand_ratio != 1):
@@ -134,7 +146,11 @@ class MBConvBlock(nn.Module):
         x = skip_in = inputs
         skip = self.stride == 1 and self.input_filters == self.output_filters
         fused = self._takes_fused_middle(x)
-        if self.expand_ratio != 1 and not fused:
+        entry = not fused and self._takes_fused_entry(x)
+        if entry:
+            dw = self._depthwise_conv
+            d = SF.bn_act_dwconv_s2(self._expand_conv(x), self._bn0, dw.weight, dw.stride[0], dw.static_pad)
+        elif self.expand_ratio != 1 and not fused:
             # (`inputs` has two consumers when there is a skip connection.  Routing the second through the GEMM op's input alias -- its gradient added
             # inside the expansion's dX GEMM, SF.conv1x1(pass_input=True), what the Inception modules do -- was measured here, r04_d: the residual keeps
             # those dX GEMMs off the wave-specialised tiles, +0.40 ms/step of GEMM time against 0.24 ms of accumulation adds saved.  Not used.)
@@ -148,10 +164,10 @@ class MBConvBlock(nn.Module):
             x = SF.conv1x1_per_sample(y, Wb)
         elif MBConvBlock.gate_in_weights:
             # squeeze-excite gate folded into the projection weights (per-sample weights; the gated tensor is never written)
-            y, Wb = SF.bn_act_gate_weights(self._depthwise_conv(x), self._bn1, SF.ACT_SWISH, *se, self._project_conv.weight)
+            y, Wb = SF.bn_act_gate_weights(d if entry else self._depthwise_conv(x), self._bn1, SF.ACT_SWISH, *se, self._project_conv.weight)
             x = SF.conv1x1_per_sample(y, Wb)
         else:
-            x = self._project_conv(SF.bn_act_se(self._depthwise_conv(x), self._bn1, SF.ACT_SWISH, *se))
+            x = self._project_conv(SF.bn_act_se(d if entry else self._depthwise_conv(x), self._bn1, SF.ACT_SWISH, *se))
         return SF.bn_act(x, self._bn2, SF.ACT_NONE, resid=skip_in if skip else None, drop_connect=rate)
 
 

@@ -422,6 +422,22 @@ class SegxLib:
     def se_bwd2(self, dWb, Wproj, dgate, gate, hpre, p, W1, W2, inv_S, dpool, dW1, db1, dW2, db2, dWproj, ws, B, C, Cs, M):
         self._call('segx_se_bwd2', gate, dWb, Wproj, dgate, gate, hpre, p, W1, W2, inv_S, dpool, dW1, db1, dW2, db2, dWproj, ws, B, C, Cs, M)
 
+    def bn_dw_s2_ok(self, B, C, H, W, k, stride, pt, pl):
+        """does the fused entry of a stride-2 MBConv block (bn_dw_s2_fwd / bn_dw_s2_bwd) serve this expanded tensor, filter size, stride and begin padding?"""
+        return bool(self.c.segx_bn_dw_s2_ok(B, C, H, W, k, stride, pt, pl))
+
+    def bn_dw_s2_ws(self, B, C, H, W, backward):
+        return int(self.c.segx_bn_dw_s2_ws_floats(B, C, H, W, 1 if backward else 0))
+
+    def bn_dw_s2_rows(self, B, H, W):
+        return int(self.c.segx_bn_dw_s2_rows(B, H, W))
+
+    def bn_dw_s2_fwd(self, E, w0, b0, rm, rv, Wdw, D, mean, var, ws, mom, eps, B, C, H, W, k, pt, pl):
+        self._call('segx_bn_dw_s2_fwd', E, E, w0, b0, rm, rv, Wdw, D, mean, var, ws, float(mom), float(eps), B, C, H, W, k, pt, pl, ws.numel())
+
+    def bn_dw_s2_bwd(self, dD, E, mean, var, w0, b0, Wdw, dE, dw0, db0, part, ws, eps, B, C, H, W, k, pt, pl):
+        self._call('segx_bn_dw_s2_bwd', dD, dD, E, mean, var, w0, b0, Wdw, dE, dw0, db0, part, ws, float(eps), B, C, H, W, k, pt, pl, part.shape[0], ws.numel())
+
     def mbconv_mid_ok(self, B, C, H, W, k):
         """does the channel-resident MBConv middle (mbconv_mid_fwd / mbconv_mid_bwd) serve this shape?"""
         return bool(self.c.segx_mbconv_mid_ok(B, C, H, W, k))
@@ -883,6 +899,8 @@ _SIGS = {
     'segx_plane_chunks': 'l', 'segx_bn_pool_chunks': 'ili', 'segx_bn_parts_floats': 'iil', 'segx_bn_stats_local': 'pppiilp',
     'segx_bn_act_fwd2': 'ppippppfpppppfuuiilfillp', 'segx_bn_act_bwd2': 'ppppppppppiilfiippffuullp',
     'segx_team_status': 'i', 'segx_team_cap': '', 'segx_occupy': 'iifpp',
+    'segx_bn_dw_s2_ok': 'iiiiiiii', 'segx_bn_dw_s2_ws_floats': 'iiiii', 'segx_bn_dw_s2_rows': 'iii',
+    'segx_bn_dw_s2_fwd': 'p' * 10 + 'ff' + 'iiiiiii' + 'l' + 'p', 'segx_bn_dw_s2_bwd': 'p' * 12 + 'f' + 'iiiiiii' + 'll' + 'p',
     'segx_mbconv_mid_ok': 'iiiii', 'segx_mbconv_mid_fwd': 'p' * 17 + 'ffff' + 'iiiii' + 'p', 'segx_mbconv_mid_bwd': 'p' * 19 + 'fff' + 'iiiii' + 'p',
     'segx_se_fwd2': 'pifpppppppppiiiip', 'segx_se_ws2_floats': 'iii', 'segx_se_bwd2': 'ppppppppfpppppppiiiip',
     'segx_bn_act_bwd_reduce': 'pppppppppiilfippffuup', 'segx_bn_act_bwd_apply': 'pppppppppiilfifppffuup',
