@@ -358,6 +358,20 @@ int segx_bn_dw_s2_fwd(const float* E, const float* w0, const float* b0, float* r
 int segx_bn_dw_s2_bwd(const float* dD, const float* E, const float* mean, const float* var, const float* w0, const float* b0, const float* Wdw,
                       float* dE, float* dw0, float* db0, float* part, float* ws, float eps, int B, int C, int H, int W, int k, int pad_t, int pad_l,
                       int64_t part_rows, int64_t ws_floats, void* stream);
+/* The stride-1 siblings (backbone.hip: bn_dw_s1_{fwd,bwd}_team_kernel): BatchNorm + swish and a k x k 'same' depthwise convolution in ONE team launch per direction -- the
+ * stride-1 MBConv blocks whose planes segx_mbconv_mid_* does not hold, and the stem's BatchNorm in front of block 0's depthwise convolution.  Argument lists, scratch, `part`
+ * and the bit-identical statistics as for the stride-2 pair; D is [B,C,H,W].
+ * segx_bn_dw_s1_ok: served are stride 1, k in {3, 5}, begin pads pad_t == pad_l == (k - 1) / 2 (the caller checks the end pads: 'same' on both axes), any H, W a power of
+ *      two in 16..512 (a team member's chunk is a run of whole rows), B * C <= 65535, planes for which segx_bn_act_fwd2 / segx_bn_act_bwd2 take the team form with 4, 16 or
+ *      (forward) 32 float4 per lane under the current SEGX_KNOB_BN_PATH, and rows short enough for the backward's image of dD (W == 16 with 16 float4 per lane is not). */
+int segx_bn_dw_s1_ok(int B, int C, int H, int W, int k, int stride, int pad_t, int pad_l);
+int64_t segx_bn_dw_s1_ws_floats(int B, int C, int H, int W, int backward);
+int64_t segx_bn_dw_s1_rows(int B, int H, int W);
+int segx_bn_dw_s1_fwd(const float* E, const float* w0, const float* b0, float* run_mean, float* run_var, const float* Wdw, float* D, float* mean, float* var,
+                      float* ws, float momentum, float eps, int B, int C, int H, int W, int k, int pad_t, int pad_l, int64_t ws_floats, void* stream);
+int segx_bn_dw_s1_bwd(const float* dD, const float* E, const float* mean, const float* var, const float* w0, const float* b0, const float* Wdw,
+                      float* dE, float* dw0, float* db0, float* part, float* ws, float eps, int B, int C, int H, int W, int k, int pad_t, int pad_l,
+                      int64_t part_rows, int64_t ws_floats, void* stream);
 /* r04: the weight gradient dW [C][k*k] in ONE launch where a channel's B planes are one workgroup's work (B <= 8, <= 8192 outputs per plane, the float4
  * layout): returns 1 when done, 0 when the shape needs the two-stage form above (nothing launched), < 0 on error */
 int segx_dwconv2d_bwd_weight_direct(const float* dY, const float* X, float* dW, int B, int C, int H, int Wd, int OH, int OW, int k,

@@ -757,56 +757,24 @@ static int bn_team_launch_bwd(const BnBwdArgs& g, const BnTeam& t, dim3 grid, hi
 // the convolution between the exchange and the stores.  Geometry: H even, W a power of two in 16..512, OH = H / 2, OW = W / 2, so
 //   * a lane's float4 k sits at row tr + k * rpk, column tc of its chunk (rpk = 256 / (W / 4) rows per k index, (tr, tc) = thread / (W / 4), thread % (W / 4)): rows and
 //     columns step by compile-time multiples, every element of a thread has the row parity of tr;
-//   * a chunk (and a forward band of S2_BAND k indices) is an even number of whole rows and yields whole output rows.
+//   * a chunk (and a forward band of DW_BAND k indices) is an even number of whole rows and yields whole output rows.
 // LDS images use the guarded layout of mbconv_mid.hip: one zero float4 in front of every row, so the columns left of a row's first and right of its last element read zeros.
 // =================================================================================================
-constexpr int S2_BAND = 4;                 // float4 per lane of one forward band: 1024 float4 of e' = 4096 / W rows -> 256 float4 of d, one per thread
+constexpr int DW_BAND = 4;                 // float4 per lane of one forward band: 1024 float4 of e' = 4096 / W rows -> 256 float4 of d, one per thread
 constexpr int S2_IMG = 1440;               // float4 per forward image: (4096 / W + K - 2) rows of (W / 4 + 1); largest at W = 512, K = 5: 11 * 129 + 1
 constexpr int S2_GIMG = 1600;              // float4 of the backward's image of g_d: (KP * 512 / W + (K + 1) / 2) rows of (W / 8 + 1); largest at KP = 16, W = 16: 515 * 3 + 1
 struct BnDwS2Args {
     const float* E; const float* w; const float* b; const float* Wdw; float* mean; float* var;     // mean / var: written forward, read backward
     float* D; float* run_mean; float* run_var; float momentum;                                     // forward
     const float* dD; float* dE; float* dw; float* db; float* part;                                  // backward; part [team members][C][K * K]
-    float eps; int C, H, W4, pt;                                                                   // W4 = W / 4; pt = zero rows above the plane (the template's PL: columns left of it)
+    float eps; int C, H, W4, pt;                                                                   // W4 = W / 4; pt = zero rows above the plane (the template's PL: columns left of it) -- read by the stride-2 kernels only, stride 1 has (K - 1) / 2
 };
-// Forward.  After the exchange the chunk goes through LDS in bands of S2_BAND k indices (two images in turn: one barrier per band): every thread writes swish(sc * e + sh)
-// of the band's registers and of the rows the windows reach above and below it -- from the neighbouring k index (the same registers), or, at the ends of the chunk, from
-// K - 2 rows of e read again (requested before the exchange; rows outside the plane are zeros) -- then convolves at its own output float4 with dwconv_rows4_kernel's tap
-// order (ky outer, kx inner, one chain of scalar FMAs per output starting from zero).
-template <int KP, int K, int PL>
-__global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(KP <= 16 ? 3 : 2) void bn_dw_s2_fwd_team_kernel(BnDwS2Args g, BnTeam t) {
-    static_assert(KP % S2_BAND == 0 && PL <= 4 && 4 + 3 * 2 + K - 1 - PL < 16, "window does not fit the four float4 read per row");
-    constexpr int NB = KP / S2_BAND;
-    __shared__ float red[4];
-    __shared__ f32x4 img[NB > 1 ? 2 : 1][S2_IMG];
-    const int TS = t.B * t.cpp, tl = threadIdx.x;
-    const int c = blockIdx.x / TS, r = blockIdx.x - c * TS, b = r / t.cpp, ch = r - b * t.cpp;
-    const int C = g.C, W4 = g.W4, S4 = g.H * W4, j0 = ch * 256 * KP;
-    const int64_t S = 4 * (int64_t)S4, plane = ((int64_t)b * C + c) * S;
-    auto offk = [&](int k) { const int j = j0 + tl + 256 * k; return 16u * (unsigned)(j < S4 ? j : S4 - 1); };
-    f32x4 v[KP];
-    const ws_gptr xb = ws_uniform_base(g.E + plane);
-#pragma unroll
-    for (int k = 0; k < KP; ++k) v[k] = ws_load<f32x4>(xb, offk(k));
-    // the K - 2 rows above / below the chunk: thread (tr, tc) takes column tc of halo row tr (+ rpk); rows 0 .. pt - 1 lie above, the others below
-    const int rpk = 256 / W4, tr = tl / W4, tc = tl - tr * W4, HT = g.pt, LS = W4 + 1, IR = S2_BAND * rpk + K - 2;
-    f32x4 hv[2]; bool hok[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int hr = tr + q * rpk;
-        const int jh = (hr < HT ? j0 - (HT - hr) * W4 : j0 + 256 * KP + (hr - HT) * W4) + tc;
-        hok[q] = hr < K - 2 && jh >= 0 && jh < S4;
-        hv[q] = ws_load<f32x4>(xb, 16u * (unsigned)(hok[q] ? jh : 0));
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    for (int i = tl; i <= IR; i += 256) {                       // guards (visible after the barriers of the first block_sum)
-        img[0][i * LS] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (NB > 1) img[NB > 1 ? 1 : 0][i * LS] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    float w[K * K];
-#pragma unroll
-    for (int i = 0; i < K * K; ++i) w[i] = g.Wdw[(int64_t)c * K * K + i];
-    // statistics, exchange, running statistics: bn_act_fwd_team_kernel's expressions
+// ---- the stages the two strides have in common (both directions): bn_act_{fwd,bwd}_team_kernel's, on a chunk in registers ----
+// the statistics stage of bn_act_fwd_team_kernel on a chunk in registers (floats beyond the plane become zeros): the channel's mean / var / running statistics are
+// written by member 0, every thread receives the normalisation's scale and shift
+template <int KP>
+__device__ __forceinline__ void dw_team_stats(f32x4 (&v)[KP], const BnDwS2Args& g, const BnTeam& t, int c, int r, int TS, int j0, int S4, float* red, float& sc, float& sh) {
+    const int tl = threadIdx.x;
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < KP; ++k) {
@@ -836,19 +804,105 @@ __global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(KP <= 16 ? 3 : 2) void
             g.run_var[c] = (1.0f - g.momentum) * g.run_var[c] + g.momentum * (st.m2 / fmaxf(st.n - 1.0f, 1.0f));
         }
     }
-    const float sc = rsqrtf(var + g.eps) * g.w[c], sh = g.b[c] - mean * sc;
-    auto act4 = [&](const f32x4& x, bool ok) {
-        f32x4 o;
-        o.x = act_fwd_c<ACT_SWISH>(x.x * sc + sh, ACT_SWISH); o.y = act_fwd_c<ACT_SWISH>(x.y * sc + sh, ACT_SWISH);
-        o.z = act_fwd_c<ACT_SWISH>(x.z * sc + sh, ACT_SWISH); o.w = act_fwd_c<ACT_SWISH>(x.w * sc + sh, ACT_SWISH);
-        return ok ? o : f32x4{0.f, 0.f, 0.f, 0.f};
-    };
+    sc = rsqrtf(var + g.eps) * g.w[c]; sh = g.b[c] - mean * sc;
+}
+// swish(sc * e + sh) of one float4 as bn_act_fwd_team_kernel forms it; zeros where the float4 lies outside the plane
+__device__ __forceinline__ f32x4 dw_act4(const f32x4& x, float sc, float sh, bool ok) {
+    f32x4 o;
+    o.x = act_fwd_c<ACT_SWISH>(x.x * sc + sh, ACT_SWISH); o.y = act_fwd_c<ACT_SWISH>(x.y * sc + sh, ACT_SWISH);
+    o.z = act_fwd_c<ACT_SWISH>(x.z * sc + sh, ACT_SWISH); o.w = act_fwd_c<ACT_SWISH>(x.w * sc + sh, ACT_SWISH);
+    return ok ? o : f32x4{0.f, 0.f, 0.f, 0.f};
+}
+// xhat and du of one float4 from e and the gradient w.r.t. e' (de), the slope taken at xhat * w + b as bn_act_bwd_team_kernel takes it; adds to the chunk's two sums
+__device__ __forceinline__ void dw_slope4(const f32x4& xv, const float (&de)[4], bool ok, float m, float rstd, float wc, float bc_, f32x4& hh, f32x4& dd, float& sa, float& sq) {
+    hh.x = (xv.x - m) * rstd; hh.y = (xv.y - m) * rstd; hh.z = (xv.z - m) * rstd; hh.w = (xv.w - m) * rstd;
+    dd.x = de[0] * act_grad_c<ACT_SWISH>(hh.x * wc + bc_, ACT_SWISH); dd.y = de[1] * act_grad_c<ACT_SWISH>(hh.y * wc + bc_, ACT_SWISH);
+    dd.z = de[2] * act_grad_c<ACT_SWISH>(hh.z * wc + bc_, ACT_SWISH); dd.w = de[3] * act_grad_c<ACT_SWISH>(hh.w * wc + bc_, ACT_SWISH);
+    if (!ok) { dd = f32x4{0.f, 0.f, 0.f, 0.f}; hh = dd; }
+    sa += (dd.x + dd.y) + (dd.z + dd.w); sq += (dd.x * hh.x + dd.y * hh.y) + (dd.z * hh.z + dd.w * hh.w);
+}
+// the exchange and the store stage of bn_act_bwd_team_kernel: the team's two sums (members l, l + 64 per lane, then a symmetric butterfly), dw0 / db0 by member 0, g_e
+template <int KP>
+__device__ __forceinline__ void dw_team_bwd_finish(const f32x4 (&h)[KP], const f32x4 (&d)[KP], float sa, float sq, const BnDwS2Args& g, const BnTeam& t, int c, int r, int TS,
+                                                   int j0, int S4, int64_t S, int64_t plane, float sc, float* red) {
+    const int tl = threadIdx.x;
+    sa = block_sum<4>(sa, red); sq = block_sum<4>(sq, red);
+    const TeamBufs tb{t.slots + (int64_t)c * TS * TEAM_SLOT, t.mbox + (int64_t)c * TS * TEAM_MBOX, t.tag_lo, t.tag_hi, t.err, t.spin};
+    if (tl == 0) { float* pp = tb.slots + r * TEAM_SLOT; team_store(pp, sa); team_store(pp + 1, sq); }
+    float res[3];
+    team_exchange(tb, r, TS, res, [](const float* parts, int members, float (&o)[3]) {
+        const int lane = threadIdx.x & 63;
+        const bool h0 = lane < members, h1 = lane + 64 < members;
+        const float a0 = team_load(parts + TEAM_SLOT * (h0 ? lane : 0)), q0 = team_load(parts + TEAM_SLOT * (h0 ? lane : 0) + 1);
+        const float a1 = team_load(parts + TEAM_SLOT * (h1 ? lane + 64 : 0)), q1 = team_load(parts + TEAM_SLOT * (h1 ? lane + 64 : 0) + 1);
+        float As = (h0 ? a0 : 0.f) + (h1 ? a1 : 0.f), Qs = (h0 ? q0 : 0.f) + (h1 ? q1 : 0.f);
+#pragma unroll
+        for (int o2 = 1; o2 < 64; o2 <<= 1) { As += __shfl_xor(As, o2); Qs += __shfl_xor(Qs, o2); }
+        o[0] = As; o[1] = Qs; o[2] = 0.f;
+    });
+    const float As = res[0], Qs = res[1];
+    if (r == 0 && tl == 0) { g.db[c] = As; g.dw[c] = Qs; }
+    const float inv_n = 1.0f / ((float)t.B * (float)S), k1 = As * inv_n, k2 = Qs * inv_n;
+    const ws_gptr_w ob = ws_uniform_base_w(g.dE + plane);
+    int tl2 = tl;                                                // an opaque copy of the lane index: the load phase's offsets do not stay alive (bn_act_fwd_team_kernel)
+    SEGX_PIN(tl2);
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+        const int j = j0 + tl2 + 256 * k;
+        if (j < S4) {
+            f32x4 o;
+            o.x = sc * (d[k].x - k1 - h[k].x * k2); o.y = sc * (d[k].y - k1 - h[k].y * k2);
+            o.z = sc * (d[k].z - k1 - h[k].z * k2); o.w = sc * (d[k].w - k1 - h[k].w * k2);
+            ws_store<f32x4>(ob, 16u * (unsigned)j, o);
+        }
+    }
+}
+// Forward.  After the exchange the chunk goes through LDS in bands of DW_BAND k indices (two images in turn: one barrier per band): every thread writes swish(sc * e + sh)
+// of the band's registers and of the rows the windows reach above and below it -- from the neighbouring k index (the same registers), or, at the ends of the chunk, from
+// K - 2 rows of e read again (requested before the exchange; rows outside the plane are zeros) -- then convolves at its own output float4 with dwconv_rows4_kernel's tap
+// order (ky outer, kx inner, one chain of scalar FMAs per output starting from zero).
+template <int KP, int K, int PL>
+__global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(KP <= 16 ? 3 : 2) void bn_dw_s2_fwd_team_kernel(BnDwS2Args g, BnTeam t) {
+    static_assert(KP % DW_BAND == 0 && PL <= 4 && 4 + 3 * 2 + K - 1 - PL < 16, "window does not fit the four float4 read per row");
+    constexpr int NB = KP / DW_BAND;
+    __shared__ float red[4];
+    __shared__ f32x4 img[NB > 1 ? 2 : 1][S2_IMG];
+    const int TS = t.B * t.cpp, tl = threadIdx.x;
+    const int c = blockIdx.x / TS, r = blockIdx.x - c * TS, b = r / t.cpp, ch = r - b * t.cpp;
+    const int C = g.C, W4 = g.W4, S4 = g.H * W4, j0 = ch * 256 * KP;
+    const int64_t S = 4 * (int64_t)S4, plane = ((int64_t)b * C + c) * S;
+    auto offk = [&](int k) { const int j = j0 + tl + 256 * k; return 16u * (unsigned)(j < S4 ? j : S4 - 1); };
+    f32x4 v[KP];
+    const ws_gptr xb = ws_uniform_base(g.E + plane);
+#pragma unroll
+    for (int k = 0; k < KP; ++k) v[k] = ws_load<f32x4>(xb, offk(k));
+    // the K - 2 rows above / below the chunk: thread (tr, tc) takes column tc of halo row tr (+ rpk); rows 0 .. pt - 1 lie above, the others below
+    const int rpk = 256 / W4, tr = tl / W4, tc = tl - tr * W4, HT = g.pt, LS = W4 + 1, IR = DW_BAND * rpk + K - 2;
+    f32x4 hv[2]; bool hok[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const int hr = tr + q * rpk;
+        const int jh = (hr < HT ? j0 - (HT - hr) * W4 : j0 + 256 * KP + (hr - HT) * W4) + tc;
+        hok[q] = hr < K - 2 && jh >= 0 && jh < S4;
+        hv[q] = ws_load<f32x4>(xb, 16u * (unsigned)(hok[q] ? jh : 0));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    for (int i = tl; i <= IR; i += 256) {                       // guards (visible after the barriers of the first block_sum)
+        img[0][i * LS] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (NB > 1) img[NB > 1 ? 1 : 0][i * LS] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    float w[K * K];
+#pragma unroll
+    for (int i = 0; i < K * K; ++i) w[i] = g.Wdw[(int64_t)c * K * K + i];
+    float sc, sh;
+    dw_team_stats<KP>(v, g, t, c, r, TS, j0, S4, red, sc, sh);       // statistics, exchange, running statistics: bn_act_fwd_team_kernel's
+    auto act4 = [&](const f32x4& x, bool ok) { return dw_act4(x, sc, sh, ok); };
     const int OW4 = W4 >> 1, orow = tl / OW4, oc = tl - orow * OW4, D4 = S4 >> 2;
     const int rpos = (2 * orow) * LS + 2 * oc + 1;               // image position of the float4 at (row 2 orow, column 8 oc): the window's rows start there
     const ws_gptr_w db_ = ws_uniform_base_w(g.D + ((int64_t)b * C + c) * (S >> 2));
 #pragma unroll
     for (int bd = 0; bd < NB; ++bd) {
-        constexpr int KB = S2_BAND;
+        constexpr int KB = DW_BAND;
         const int k0 = bd * KB;
         f32x4* im = img[bd & (NB > 1 ? 1 : 0)];
         // image row of this thread's float4 kk: tr + (kk - k0) * rpk + HT; the band's own are all inside, of the neighbours' the last HT / first K - 2 - HT rows
@@ -968,13 +1022,11 @@ __global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(2) void bn_dw_s2_bwd_t
         // e' above is the forward's (u = sc * e + sh: what the convolution saw); the activation's slope is taken at xhat * w + b as bn_act_bwd_team_kernel takes it --
         // free of the cancellation sc * e + sh suffers where |mean| >> sigma
         f32x4 hh, dd;
-        hh.x = (xv.x - m) * rstd; hh.y = (xv.y - m) * rstd; hh.z = (xv.z - m) * rstd; hh.w = (xv.w - m) * rstd;
-        dd.x = de[0] * act_grad_c<ACT_SWISH>(hh.x * wc + bc_, ACT_SWISH); dd.y = de[1] * act_grad_c<ACT_SWISH>(hh.y * wc + bc_, ACT_SWISH);
-        dd.z = de[2] * act_grad_c<ACT_SWISH>(hh.z * wc + bc_, ACT_SWISH); dd.w = de[3] * act_grad_c<ACT_SWISH>(hh.w * wc + bc_, ACT_SWISH);
-        if (!ok) { dd = f32x4{0.f, 0.f, 0.f, 0.f}; hh = dd; }
+        dw_slope4(xv, de, ok, m, rstd, wc, bc_, hh, dd, sa, sq);
         h[k] = hh; d[k] = dd;
-        sa += (dd.x + dd.y) + (dd.z + dd.w); sq += (dd.x * hh.x + dd.y * hh.y) + (dd.z * hh.z + dd.w * hh.w);
     }
+    // The rest is dw_team_bwd_finish, kept inline HERE (and e' above, not dw_act4): through the device functions this kernel's register allocation moved -- the finish:
+    // 79 -> 77 SGPRs at <4, 3, *>; dw_act4: 1-4 VGPRs fewer in every instantiation -- and its entries in lib/resource_usage.json are held fixed.
     sa = block_sum<4>(sa, red); sq = block_sum<4>(sq, red);
     const TeamBufs tb{t.slots + (int64_t)c * TS * TEAM_SLOT, t.mbox + (int64_t)c * TS * TEAM_MBOX, t.tag_lo, t.tag_hi, t.err, t.spin};
     if (tl == 0) { float* pp = tb.slots + r * TEAM_SLOT; team_store(pp, sa); team_store(pp + 1, sq); }
@@ -1022,24 +1074,24 @@ __global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(2) void bn_dw_s2_bwd_t
     __syncthreads();
     if (tl < KK) g.part[((int64_t)r * C + c) * KK + tl] = (float)((wred[0][tl] + wred[1][tl]) + (wred[2][tl] + wred[3][tl]));
 }
-static inline bool s2_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+static inline bool dw_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 // float4 per lane of the pair's team form, 0 = not served.  The pair serves where training BatchNorm itself takes the team form (bn_auto_form: knob 3 included) and chunks
 // the planes as that launch does -- the forward statistics then are its statistics to the last bit.  Instantiated: 4, 16 and (forward) 32 float4 per lane.
-static inline int s2_kp(int B, int64_t S, bool backward) {
+static inline int dw_kp(int B, int64_t S, bool backward) {
     int kp = 0;
     if (B < 1 || S < 4 || bn_auto_form(B, S, backward, &kp) != 1) return 0;
     return kp == 4 || kp == 16 || (kp == 32 && !backward) ? kp : 0;
 }
 static inline bool s2_serves(int B, int C, int H, int W, int k, int stride, int pt, int pl) {
-    if (!(stride == 2 && (k == 3 || k == 5) && B >= 1 && C >= 1 && H >= 2 && (H & 1) == 0 && W >= 16 && W <= 512 && s2_pow2(W))) return false;
+    if (!(stride == 2 && (k == 3 || k == 5) && B >= 1 && C >= 1 && H >= 2 && (H & 1) == 0 && W >= 16 && W <= 512 && dw_pow2(W))) return false;
     // the begin pads that give OH = H / 2 (k 3: 0 | 1, k 5: 1 | 2), the same on both axes: what dwconv_bwd4s2_kernel serves -- the backward reproduces ITS chain
     if (!(pt == pl && pt >= (k - 2) / 2 && pt <= k / 2)) return false;
     const int64_t S = (int64_t)H * W;
     if (S > (int64_t)1 << 26 || (int64_t)B * C > 65535) return false;
-    const int kf = s2_kp(B, S, false), kb = s2_kp(B, S, true);
+    const int kf = dw_kp(B, S, false), kb = dw_kp(B, S, true);
     if (!kf || !kb || (1024 * kf) % (2 * W) || (1024 * kb) % (2 * W)) return false;                 // a chunk is a run of whole row pairs
     const int W4 = W / 4, rpk = 256 / W4;
-    return (S2_BAND * rpk + k - 2) * (W4 + 1) + 1 <= S2_IMG && (kb * (rpk / 2) + (k + 1) / 2) * (W4 / 2 + 1) + 1 <= S2_GIMG;
+    return (DW_BAND * rpk + k - 2) * (W4 + 1) + 1 <= S2_IMG && (kb * (rpk / 2) + (k + 1) / 2) * (W4 / 2 + 1) + 1 <= S2_GIMG;
 }
 template <int KP, int K>
 static int s2_launch_fwd(const BnDwS2Args& g, const BnTeam& t, dim3 grid, hipStream_t stream, int pl) {
@@ -1056,6 +1108,229 @@ static int s2_launch_bwd(const BnDwS2Args& g, const BnTeam& t, dim3 grid, hipStr
     if (pl == (K - 2) / 2) SEGX_S2B((K - 2) / 2); else SEGX_S2B(K / 2);
 #undef SEGX_S2B
     return check_launch("segx_bn_dw_s2_bwd");
+}
+// =================================================================================================
+// r09: the same for the STRIDE-1 blocks whose planes the channel-resident middle (mbconv_mid.hip) does not hold, and for the stem's BatchNorm + swish in front of block
+// 0's depthwise convolution: e --BatchNorm0 + swish--> e' --k x k 'same' depthwise convolution--> d, one team launch per direction, e' and the gradient w.r.t. e' never
+// written:  forward read e, write d (2 passes; bn_act_fwd_team_kernel -> dwconv_rows4_kernel<K, 1, P>: 4);  backward read e and g_d, write g_e (3;
+// dwconv_bwd_s1_fused_kernel -> bn_act_bwd_team_kernel: 6).  Chunking, lanes, statistics and the exchange are the team BatchNorm's again (dw_team_* above: the stages
+// the two strides have in common).  Geometry: W a power of two in 16..512, pads (K - 1) / 2 on every side; a lane's float4 k sits at row tr + k * rpk, column tc of its
+// chunk, which is KP * rpk whole rows; every thread produces d (g_e) at its own element positions.  Beyond its own rows a member needs P = (K - 1) / 2 rows above and
+// below: functions of e (forward) and g_d (backward) alone, read from global memory whichever member owns them -- no second exchange, no halo between members.
+// =================================================================================================
+// one row of a stride-1 window from a guarded LDS image: the 4 + 2 P floats around the float4 at `row` (P floats | float4 | P floats: 8 + 16 + 8 bytes at K = 5 --
+// less than the three float4 per row of dwconv_rows4_kernel)
+template <int P>
+__device__ __forceinline__ void dw_s1_row(float (&e)[4 + 2 * P], const float* row) {
+    static_assert(P == 1 || P == 2, "k 3 or 5");
+    const f32x4 cc = *reinterpret_cast<const f32x4*>(row);
+    if constexpr (P == 1) { e[0] = row[-1]; e[5] = row[4]; }
+    else {
+        const float2 l = *reinterpret_cast<const float2*>(row - 2), rr = *reinterpret_cast<const float2*>(row + 4);
+        e[0] = l.x; e[1] = l.y; e[6] = rr.x; e[7] = rr.y;
+    }
+    e[P] = cc.x; e[P + 1] = cc.y; e[P + 2] = cc.z; e[P + 3] = cc.w;
+}
+// One step of the backward's chains, rounded as dwconv_bwd_s1_fused_kernel's `acc += w * dy` is on the same target: the device compiler contracts that into one FMA, a
+// host build (no FMA in the baseline instruction set) rounds twice.  Written as `+=` here the products were paired into v_pk_mul_f32 first and added separately -- 45 %
+// of g_e then differed from the two-launch route in the last bit, and with them the two BatchNorm sums.
+__device__ __forceinline__ float dw_chain_fma(float a, float b, float c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_fmaf(a, b, c);
+#else
+    return a * b + c;
+#endif
+}
+constexpr int S1_IMG = 1549;              // float4 per forward image: (DW_BAND * 1024 / W + K - 1) rows of (W / 4 + 1), plus the guard behind the last; largest at W = 512, K = 5: 12 * 129 + 1
+template <int KP> struct S1G { static constexpr int IMG = KP <= 4 ? 1549 : 4645; };       // the backward's image of g_d: (KP * 1024 / W + K - 1) rows; KP 16, W = 512 | 32, K = 5: 36 * 129 + 1
+// Forward: bn_dw_s2_fwd_team_kernel's band walk with stride-1 windows.  A band of DW_BAND k indices is an image of DW_BAND * rpk + 2 P rows; the P rows above and below
+// it come from the neighbouring k index of the same registers or, at the ends of the chunk, from e read again (requested before the exchange; zeros outside the plane);
+// every thread then convolves at the band's DW_BAND float4 of its own: ky outer, kx inner, one chain of scalar FMAs from zero -- dwconv_rows4_kernel<K, 1, P, false>'s.
+template <int KP, int K>
+__global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(KP <= 16 ? 3 : 2) void bn_dw_s1_fwd_team_kernel(BnDwS2Args g, BnTeam t) {
+    static_assert(KP % DW_BAND == 0 && (K == 3 || K == 5), "bands of DW_BAND k indices; k 3 or 5");
+    constexpr int P = (K - 1) / 2, NB = KP / DW_BAND, KB = DW_BAND;
+    __shared__ float red[4];
+    __shared__ f32x4 img[NB > 1 ? 2 : 1][S1_IMG];
+    const int TS = t.B * t.cpp, tl = threadIdx.x;
+    const int c = blockIdx.x / TS, r = blockIdx.x - c * TS, b = r / t.cpp, ch = r - b * t.cpp;
+    const int C = g.C, W4 = g.W4, S4 = g.H * W4, j0 = ch * 256 * KP;
+    const int64_t S = 4 * (int64_t)S4, plane = ((int64_t)b * C + c) * S;
+    auto offk = [&](int k) { const int j = j0 + tl + 256 * k; return 16u * (unsigned)(j < S4 ? j : S4 - 1); };
+    f32x4 v[KP];
+    const ws_gptr xb = ws_uniform_base(g.E + plane);
+#pragma unroll
+    for (int k = 0; k < KP; ++k) v[k] = ws_load<f32x4>(xb, offk(k));
+    // the P rows above / below the chunk: thread (tr, tc) takes column tc of halo row tr (+ rpk); rows 0 .. P - 1 lie above, P .. 2 P - 1 below
+    const int rpk = 256 / W4, tr = tl / W4, tc = tl - tr * W4, LS = W4 + 1, IR = KB * rpk + 2 * P;
+    f32x4 hv[2]; bool hok[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const int hr = tr + q * rpk;
+        const int jh = (hr < P ? j0 - (P - hr) * W4 : j0 + 256 * KP + (hr - P) * W4) + tc;
+        hok[q] = hr < 2 * P && jh >= 0 && jh < S4;
+        hv[q] = ws_load<f32x4>(xb, 16u * (unsigned)(hok[q] ? jh : 0));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    for (int i = tl; i <= IR; i += 256) {                       // guards (visible after the barriers of the first block_sum)
+        img[0][i * LS] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (NB > 1) img[NB > 1 ? 1 : 0][i * LS] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    float w[K * K];
+#pragma unroll
+    for (int i = 0; i < K * K; ++i) w[i] = g.Wdw[(int64_t)c * K * K + i];
+    float sc, sh;
+    dw_team_stats<KP>(v, g, t, c, r, TS, j0, S4, red, sc, sh);
+    const ws_gptr_w db_ = ws_uniform_base_w(g.D + plane);
+    int tl2 = tl;                                                // the stores' offsets from an opaque copy of the lane index (bn_act_fwd_team_kernel)
+    SEGX_PIN(tl2);
+#pragma unroll
+    for (int bd = 0; bd < NB; ++bd) {
+        const int k0 = bd * KB;
+        f32x4* im = img[bd & (NB > 1 ? 1 : 0)];
+        // image row of this thread's float4 kk: tr + (kk - k0) * rpk + P; the band's own are all inside, of the neighbours' the last / first P rows
+#pragma unroll
+        for (int kk = k0 - 1; kk <= k0 + KB; ++kk) {
+            if (kk < 0 || kk >= KP) continue;                    // compile-time: the chunk's ends take the rows read again (below)
+            const int ir = tr + (kk - k0) * rpk + P;
+            if (kk < k0 ? ir >= 0 : kk < k0 + KB || ir < IR) im[ir * LS + 1 + tc] = dw_act4(v[kk], sc, sh, j0 + tl + 256 * kk < S4);
+        }
+        if (bd == 0 || bd == NB - 1) {
+#pragma unroll
+            for (int q2 = 0; q2 < 2; ++q2) {
+                const int hr = tr + q2 * rpk;
+                if (hr < 2 * P && (hr < P ? bd == 0 : bd == NB - 1)) im[(hr < P ? hr : KB * rpk + hr) * LS + 1 + tc] = dw_act4(hv[q2], sc, sh, hok[q2]);
+            }
+        }
+        __syncthreads();
+        // float 0 of the float4 (image row i, column tc) sits at 4 (i LS + 1 + tc); the window of this thread's float4 kq of the band starts at image row tr + kq rpk
+        const float* pf = reinterpret_cast<const float*>(im) + 4 * (tr * LS + 1 + tc);
+#pragma unroll
+        for (int kq = 0; kq < KB; ++kq) {
+            float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ky = 0; ky < K; ++ky) {
+                float e[4 + 2 * P];
+                dw_s1_row<P>(e, pf + 4 * ((kq * rpk + ky) * LS));
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int kx = 0; kx < K; ++kx) acc[j] += w[ky * K + kx] * e[j + kx];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) SEGX_PIN(acc[j]);    // as dwconv_rows4_kernel: the chain stays a chain of scalar FMAs
+            }
+            const int dj = j0 + tl2 + 256 * (k0 + kq);
+            if (dj < S4) ws_store<f32x4>(db_, 16u * (unsigned)dj, f32x4{acc[0], acc[1], acc[2], acc[3]});
+        }
+        __builtin_amdgcn_sched_barrier(0);                       // one band at a time
+    }
+}
+// Backward: the chunk of e in registers, the rows of g_d under it plus P above and below (zeros outside the plane) as ONE guarded image in LDS.  Per own element one walk
+// over the K x K window of g_d feeds the gradient w.r.t. e' -- dwconv_bwd_s1_fused_kernel's chain: the rotated filter, rows then columns ascending, scalar FMAs from zero,
+// so xhat and du are the two launches' bits -- and the K x K filter-gradient sums e' * g_d with e' = swish(sc * e + sh) as the forward forms it.  The slope, the two
+// BatchNorm sums, the exchange and g_e are bn_act_bwd_team_kernel's (dw_slope4, dw_team_bwd_finish); the filter gradient leaves as in bn_dw_s2_bwd_team_kernel: a lane's
+// products per tap in an fp32 chain, the lanes' sums added in double across lanes and waves, one row of partials per member.  The filter taps are read through a uniform address: scalar registers.
+template <int KP, int K>
+__global__ __launch_bounds__(256) SEGX_MIN_WAVES_PER_SIMD(2) void bn_dw_s1_bwd_team_kernel(BnDwS2Args g, BnTeam t) {
+    static_assert(K == 3 || K == 5, "k 3 or 5");
+    constexpr int P = (K - 1) / 2, KK = K * K, NGV = KP + P;     // g_d float4 per thread: 256 KP + 2 P W / 4 <= 256 (KP + P) for W <= 512
+    __shared__ float red[4];
+    __shared__ double wred[4][KK];
+    __shared__ f32x4 gim[S1G<KP>::IMG];
+    const int TS = t.B * t.cpp, tl = threadIdx.x;
+    const int c = blockIdx.x / TS, r = blockIdx.x - c * TS, b = r / t.cpp, ch = r - b * t.cpp;
+    const int C = g.C, W4 = g.W4, H = g.H, S4 = H * W4, j0 = ch * 256 * KP;
+    const int64_t S = 4 * (int64_t)S4, plane = ((int64_t)b * C + c) * S;
+    auto offk = [&](int k) { const int j = j0 + tl + 256 * k; return 16u * (unsigned)(j < S4 ? j : S4 - 1); };
+    f32x4 h[KP], d[KP];                              // e as loaded -> xhat; du
+    const ws_gptr xb = ws_uniform_base(g.E + plane);
+#pragma unroll
+    for (int k = 0; k < KP; ++k) h[k] = ws_load<f32x4>(xb, offk(k));
+    // g_d: image row gi holds plane row y_lo + gi; thread (tr, tc) takes column tc of rows tr + i * rpk
+    const int rpk = 256 / W4, tr = tl / W4, tc = tl - tr * W4, LS = W4 + 1, NG = KP * rpk + 2 * P, y_lo = j0 / W4 - P;
+    {
+        const ws_gptr gb = ws_uniform_base(g.dD + plane);
+        f32x4 gv[NGV];
+#pragma unroll
+        for (int i = 0; i < NGV; ++i) {
+            const int gi = tr + i * rpk, y = y_lo + gi;
+            gv[i] = ws_load<f32x4>(gb, 16u * (unsigned)(gi < NG && y >= 0 && y < H ? y * W4 + tc : 0));
+        }
+        for (int i = tl; i <= NG; i += 256) gim[i * LS] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < NGV; ++i) {
+            const int gi = tr + i * rpk, y = y_lo + gi;
+            if (gi < NG) gim[gi * LS + 1 + tc] = y >= 0 && y < H ? gv[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    }
+    __syncthreads();
+    __builtin_amdgcn_sched_barrier(0);
+    const float rstd = rsqrtf(g.var[c] + g.eps), m = g.mean[c], wc = g.w[c], bc_ = g.b[c], sc = rstd * wc, sh = bc_ - m * sc;       // sc, sh: the forward's bits
+    float wr[KK], dwa[KK];                           // the rotated filter (dwconv_bwd_s1_fused_kernel's w); dwa[t]: the filter-gradient sum of tap KK - 1 - t
+#pragma unroll
+    for (int i = 0; i < KK; ++i) { wr[i] = g.Wdw[(int64_t)c * KK + (KK - 1 - i)]; dwa[i] = 0.f; }
+    // the window of this thread's float4 k starts at image row tr + k rpk (plane row - P)
+    const float* gf = reinterpret_cast<const float*>(gim) + 4 * (tr * LS + 1 + tc);
+    float sa = 0.f, sq = 0.f;
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+        const bool ok = j0 + tl + 256 * k < S4;
+        const f32x4 xv = h[k];
+        const f32x4 ev = dw_act4(xv, sc, sh, ok);
+        const float ep[4] = {ev.x, ev.y, ev.z, ev.w};
+        float de[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ky = 0; ky < K; ++ky) {
+            float G[4 + 2 * P];
+            dw_s1_row<P>(G, gf + 4 * ((k * rpk + ky) * LS));
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int kx = 0; kx < K; ++kx) {
+                    de[i] = dw_chain_fma(wr[ky * K + kx], G[i + kx], de[i]); dwa[ky * K + kx] = dw_chain_fma(ep[i], G[i + kx], dwa[ky * K + kx]);
+                }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) SEGX_PIN(de[i]);         // scalar FMAs (mbconv_mid.hip: paired into v_pk_fma_f32 the chains spilled)
+#pragma unroll
+            for (int kx = 0; kx < K; ++kx) SEGX_PIN(dwa[ky * K + kx]);
+            __builtin_amdgcn_sched_barrier(0);                   // one row of the walk at a time
+        }
+        f32x4 hh, dd;
+        dw_slope4(xv, de, ok, m, rstd, wc, bc_, hh, dd, sa, sq);
+        h[k] = hh; d[k] = dd;
+    }
+    dw_team_bwd_finish<KP>(h, d, sa, sq, g, t, c, r, TS, j0, S4, S, plane, sc, red);
+    // this member's share of the filter gradient
+#pragma unroll
+    for (int i = 0; i < KK; ++i) {
+        const double sw = wave_sum_d((double)dwa[i]);
+        if ((tl & 63) == 0) wred[tl >> 6][KK - 1 - i] = sw;
+    }
+    __syncthreads();
+    if (tl < KK) g.part[((int64_t)r * C + c) * KK + tl] = (float)((wred[0][tl] + wred[1][tl]) + (wred[2][tl] + wred[3][tl]));
+}
+// the pair serves where training BatchNorm takes the team form with an instantiated chunk (dw_kp), the rows are a power of two wide and both LDS images fit
+static inline bool s1_serves(int B, int C, int H, int W, int k, int stride, int pt, int pl) {
+    if (!(stride == 1 && (k == 3 || k == 5) && B >= 1 && C >= 1 && H >= 1 && W >= 16 && W <= 512 && dw_pow2(W))) return false;
+    if (!(pt == (k - 1) / 2 && pl == (k - 1) / 2)) return false;                                     // 'same': dwconv_bwd_s1_fused_kernel's case -- the backward reproduces ITS chain
+    const int64_t S = (int64_t)H * W;
+    if (S > (int64_t)1 << 26 || (int64_t)B * C > 65535) return false;
+    const int kf = dw_kp(B, S, false), kb = dw_kp(B, S, true);
+    if (!kf || !kb || (1024 * kf) % W || (1024 * kb) % W) return false;                             // a chunk is a run of whole rows
+    const int W4 = W / 4, rpk = 256 / W4;
+    return (DW_BAND * rpk + k - 1) * (W4 + 1) + 1 <= S1_IMG && (kb * rpk + k - 1) * (W4 + 1) + 1 <= (kb <= 4 ? S1G<4>::IMG : S1G<16>::IMG);
+}
+template <int KP, int K>
+static int s1_launch_fwd(const BnDwS2Args& g, const BnTeam& t, dim3 grid, hipStream_t stream) {
+    if (int rc = team_occupancy_ok((const void*)bn_dw_s1_fwd_team_kernel<KP, K>, "segx_bn_dw_s1_fwd")) return rc;
+    hipLaunchKernelGGL((bn_dw_s1_fwd_team_kernel<KP, K>), grid, dim3(256), 0, stream, g, t);
+    return check_launch("segx_bn_dw_s1_fwd");
+}
+template <int KP, int K>
+static int s1_launch_bwd(const BnDwS2Args& g, const BnTeam& t, dim3 grid, hipStream_t stream) {
+    if (int rc = team_occupancy_ok((const void*)bn_dw_s1_bwd_team_kernel<KP, K>, "segx_bn_dw_s1_bwd")) return rc;
+    hipLaunchKernelGGL((bn_dw_s1_bwd_team_kernel<KP, K>), grid, dim3(256), 0, stream, g, t);
+    return check_launch("segx_bn_dw_s1_bwd");
 }
 // The resident kernels exist per (activation, pooling, skip) combination the backbones use -- swish (+ pooling), none (+ skip), relu -- and once with
 // the run-time values for everything else.
@@ -2301,56 +2576,81 @@ extern "C" int segx_plane_dot(const float* A, const float* Bm, float* out, int64
 extern "C" int segx_bn_dw_s2_ok(int B, int C, int H, int W, int k, int stride, int pad_t, int pad_l) { return s2_serves(B, C, H, W, k, stride, pad_t, pad_l) ? 1 : 0; }
 /* floats of the exchange scratch of one call (slots + mailboxes of every team), 0 where the pair does not serve */
 extern "C" int64_t segx_bn_dw_s2_ws_floats(int B, int C, int H, int W, int backward) {
-    const int kp = H > 0 && W > 0 ? s2_kp(B, (int64_t)H * W, backward != 0) : 0;
+    const int kp = H > 0 && W > 0 ? dw_kp(B, (int64_t)H * W, backward != 0) : 0;
     return kp ? (int64_t)C * B * bn_team_chunks((int64_t)H * W, kp) * (TEAM_SLOT + TEAM_MBOX) : 0;
 }
 /* rows of the backward's filter-gradient partials: part [rows][C][k * k] (one per team member) */
 extern "C" int64_t segx_bn_dw_s2_rows(int B, int H, int W) {
-    const int kp = H > 0 && W > 0 ? s2_kp(B, (int64_t)H * W, true) : 0;
+    const int kp = H > 0 && W > 0 ? dw_kp(B, (int64_t)H * W, true) : 0;
     return kp ? (int64_t)B * bn_team_chunks((int64_t)H * W, kp) : 0;
 }
-static int s2_team(BnTeam& t, float* ws, int64_t ws_floats, int B, int C, int64_t S, int kp, const char* what) {
+static int dw_team(BnTeam& t, float* ws, int64_t ws_floats, int B, int C, int64_t S, int kp, const char* what, int stride) {
     t.B = B; t.cpp = bn_team_chunks(S, kp); t.slots = ws; t.mbox = ws + (int64_t)C * B * t.cpp * TEAM_SLOT;
     team_fill(t);
     SEGX_REQUIRE(B * t.cpp <= team_cap() && (int64_t)C * B * t.cpp < 2147483647LL, "%s: team of %d workgroups", what, B * t.cpp);
     const int64_t need = (int64_t)C * B * t.cpp * (TEAM_SLOT + TEAM_MBOX);
-    SEGX_REQUIRE(ws_floats >= need, "%s: the scratch holds %lld floats, this call needs %lld (segx_bn_dw_s2_ws_floats under the current knob 3)", what, (long long)ws_floats, (long long)need);
+    SEGX_REQUIRE(ws_floats >= need, "%s: the scratch holds %lld floats, this call needs %lld (segx_bn_dw_s%d_ws_floats under the current knob 3)", what, (long long)ws_floats, (long long)need, stride);
     return 0;
+}
+// both strides: `what` names the entry point in messages, stride picks the predicate and the kernels
+static int bn_dw_fwd(const char* what, int stride, const float* E, const float* w0, const float* b0, float* run_mean, float* run_var, const float* Wdw, float* D, float* mean,
+                     float* var, float* ws, float momentum, float eps, int B, int C, int H, int W, int k, int pad_t, int pad_l, int64_t ws_floats, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(E && w0 && b0 && Wdw && D && mean && var && ws && (!run_mean == !run_var), "%s: bad args", what);
+    SEGX_REQUIRE(stride == 2 ? s2_serves(B, C, H, W, k, 2, pad_t, pad_l) : s1_serves(B, C, H, W, k, 1, pad_t, pad_l), "%s: shape not served (segx_bn_dw_s%d_ok == 0)", what, stride);
+    SEGX_REQUIRE(((reinterpret_cast<uintptr_t>(E) | reinterpret_cast<uintptr_t>(D)) & 15) == 0, "%s: tensors must be 16-byte aligned", what);
+    const int64_t S = (int64_t)H * W;
+    const int kp = dw_kp(B, S, false);
+    BnTeam t;
+    if (int rc = dw_team(t, ws, ws_floats, B, C, S, kp, what, stride)) return rc;
+    BnDwS2Args g; memset(&g, 0, sizeof(g));
+    g.E = E; g.w = w0; g.b = b0; g.Wdw = Wdw; g.mean = mean; g.var = var; g.D = D; g.run_mean = run_mean; g.run_var = run_var; g.momentum = momentum;
+    g.eps = eps; g.C = C; g.H = H; g.W4 = W / 4; g.pt = stride == 2 ? pad_t : 0;
+    const dim3 tg = team_grid((int64_t)C * B * t.cpp);
+#define SEGX_DW(KP) (stride == 2 ? (k == 3 ? s2_launch_fwd<KP, 3>(g, t, tg, stream, pad_l) : s2_launch_fwd<KP, 5>(g, t, tg, stream, pad_l)) \
+                                 : (k == 3 ? s1_launch_fwd<KP, 3>(g, t, tg, stream) : s1_launch_fwd<KP, 5>(g, t, tg, stream)))
+    return kp == 4 ? SEGX_DW(4) : kp == 16 ? SEGX_DW(16) : SEGX_DW(32);
+#undef SEGX_DW
+}
+static int bn_dw_bwd(const char* what, int stride, const float* dD, const float* E, const float* mean, const float* var, const float* w0, const float* b0, const float* Wdw,
+                     float* dE, float* dw0, float* db0, float* part, float* ws, float eps, int B, int C, int H, int W, int k, int pad_t, int pad_l,
+                     int64_t part_rows, int64_t ws_floats, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(dD && E && mean && var && w0 && b0 && Wdw && dE && dw0 && db0 && part && ws, "%s: bad args", what);
+    SEGX_REQUIRE(stride == 2 ? s2_serves(B, C, H, W, k, 2, pad_t, pad_l) : s1_serves(B, C, H, W, k, 1, pad_t, pad_l), "%s: shape not served (segx_bn_dw_s%d_ok == 0)", what, stride);
+    SEGX_REQUIRE(((reinterpret_cast<uintptr_t>(E) | reinterpret_cast<uintptr_t>(dD) | reinterpret_cast<uintptr_t>(dE)) & 15) == 0, "%s: tensors must be 16-byte aligned", what);
+    const int64_t S = (int64_t)H * W;
+    const int kp = dw_kp(B, S, true);
+    BnTeam t;
+    if (int rc = dw_team(t, ws, ws_floats, B, C, S, kp, what, stride)) return rc;
+    SEGX_REQUIRE(part_rows >= (int64_t)B * t.cpp, "%s: the filter-gradient partials hold %lld rows, this call writes %d (segx_bn_dw_s%d_rows under the current knob 3)",
+                 what, (long long)part_rows, B * t.cpp, stride);
+    BnDwS2Args g; memset(&g, 0, sizeof(g));
+    g.E = E; g.w = w0; g.b = b0; g.Wdw = Wdw; g.mean = const_cast<float*>(mean); g.var = const_cast<float*>(var); g.dD = dD; g.dE = dE; g.dw = dw0; g.db = db0; g.part = part;
+    g.eps = eps; g.C = C; g.H = H; g.W4 = W / 4; g.pt = stride == 2 ? pad_t : 0;
+    const dim3 tg = team_grid((int64_t)C * B * t.cpp);
+#define SEGX_DW(KP) (stride == 2 ? (k == 3 ? s2_launch_bwd<KP, 3>(g, t, tg, stream, pad_l) : s2_launch_bwd<KP, 5>(g, t, tg, stream, pad_l)) \
+                                 : (k == 3 ? s1_launch_bwd<KP, 3>(g, t, tg, stream) : s1_launch_bwd<KP, 5>(g, t, tg, stream)))
+    return kp == 4 ? SEGX_DW(4) : SEGX_DW(16);
+#undef SEGX_DW
 }
 extern "C" int segx_bn_dw_s2_fwd(const float* E, const float* w0, const float* b0, float* run_mean, float* run_var, const float* Wdw, float* D, float* mean, float* var,
                                  float* ws, float momentum, float eps, int B, int C, int H, int W, int k, int pad_t, int pad_l, int64_t ws_floats, void* stream_) {
-    SEGX_STREAM; SEGX_REQUIRE(E && w0 && b0 && Wdw && D && mean && var && ws && (!run_mean == !run_var), "segx_bn_dw_s2_fwd: bad args");
-    SEGX_REQUIRE(s2_serves(B, C, H, W, k, 2, pad_t, pad_l), "segx_bn_dw_s2_fwd: shape not served (segx_bn_dw_s2_ok == 0)");
-    SEGX_REQUIRE(((reinterpret_cast<uintptr_t>(E) | reinterpret_cast<uintptr_t>(D)) & 15) == 0, "segx_bn_dw_s2_fwd: tensors must be 16-byte aligned");
-    const int64_t S = (int64_t)H * W;
-    const int kp = s2_kp(B, S, false);
-    BnTeam t;
-    if (int rc = s2_team(t, ws, ws_floats, B, C, S, kp, "segx_bn_dw_s2_fwd")) return rc;
-    BnDwS2Args g; memset(&g, 0, sizeof(g));
-    g.E = E; g.w = w0; g.b = b0; g.Wdw = Wdw; g.mean = mean; g.var = var; g.D = D; g.run_mean = run_mean; g.run_var = run_var; g.momentum = momentum;
-    g.eps = eps; g.C = C; g.H = H; g.W4 = W / 4; g.pt = pad_t;
-    const dim3 tg = team_grid((int64_t)C * B * t.cpp);
-#define SEGX_S2(KP) (k == 3 ? s2_launch_fwd<KP, 3>(g, t, tg, stream, pad_l) : s2_launch_fwd<KP, 5>(g, t, tg, stream, pad_l))
-    return kp == 4 ? SEGX_S2(4) : kp == 16 ? SEGX_S2(16) : SEGX_S2(32);
-#undef SEGX_S2
+    return bn_dw_fwd("segx_bn_dw_s2_fwd", 2, E, w0, b0, run_mean, run_var, Wdw, D, mean, var, ws, momentum, eps, B, C, H, W, k, pad_t, pad_l, ws_floats, stream_);
 }
 extern "C" int segx_bn_dw_s2_bwd(const float* dD, const float* E, const float* mean, const float* var, const float* w0, const float* b0, const float* Wdw,
                                  float* dE, float* dw0, float* db0, float* part, float* ws, float eps, int B, int C, int H, int W, int k, int pad_t, int pad_l,
                                  int64_t part_rows, int64_t ws_floats, void* stream_) {
-    SEGX_STREAM; SEGX_REQUIRE(dD && E && mean && var && w0 && b0 && Wdw && dE && dw0 && db0 && part && ws, "segx_bn_dw_s2_bwd: bad args");
-    SEGX_REQUIRE(s2_serves(B, C, H, W, k, 2, pad_t, pad_l), "segx_bn_dw_s2_bwd: shape not served (segx_bn_dw_s2_ok == 0)");
-    SEGX_REQUIRE(((reinterpret_cast<uintptr_t>(E) | reinterpret_cast<uintptr_t>(dD) | reinterpret_cast<uintptr_t>(dE)) & 15) == 0, "segx_bn_dw_s2_bwd: tensors must be 16-byte aligned");
-    const int64_t S = (int64_t)H * W;
-    const int kp = s2_kp(B, S, true);
-    BnTeam t;
-    if (int rc = s2_team(t, ws, ws_floats, B, C, S, kp, "segx_bn_dw_s2_bwd")) return rc;
-    SEGX_REQUIRE(part_rows >= (int64_t)B * t.cpp, "segx_bn_dw_s2_bwd: the filter-gradient partials hold %lld rows, this call writes %d (segx_bn_dw_s2_rows under the current knob 3)",
-                 (long long)part_rows, B * t.cpp);
-    BnDwS2Args g; memset(&g, 0, sizeof(g));
-    g.E = E; g.w = w0; g.b = b0; g.Wdw = Wdw; g.mean = const_cast<float*>(mean); g.var = const_cast<float*>(var); g.dD = dD; g.dE = dE; g.dw = dw0; g.db = db0; g.part = part;
-    g.eps = eps; g.C = C; g.H = H; g.W4 = W / 4; g.pt = pad_t;
-    const dim3 tg = team_grid((int64_t)C * B * t.cpp);
-#define SEGX_S2(KP) (k == 3 ? s2_launch_bwd<KP, 3>(g, t, tg, stream, pad_l) : s2_launch_bwd<KP, 5>(g, t, tg, stream, pad_l))
-    return kp == 4 ? SEGX_S2(4) : SEGX_S2(16);
-#undef SEGX_S2
+    return bn_dw_bwd("segx_bn_dw_s2_bwd", 2, dD, E, mean, var, w0, b0, Wdw, dE, dw0, db0, part, ws, eps, B, C, H, W, k, pad_t, pad_l, part_rows, ws_floats, stream_);
+}
+// ---- r09: the stride-1 siblings (bn_dw_s1_{fwd,bwd}_team_kernel): the same argument lists; the scratch and the partials' rows depend on the plane alone, as above ----
+extern "C" int segx_bn_dw_s1_ok(int B, int C, int H, int W, int k, int stride, int pad_t, int pad_l) { return s1_serves(B, C, H, W, k, stride, pad_t, pad_l) ? 1 : 0; }
+extern "C" int64_t segx_bn_dw_s1_ws_floats(int B, int C, int H, int W, int backward) { return segx_bn_dw_s2_ws_floats(B, C, H, W, backward); }
+extern "C" int64_t segx_bn_dw_s1_rows(int B, int H, int W) { return segx_bn_dw_s2_rows(B, H, W); }
+extern "C" int segx_bn_dw_s1_fwd(const float* E, const float* w0, const float* b0, float* run_mean, float* run_var, const float* Wdw, float* D, float* mean, float* var,
+                                 float* ws, float momentum, float eps, int B, int C, int H, int W, int k, int pad_t, int pad_l, int64_t ws_floats, void* stream_) {
+    return bn_dw_fwd("segx_bn_dw_s1_fwd", 1, E, w0, b0, run_mean, run_var, Wdw, D, mean, var, ws, momentum, eps, B, C, H, W, k, pad_t, pad_l, ws_floats, stream_);
+}
+extern "C" int segx_bn_dw_s1_bwd(const float* dD, const float* E, const float* mean, const float* var, const float* w0, const float* b0, const float* Wdw,
+                                 float* dE, float* dw0, float* db0, float* part, float* ws, float eps, int B, int C, int H, int W, int k, int pad_t, int pad_l,
+                                 int64_t part_rows, int64_t ws_floats, void* stream_) {
+    return bn_dw_bwd("segx_bn_dw_s1_bwd", 1, dD, E, mean, var, w0, b0, Wdw, dE, dw0, db0, part, ws, eps, B, C, H, W, k, pad_t, pad_l, part_rows, ws_floats, stream_);
 }

@@ -102,15 +102,20 @@ class MBConvBlock(nn.Module):
 
     fused_entry = True         # _bn0 + swish and a stride-2 depthwise convolution as ONE team launch per direction where the library serves the shape (SF.bn_act_dwconv_s2);
                                # False: the two ops (tools/ab_switch.py)
+    fused_entry_s1 = True      # the same for the stride-1 blocks the channel-resident middle does not take (SF.bn_act_dwconv_s1); a switch of its own
 
     def _takes_fused_entry(self, x):
-        """training, one process, an expansion, a stride-2 depthwise convolution, a served shape (x: the block's input -- the expansion keeps its height and width)"""
-        if not (MBConvBlock.fused_entry and self.training and SF._bn_stats_sync is None and self.expand_ratio != 1):
-            return False
+        """training, one process, an expansion, a stride-2 or a 'same' stride-1 depthwise convolution, a served shape (x: the block's input -- the expansion keeps its height
+        and width).  Asked after _takes_fused_middle: the channel-resident middle keeps the planes it serves."""
         dw = self._depthwise_conv
-        if not (self._bn0.training and dw.stride == (2, 2) and dw.kernel_size[0] == dw.kernel_size[1] and x.dim() == 4 and x.dtype == torch.float32):
+        if not (self.training and SF._bn_stats_sync is None and self.expand_ratio != 1 and dw.stride in ((1, 1), (2, 2))):
             return False
-        return SF.bn_dw_s2_ok((x.shape[0], dw.in_channels, x.shape[2], x.shape[3]), dw.kernel_size[0], 2, dw.static_pad)
+        if not (MBConvBlock.fused_entry if dw.stride == (2, 2) else MBConvBlock.fused_entry_s1):
+            return False
+        if not (self._bn0.training and dw.kernel_size[0] == dw.kernel_size[1] and x.dim() == 4 and x.dtype == torch.float32):
+            return False
+        ok = SF.bn_dw_s2_ok if dw.stride == (2, 2) else SF.bn_dw_s1_ok
+        return ok((x.shape[0], dw.in_channels, x.shape[2], x.shape[3]), dw.kernel_size[0], dw.stride[0], dw.static_pad)
 
     def _takes_fused_middle(self, x):
         """training, one process (synchronised BatchNorm exchanges statistics between statistics and apply), an expansion, stride 1 with symmetric padding, a served shape"""
@@ -141,15 +146,19 @@ class MBConvBlock(nn.Module):
         Wb = SF.se_gate_weights(y, psum, nch, self._se_reduce.weight, self._se_reduce.bias, self._se_expand.weight, self._se_expand.bias, w2)
         return SF.conv1x1_per_sample_bias(y, Wb, b2, resid=inputs if skip else None)
 
-    def forward(self, inputs, drop_connect_rate=None):
-        """efficientnet/model.py:82-126"""
+    def forward(self, inputs, drop_connect_rate=None, entry_bn=None):
+        """efficientnet/model.py:82-126.  entry_bn: the BatchNorm (+ swish) the caller left to this block's depthwise convolution (EfficientNet._stem_into_block0: the
+        stem's, `inputs` is then the stem convolution's raw output; only for a block without expansion and skip)"""
         x = skip_in = inputs
         skip = self.stride == 1 and self.input_filters == self.output_filters
-        fused = self._takes_fused_middle(x)
-        entry = not fused and self._takes_fused_entry(x)
-        if entry:
-            dw = self._depthwise_conv
-            d = SF.bn_act_dwconv_s2(self._expand_conv(x), self._bn0, dw.weight, dw.stride[0], dw.static_pad)
+        fused = entry_bn is None and self._takes_fused_middle(x)
+        entry = entry_bn is not None or (not fused and self._takes_fused_entry(x))
+        dw = self._depthwise_conv
+        if entry_bn is not None:
+            assert self.expand_ratio == 1 and not skip
+            d = SF.bn_act_dwconv_s1(x, entry_bn, dw.weight, dw.stride[0], dw.static_pad)
+        elif entry:
+            d = (SF.bn_act_dwconv_s2 if dw.stride == (2, 2) else SF.bn_act_dwconv_s1)(self._expand_conv(x), self._bn0, dw.weight, dw.stride[0], dw.static_pad)
         elif self.expand_ratio != 1 and not fused:
             # (`inputs` has two consumers when there is a skip connection.  Routing the second through the GEMM op's input alias -- its gradient added
             # inside the expansion's dX GEMM, SF.conv1x1(pass_input=True), what the Inception modules do -- was measured here, r04_d: the residual keeps
@@ -234,16 +243,35 @@ class EfficientNet(FoldableBackbone, nn.Module):
                                 ignore_missing_keys=ignore_missing_keys)
         return model
 
+    fused_stem_entry = True    # the stem's _bn0 + swish inside block 0's depthwise convolution (SF.bn_act_dwconv_s1) where _stem_into_block0 says so; False: SF.bn_act
+
+    def _stem_into_block0(self, inputs):
+        """does block 0 take the stem convolution's raw output and the stem's _bn0?  Training, one process, not folded; block 0 without expansion and skip (the stem's
+        activation then has no other consumer) and with a 'same' stride-1 depthwise convolution; a stem output the library serves."""
+        blk = self._blocks[0]
+        dw, st = blk._depthwise_conv, self._conv_stem
+        if not (EfficientNet.fused_stem_entry and self.training and self._bn0.training and blk.training and SF._bn_stats_sync is None and not self.batchnorm_folded):
+            return False
+        if blk.expand_ratio != 1 or dw.stride != (1, 1) or dw.kernel_size[0] != dw.kernel_size[1] or (blk.stride == 1 and blk.input_filters == blk.output_filters):
+            return False
+        if inputs.dim() != 4 or inputs.dtype != torch.float32 or 0 in self.endpoint_blk_indices:
+            return False
+        pl, pr, pt, pb = st.static_pad
+        H = (inputs.shape[2] + pt + pb - st.kernel_size[0]) // st.stride[0] + 1
+        W = (inputs.shape[3] + pl + pr - st.kernel_size[1]) // st.stride[1] + 1
+        return SF.bn_dw_s1_ok((inputs.shape[0], dw.in_channels, H, W), dw.kernel_size[0], 1, dw.static_pad)
+
     def extract_endpoints(self, inputs):
         if self.batchnorm_folded:
             return self._extract_endpoints_folded(inputs)
         endpoints = {}
-        x = SF.bn_act(self._conv_stem(inputs), self._bn0, SF.ACT_SWISH)
-        prev_x = x
+        stem_bn = self._bn0 if self._stem_into_block0(inputs) else None          # block 0 then applies the stem's BatchNorm + swish inside its depthwise convolution
+        x = self._conv_stem(inputs) if stem_bn is not None else SF.bn_act(self._conv_stem(inputs), self._bn0, SF.ACT_SWISH)
+        prev_x = x                                                                # (never an endpoint: the first endpoint index is >= 1)
         nblk = len(self._blocks)
         for idx, block in enumerate(self._blocks):
             rate = self.drop_connect_rate * float(idx) / nblk if self.drop_connect_rate else None
-            x = block(x, drop_connect_rate=rate)
+            x = block(x, drop_connect_rate=rate, entry_bn=stem_bn) if idx == 0 and stem_bn is not None else block(x, drop_connect_rate=rate)
             if idx in self.endpoint_blk_indices:
                 endpoints['reduction_%d' % (len(endpoints) + 1)] = prev_x
             prev_x = x

@@ -1260,22 +1260,26 @@ def mbconv_mid(e, bn0, dw_weight, bn1, w1, b1, w2, b2, proj_weight):
                             bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var, float(bn1.momentum), float(bn1.eps), w1, b1, w2, b2, proj_weight)
 
 
-class _BNActDWConvS2(_Fn):
-    """The entry of a stride-2 MBConv block in training mode as ONE op: d = dwconv2d(_BNAct(e, bn0, swish), stride 2), one team launch per direction (segx_bn_dw_s2_fwd /
-    _bwd: 1 1/4 + 2 1/4 passes over the expanded tensor instead of 3 1/4 + 5 1/2).  Saved for backward: e and the two statistics; swish(bn0(e)) is neither written nor kept.
-    Only for shapes bn_dw_s2_ok accepts and one process: MBConvBlock.forward routes."""
+class _BNActDWConv(_Fn):
+    """BatchNorm0 + swish + the depthwise convolution behind it in training mode as ONE op: d = dwconv2d(_BNAct(e, bn0, swish), stride), one team launch per direction.
+    stride 2 (segx_bn_dw_s2_fwd / _bwd: the entry of a stride-2 MBConv block, 1 1/4 + 2 1/4 passes over the expanded tensor instead of 3 1/4 + 5 1/2) or stride 1 with 'same'
+    padding (segx_bn_dw_s1_fwd / _bwd: 2 + 3 passes instead of 4 + 6).  Saved for backward: e and the two statistics; swish(bn0(e)) is neither written nor kept.
+    Only for shapes bn_dw_s2_ok / bn_dw_s1_ok accept and one process: MBConvBlock.forward and EfficientNet.extract_endpoints route."""
 
     @staticmethod
-    def forward(ctx, e, w0, b0, rm0, rv0, mom0, eps0, wdw, pt, pl):
+    def forward(ctx, e, w0, b0, rm0, rv0, mom0, eps0, wdw, pt, pl, stride):
         L = segx.lib()
         e, wdw = _c(e), _c(wdw)
         if e.data_ptr() % 16:
             e = e.clone()
         B, C, H, W = e.shape
         k = wdw.shape[-1]
-        d, stats = _empty(e, B, C, H // 2, W // 2), _empty(e, 2, C)     # stats: mean0, var0
-        L.bn_dw_s2_fwd(e, w0, b0, rm0, rv0, wdw, d, stats[0], stats[1], _empty(e, L.bn_dw_s2_ws(B, C, H, W, False)), mom0, eps0, B, C, H, W, k, pt, pl)
-        ctx.cfg = (B, C, H, W, k, pt, pl, eps0, tuple(wdw.shape))
+        d, stats = _empty(e, B, C, H // stride, W // stride), _empty(e, 2, C)     # stats: mean0, var0
+        if stride == 2:
+            L.bn_dw_s2_fwd(e, w0, b0, rm0, rv0, wdw, d, stats[0], stats[1], _empty(e, L.bn_dw_s2_ws(B, C, H, W, False)), mom0, eps0, B, C, H, W, k, pt, pl)
+        else:
+            L.bn_dw_s1_fwd(e, w0, b0, rm0, rv0, wdw, d, stats[0], stats[1], _empty(e, L.bn_dw_s1_ws(B, C, H, W, False)), mom0, eps0, B, C, H, W, k, pt, pl)
+        ctx.cfg = (B, C, H, W, k, pt, pl, eps0, tuple(wdw.shape), stride)
         ctx.save_for_backward(e, stats, w0, b0, wdw)
         return d
 
@@ -1283,20 +1287,23 @@ class _BNActDWConvS2(_Fn):
     def backward(ctx, dd):
         L = segx.lib()
         e, stats, w0, b0, wdw = ctx.saved_tensors
-        B, C, H, W, k, pt, pl, eps0, wds = ctx.cfg
+        B, C, H, W, k, pt, pl, eps0, wds, stride = ctx.cfg
         dd = _c(dd)
         if dd.data_ptr() % 16:
             dd = dd.clone()
-        rows = L.bn_dw_s2_rows(B, H, W)
+        rows = L.bn_dw_s2_rows(B, H, W) if stride == 2 else L.bn_dw_s1_rows(B, H, W)
         de, g, part = torch.empty_like(e), _empty(e, 2, C), _empty(e, rows, C * k * k)      # g: dw0, db0
-        L.bn_dw_s2_bwd(dd, e, stats[0], stats[1], w0, b0, wdw, de, g[0], g[1], part, _empty(e, L.bn_dw_s2_ws(B, C, H, W, True)), eps0, B, C, H, W, k, pt, pl)
+        if stride == 2:
+            L.bn_dw_s2_bwd(dd, e, stats[0], stats[1], w0, b0, wdw, de, g[0], g[1], part, _empty(e, L.bn_dw_s2_ws(B, C, H, W, True)), eps0, B, C, H, W, k, pt, pl)
+        else:
+            L.bn_dw_s1_bwd(dd, e, stats[0], stats[1], w0, b0, wdw, de, g[0], g[1], part, _empty(e, L.bn_dw_s1_ws(B, C, H, W, True)), eps0, B, C, H, W, k, pt, pl)
         dwd = _empty(e, C * k * k)
         L.colsum(part, dwd, _empty(e, L.colreduce_ws(rows, C * k * k, 1)), rows, C * k * k)
-        return de, g[0], g[1], None, None, None, None, dwd.view(wds), None, None
+        return de, g[0], g[1], None, None, None, None, dwd.view(wds), None, None, None
 
 
 def bn_dw_s2_ok(e_shape, k, stride, pad):
-    """does the op below serve an expanded tensor of this shape and a k x k depthwise convolution of this stride and padding (left, right, top, bottom)?"""
+    """does the op above serve an expanded tensor of this shape and a k x k depthwise convolution of this stride and padding (left, right, top, bottom)?"""
     if len(e_shape) != 4:
         return False
     B, C, H, W = (int(v) for v in e_shape)
@@ -1307,12 +1314,32 @@ def bn_dw_s2_ok(e_shape, k, stride, pad):
 
 
 def bn_act_dwconv_s2(e, bn0, dw_weight, stride, static_pad):
-    """dwconv2d(bn_act(e, bn0, swish), dw_weight, stride, static_pad) -- see _BNActDWConvS2.  bn0 is in training mode and bn_dw_s2_ok(e.shape, k, stride, static_pad)
+    """dwconv2d(bn_act(e, bn0, swish), dw_weight, stride, static_pad) -- see _BNActDWConv.  bn0 is in training mode and bn_dw_s2_ok(e.shape, k, stride, static_pad)
     holds (the caller checks)."""
     assert int(stride) == 2
     _bn_tick(bn0)
-    return _BNActDWConvS2.apply(e, bn0.weight, bn0.bias, bn0.running_mean, bn0.running_var, float(bn0.momentum), float(bn0.eps), dw_weight,
-                                int(static_pad[2]), int(static_pad[0]))
+    return _BNActDWConv.apply(e, bn0.weight, bn0.bias, bn0.running_mean, bn0.running_var, float(bn0.momentum), float(bn0.eps), dw_weight,
+                              int(static_pad[2]), int(static_pad[0]), 2)
+
+
+def bn_dw_s1_ok(e_shape, k, stride, pad):
+    """the same for stride 1: symmetric 'same' padding (k - 1) / 2 on all four sides (left, right, top, bottom)"""
+    if len(e_shape) != 4:
+        return False
+    B, C, H, W = (int(v) for v in e_shape)
+    k = int(k)
+    if int(stride) != 1 or k % 2 != 1 or tuple(int(p) for p in pad) != ((k - 1) // 2,) * 4:
+        return False
+    return segx.lib().bn_dw_s1_ok(B, C, H, W, k, 1, (k - 1) // 2, (k - 1) // 2)
+
+
+def bn_act_dwconv_s1(e, bn0, dw_weight, stride, static_pad):
+    """dwconv2d(bn_act(e, bn0, swish), dw_weight, 1, static_pad) -- see _BNActDWConv.  bn0 is in training mode and bn_dw_s1_ok(e.shape, k, stride, static_pad) holds (the
+    caller checks)."""
+    assert int(stride) == 1
+    _bn_tick(bn0)
+    return _BNActDWConv.apply(e, bn0.weight, bn0.bias, bn0.running_mean, bn0.running_var, float(bn0.momentum), float(bn0.eps), dw_weight,
+                              int(static_pad[2]), int(static_pad[0]), 1)
 
 
 def conv1x1_per_sample(x, Wb, bias=None):

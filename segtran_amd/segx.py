@@ -438,6 +438,22 @@ class SegxLib:
     def bn_dw_s2_bwd(self, dD, E, mean, var, w0, b0, Wdw, dE, dw0, db0, part, ws, eps, B, C, H, W, k, pt, pl):
         self._call('segx_bn_dw_s2_bwd', dD, dD, E, mean, var, w0, b0, Wdw, dE, dw0, db0, part, ws, float(eps), B, C, H, W, k, pt, pl, part.shape[0], ws.numel())
 
+    def bn_dw_s1_ok(self, B, C, H, W, k, stride, pt, pl):
+        """does the stride-1 sibling (bn_dw_s1_fwd / bn_dw_s1_bwd: BatchNorm + swish + 'same' depthwise convolution) serve this tensor, filter size, stride and begin padding?"""
+        return bool(self.c.segx_bn_dw_s1_ok(B, C, H, W, k, stride, pt, pl))
+
+    def bn_dw_s1_ws(self, B, C, H, W, backward):
+        return int(self.c.segx_bn_dw_s1_ws_floats(B, C, H, W, 1 if backward else 0))
+
+    def bn_dw_s1_rows(self, B, H, W):
+        return int(self.c.segx_bn_dw_s1_rows(B, H, W))
+
+    def bn_dw_s1_fwd(self, E, w0, b0, rm, rv, Wdw, D, mean, var, ws, mom, eps, B, C, H, W, k, pt, pl):
+        self._call('segx_bn_dw_s1_fwd', E, E, w0, b0, rm, rv, Wdw, D, mean, var, ws, float(mom), float(eps), B, C, H, W, k, pt, pl, ws.numel())
+
+    def bn_dw_s1_bwd(self, dD, E, mean, var, w0, b0, Wdw, dE, dw0, db0, part, ws, eps, B, C, H, W, k, pt, pl):
+        self._call('segx_bn_dw_s1_bwd', dD, dD, E, mean, var, w0, b0, Wdw, dE, dw0, db0, part, ws, float(eps), B, C, H, W, k, pt, pl, part.shape[0], ws.numel())
+
     def mbconv_mid_ok(self, B, C, H, W, k):
         """does the channel-resident MBConv middle (mbconv_mid_fwd / mbconv_mid_bwd) serve this shape?"""
         return bool(self.c.segx_mbconv_mid_ok(B, C, H, W, k))
@@ -901,6 +917,8 @@ _SIGS = {
     'segx_team_status': 'i', 'segx_team_cap': '', 'segx_occupy': 'iifpp',
     'segx_bn_dw_s2_ok': 'iiiiiiii', 'segx_bn_dw_s2_ws_floats': 'iiiii', 'segx_bn_dw_s2_rows': 'iii',
     'segx_bn_dw_s2_fwd': 'p' * 10 + 'ff' + 'iiiiiii' + 'l' + 'p', 'segx_bn_dw_s2_bwd': 'p' * 12 + 'f' + 'iiiiiii' + 'll' + 'p',
+    'segx_bn_dw_s1_ok': 'iiiiiiii', 'segx_bn_dw_s1_ws_floats': 'iiiii', 'segx_bn_dw_s1_rows': 'iii',
+    'segx_bn_dw_s1_fwd': 'p' * 10 + 'ff' + 'iiiiiii' + 'l' + 'p', 'segx_bn_dw_s1_bwd': 'p' * 12 + 'f' + 'iiiiiii' + 'll' + 'p',
     'segx_mbconv_mid_ok': 'iiiii', 'segx_mbconv_mid_fwd': 'p' * 17 + 'ffff' + 'iiiii' + 'p', 'segx_mbconv_mid_bwd': 'p' * 19 + 'fff' + 'iiiii' + 'p',
     'segx_se_fwd2': 'pifpppppppppiiiip', 'segx_se_ws2_floats': 'iii', 'segx_se_bwd2': 'ppppppppfpppppppiiiip',
     'segx_bn_act_bwd_reduce': 'pppppppppiilfippffuup', 'segx_bn_act_bwd_apply': 'pppppppppiilfifppffuup',

@@ -4,14 +4,14 @@ import os, sys, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from segtran_amd import engine, functional as SF
-from segtran_amd.efficientnet.model import MBConvBlock
+from segtran_amd.efficientnet.model import MBConvBlock, EfficientNet
 from segtran_amd.networks.aj_i3d.aj_i3d import InceptionModule
 from segtran_amd.networks import segtran_shared as ss
 
 cfg, switch = sys.argv[1], sys.argv[2]
 steps = int(sys.argv[3]) if len(sys.argv) > 3 else 20
 owner, attr = switch.split('.')
-owner = {'InceptionModule': InceptionModule, 'MBConvBlock': MBConvBlock, 'CrossAttFeatTrans': ss.CrossAttFeatTrans, '_ModesAggr': SF._ModesAggr, '_ConvStem2d': SF._ConvStem2d, '_BGemm': SF._BGemm, '_DWConv': SF._DWConv, '_PreNorm': SF._PreNorm, 'SF': SF}[owner]
+owner = {'InceptionModule': InceptionModule, 'MBConvBlock': MBConvBlock, 'EfficientNet': EfficientNet, 'CrossAttFeatTrans': ss.CrossAttFeatTrans, '_ModesAggr': SF._ModesAggr, '_ConvStem2d': SF._ConvStem2d, '_BGemm': SF._BGemm, '_DWConv': SF._DWConv, '_PreNorm': SF._PreNorm, 'SF': SF}[owner]
 dev = torch.device('cuda', 0)
 c = engine.CONFIGS[cfg]
 batch = int(os.environ.get('SEGX_AB_BATCH', c['bs']))
