@@ -699,6 +699,21 @@ int segx_window_gather(const float* image, const int* origins, const int* origin
  *   geom (int32[15]) = {d, h, w (scores), D, H, W (window), CD, CH, CW (padded canvas), pz, py, px (left pads), ID, IH, IW (image)} */
 int segx_window_merge(const float* scores, const int* origins, const int* origins_host, float* soft, float* hard, int nwin, int B, int C,
                       const int* geom, int mode, float T, void* stream);
+/* Flip test-time augmentation of that sequence.  A view is a set of flipped image axes, as a mask: bit 0 = the ID axis, bit 1 = IH, bit 2 = IW.
+ * views: DEVICE int32 [V] masks in the caller's order; views_host: the same in HOST memory -- the refusals are decided on it: 1 <= V <= SEGX_MAX_VIEWS, no mask
+ * twice, no bit outside the three, no bit of an axis the call does not have (image, window and canvas extent all 1: the depth axis of a 2-D call).
+ * segx_window_gather_views: out[(v * nwin + k) * B + b][c] = padded_v[b][c][window k], where padded_v is the image FLIPPED along view v's axes and then zero-padded
+ *   as in segx_window_gather (pads and origins are those of the un-flipped geometry: the shape is the same).  Read from the un-flipped image through the mirrored
+ *   coordinate; no flipped image exists.  out [V * nwin * B, C, D, H, W]: view-major, then window, then image; geom as segx_window_gather. */
+#define SEGX_MAX_VIEWS 8
+int segx_window_gather_views(const float* image, const int* origins, const int* origins_host, const int* views, const int* views_host, float* out,
+                             int nwin, int V, int B, int C, const int* geom, void* stream);
+/* segx_window_merge_views: with soft_v = the soft map segx_window_merge writes for view v's scores (rows (v * nwin + k) * B + b; in mode 1 the consistent one),
+ *   flipped back along view v's axes,  soft = (((soft_0 + soft_1) + soft_2) + ...) / (float)V  in fp32, adds in the views' order, one division;  hard as
+ *   segx_harden_segmap(soft) in the same mode.  Bit for bit that composition; no per-view map exists.  scores [V * nwin * B, C, d, h, w]; soft, hard
+ *   [B, C, ID, IH, IW]; geom, mode, T as segx_window_merge. */
+int segx_window_merge_views(const float* scores, const int* origins, const int* origins_host, const int* views, const int* views_host, float* soft,
+                            float* hard, int nwin, int V, int B, int C, const int* geom, int mode, float T, void* stream);
 /* calc_dice sums (test_util2d.py:233-240) per plane: part [chunks][planes][3] = {sum pred*gt, sum pred^2, sum gt^2},
  * chunks*planes*3 = segx_dice_ws_floats(planes, S); reduce over chunks with segx_colsum */
 int64_t segx_dice_ws_floats(int64_t planes, int64_t S);

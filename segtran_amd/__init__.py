@@ -17,6 +17,7 @@ def inference_precision(name):
 
 
 def __getattr__(name):
+    # all three take tta= (flip test-time augmentation inside the captured gather and merge launches: DESIGN.md 5z)
     if name == 'GraphedSlidingWindow':          # infer2d.GraphedSlidingWindow: the whole sliding-window evaluation of one image shape as one replayable hipGraph
         from .infer2d import GraphedSlidingWindow
         return GraphedSlidingWindow

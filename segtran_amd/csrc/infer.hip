@@ -111,6 +111,82 @@ __global__ __launch_bounds__(256) void window_merge_kernel(const float* __restri
     }
 }
 
+// ---- flip test-time augmentation: a view is a set of flipped image axes (bit 0 = the depth axis ID, bit 1 = IH, bit 2 = IW); views: int32 [V] masks ----
+// the coordinate of the flipped image's cell i along an axis of extent n: the mirror when the view flips the axis.  Its own inverse.
+__device__ __forceinline__ int view_coord(int i, int n, bool flip) { return flip ? n - 1 - i : i; }
+
+// out[(v * nwin + k) * B + b][c] = the crop of window k from the zero-padded image FLIPPED along view v's axes (the flip is of the un-padded image, so pads and
+// origins are the un-flipped geometry's); read from the un-flipped image through the mirrored coordinate: neither the flipped image nor its canvas exists.
+// window_gather_kernel with one more digit in the index; the bounds check is against the image.
+__global__ __launch_bounds__(256) void window_gather_views_kernel(const float* __restrict__ image, const int* __restrict__ origins, const int* __restrict__ views,
+                                                                  float* __restrict__ out, int nwin, int V, int B, int C, int D, int H, int W, Sliding sl) {
+    const int64_t wsz = (int64_t)D * H * W, total = (int64_t)V * nwin * B * C * wsz;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        const int64_t pl = idx / wsz; int64_t r = idx - pl * wsz;            // pl = ((v * nwin + k) * B + b) * C + c
+        const int z = (int)(r / ((int64_t)H * W)); r -= (int64_t)z * H * W;
+        const int y = (int)(r / W), x = (int)(r - (int64_t)y * W);
+        const int c = (int)(pl % C), vkb = (int)(pl / C), b = vkb % B, vk = vkb / B, k = vk % nwin, m = views[vk / nwin];
+        const int fz = origins[3 * k] - sl.pz + z, fy = origins[3 * k + 1] - sl.py + y, fx = origins[3 * k + 2] - sl.px + x;      // flipped-image coordinates
+        const bool in = (unsigned)fz < (unsigned)sl.ID && (unsigned)fy < (unsigned)sl.IH && (unsigned)fx < (unsigned)sl.IW;
+        const int iz = view_coord(fz, sl.ID, m & 1), iy = view_coord(fy, sl.IH, m & 2), ix = view_coord(fx, sl.IW, m & 4);      // inside the image iff (fz, fy, fx) is
+        out[idx] = in ? image[((((int64_t)b * C + c) * sl.ID + iz) * sl.IH + iy) * sl.IW + ix] : 0.0f;
+    }
+}
+
+// soft[b][c][cell] = (((soft_0 + soft_1) + soft_2) + ...) / V, then harden_cell, where soft_v[cell] is what window_merge_kernel writes as soft for the scores of view v
+// (rows (v * nwin + k) * B + b) at the MIRRORED cell, i.e. view v's soft map flipped back: the loop of window_merge_kernel (ascending k, window_prob, mean_prob and,
+// in mode 1, the consistency rule its harden_cell applies before it writes soft) once per view, in the views' order, into a register accumulator per class.
+// A view's term is a quotient and the accumulation adds quotients: no product feeds an add, so there is nothing a contraction could fuse.
+template <int MAXC, bool EXACT>
+__global__ __launch_bounds__(256) void window_merge_views_kernel(const float* __restrict__ scores, const int* __restrict__ origins, const int* __restrict__ views,
+                                                                 float* __restrict__ soft, float* __restrict__ hard, int nwin, int V, int B, int C_, InterpDims q,
+                                                                 Sliding sl, int mode, float T) {
+    const int C = EXACT ? MAXC : C_;
+    const int64_t isz = (int64_t)sl.ID * sl.IH * sl.IW, ssz = (int64_t)q.d * q.h * q.w, total = (int64_t)B * isz;
+    const bool same = q.d == q.D && q.h == q.H && q.w == q.W;
+    const float fV = (float)V;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        const int64_t b = idx / isz, cell = idx - b * isz; int64_t r = cell;
+        const int z = (int)(r / ((int64_t)sl.IH * sl.IW)); r -= (int64_t)z * sl.IH * sl.IW;
+        const int y = (int)(r / sl.IW), x = (int)(r - (int64_t)y * sl.IW);
+        float a[MAXC];
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c) a[c] = 0.0f;
+        for (int v = 0; v < V; ++v) {
+            const int m = views[v];                                           // uniform: v is the same in every lane
+            const int fz = view_coord(z, sl.ID, m & 1) + sl.pz, fy = view_coord(y, sl.IH, m & 2) + sl.py, fx = view_coord(x, sl.IW, m & 4) + sl.px;
+            float p[MAXC], n = 0.0f;
+#pragma unroll
+            for (int c = 0; c < MAXC; ++c) p[c] = 0.0f;
+            for (int k = 0; k < nwin; ++k) {
+                const int wz = fz - origins[3 * k], wy = fy - origins[3 * k + 1], wx = fx - origins[3 * k + 2];
+                if ((unsigned)wz >= (unsigned)q.D || (unsigned)wy >= (unsigned)q.H || (unsigned)wx >= (unsigned)q.W) continue;
+#pragma unroll
+                for (int c = 0; c < MAXC; ++c)
+                    if (c < C) p[c] += window_prob(scores + ((((int64_t)v * nwin + k) * B + b) * C + c) * ssz, q, same, wz, wy, wx);
+                n += 1.0f;
+            }
+#pragma unroll
+            for (int c = 0; c < MAXC; ++c)
+                if (c < C) p[c] = mean_prob(p[c], n);
+            if constexpr (MAXC >= 4) {
+                if (mode == 1) {                                              // the soft map of a view is the consistent one, as harden_cell writes it (C == 4)
+                    const float et = p[1], wt = p[2], tc = p[3];
+                    p[2] = fmaxf(fmaxf(et, wt), tc);
+                    p[3] = fmaxf(et, tc);
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < MAXC; ++c)
+                if (c < C) a[c] = v == 0 ? p[c] : a[c] + p[c];                // the sum starts AT soft_0
+        }
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c)
+            if (c < C) a[c] = a[c] / fV;
+        harden_cell<MAXC>(a, C, mode, T, soft + (b * C) * isz + cell, hard + (b * C) * isz + cell, isz);
+    }
+}
+
 // per (plane, chunk): sum pred*gt, sum pred^2, sum gt^2  ->  part[chunk][plane][3]  (summed over chunks by segx_colsum)
 __global__ __launch_bounds__(256) void dice_sums_kernel(const float* __restrict__ pred, const float* __restrict__ gt, float* __restrict__ part,
                                                         int64_t S) {
@@ -198,6 +274,59 @@ extern "C" int segx_window_merge(const float* scores, const int* origins, const 
     else SEGX_MERGE(SEGX_MAX_CLASSES, false);
 #undef SEGX_MERGE
     return check_launch("segx_window_merge");
+}
+// the host copy of the view table: 1..SEGX_MAX_VIEWS masks of the three axis bits, no mask twice, no bit of an axis the call does not have (image, window and canvas
+// extent all 1: the depth axis of a 2-D call)
+static bool views_ok(const int* m, int V, int D, int H, int W, const Sliding& sl) {
+    if (V < 1 || V > SEGX_MAX_VIEWS) return false;
+    const int absent = (D == 1 && sl.CD == 1 && sl.ID == 1 ? 1 : 0) | (H == 1 && sl.CH == 1 && sl.IH == 1 ? 2 : 0) | (W == 1 && sl.CW == 1 && sl.IW == 1 ? 4 : 0);
+    for (int v = 0; v < V; ++v) {
+        if (m[v] < 0 || m[v] > 7 || (m[v] & absent)) return false;
+        for (int u = 0; u < v; ++u)
+            if (m[u] == m[v]) return false;
+    }
+    return true;
+}
+/* segx_window_gather for V flipped views in one launch: out [V * nwin * B, C, D, H, W] (view-major, then window, then image);  views: device int32 [V] flip masks
+ * (bit 0 = ID axis, bit 1 = IH, bit 2 = IW), views_host: the same in host memory (the refusals are decided on it);  the rest as segx_window_gather */
+extern "C" int segx_window_gather_views(const float* image, const int* origins, const int* origins_host, const int* views, const int* views_host, float* out,
+                                        int nwin, int V, int B, int C, const int* geom, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(image && origins && origins_host && views && views_host && out && geom, "segx_window_gather_views: null pointer");
+    SEGX_REQUIRE(nwin > 0 && B > 0 && C > 0, "segx_window_gather_views: nwin, B and C must be positive");
+    const Sliding sl{geom[9], geom[10], geom[11], geom[3], geom[4], geom[5], geom[0], geom[1], geom[2]};
+    const int D = geom[6], H = geom[7], W = geom[8];
+    SEGX_REQUIRE(D > 0 && H > 0 && W > 0, "segx_window_gather_views: bad window size");
+    SEGX_REQUIRE(sliding_ok(origins_host, nwin, D, H, W, sl), "segx_window_gather_views: window outside the padded canvas");
+    SEGX_REQUIRE(views_ok(views_host, V, D, H, W, sl), "segx_window_gather_views: 1..%d distinct views, each a mask of the call's spatial axes", SEGX_MAX_VIEWS);
+    const int64_t total = (int64_t)V * nwin * B * C * D * H * W;
+    hipLaunchKernelGGL(window_gather_views_kernel, dim3((unsigned)i64min(65536, (total + 255) / 256)), dim3(256), 0, stream, image, origins, views, out, nwin, V, B, C,
+                       D, H, W, sl);
+    return check_launch("segx_window_gather_views");
+}
+/* segx_window_merge over V views: scores [V * nwin * B, C, d, h, w] (segx_window_gather_views' layout) -> soft, hard [B, C, ID, IH, IW];  views / views_host as
+ * segx_window_gather_views;  the rest as segx_window_merge */
+extern "C" int segx_window_merge_views(const float* scores, const int* origins, const int* origins_host, const int* views, const int* views_host, float* soft,
+                                       float* hard, int nwin, int V, int B, int C, const int* geom, int mode, float T, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(scores && origins && origins_host && views && views_host && soft && hard && geom, "segx_window_merge_views: null pointer");
+    SEGX_REQUIRE(nwin > 0 && B > 0 && C >= 2 && C <= SEGX_MAX_CLASSES, "segx_window_merge_views: nwin and B must be positive, 2 <= C <= %d", SEGX_MAX_CLASSES);
+    SEGX_REQUIRE(mode == 0 || (mode == 1 && C == 4), "segx_window_merge_views: mode is 0, or 1 with C == 4");
+    SEGX_REQUIRE(geom[0] > 0 && geom[1] > 0 && geom[2] > 0 && geom[3] > 0 && geom[4] > 0 && geom[5] > 0, "segx_window_merge_views: bad scores / window size");
+    const InterpDims q = make_dims(geom[0], geom[1], geom[2], geom[3], geom[4], geom[5]);
+    const Sliding sl{geom[6], geom[7], geom[8], geom[9], geom[10], geom[11], geom[12], geom[13], geom[14]};
+    SEGX_REQUIRE(sliding_ok(origins_host, nwin, q.D, q.H, q.W, sl), "segx_window_merge_views: window outside the padded canvas");
+    SEGX_REQUIRE(views_ok(views_host, V, q.D, q.H, q.W, sl), "segx_window_merge_views: 1..%d distinct views, each a mask of the call's spatial axes", SEGX_MAX_VIEWS);
+    const int64_t total = (int64_t)B * sl.ID * sl.IH * sl.IW;
+    const dim3 grid((unsigned)i64min(65536, (total + 255) / 256));
+    const dim3 block(256);
+#define SEGX_MERGE(MAXC, EXACT) \
+    hipLaunchKernelGGL((window_merge_views_kernel<MAXC, EXACT>), grid, block, 0, stream, scores, origins, views, soft, hard, nwin, V, B, C, q, sl, mode, T)
+    if (C == 2) SEGX_MERGE(2, true);
+    else if (C == 3) SEGX_MERGE(3, true);
+    else if (C == 4) SEGX_MERGE(4, true);
+    else if (C <= 8) SEGX_MERGE(8, false);
+    else SEGX_MERGE(SEGX_MAX_CLASSES, false);
+#undef SEGX_MERGE
+    return check_launch("segx_window_merge_views");
 }
 extern "C" int64_t segx_dice_ws_floats(int64_t planes, int64_t S) { return 3 * planes * i64max(1, i64min(64, (S + 4095) / 4096)); }
 /* part: segx_dice_ws_floats(planes, S) floats laid out [chunks][planes][3]; sums[planes][3] = segx_colsum over the chunks */

@@ -2576,6 +2576,52 @@ class WindowTable:
         self.dev = torch.tensor(flat, dtype=torch.int32, device=device).view(self.nwin, 3)
 
 
+MAX_VIEWS = 8                                    # SEGX_MAX_VIEWS of include/segx.h
+
+
+def check_views(views, nd, what='tta'):
+    """The views of a flip test-time augmentation as a tuple of sorted axis tuples, in the given order.  A view is a tuple of distinct spatial axes to flip
+    (0 = the first spatial axis of the image; () is the identity and has to be listed to be used).  ValueError for an empty sequence, more than MAX_VIEWS views, an
+    axis outside 0..nd-1, an axis twice in a view, or the same set of axes twice."""
+    try:
+        vs = [tuple(int(a) for a in v) for v in views]
+    except TypeError:
+        raise ValueError('%s: a sequence of views, each a tuple of axis indices, not %r' % (what, views))
+    if not 1 <= len(vs) <= MAX_VIEWS:
+        raise ValueError('%s: between 1 and %d views, not %d' % (what, MAX_VIEWS, len(vs)))
+    for v in vs:
+        if any(a < 0 or a >= nd for a in v):
+            raise ValueError('%s: view %r names an axis outside 0..%d' % (what, v, nd - 1))
+        if len(set(v)) != len(v):
+            raise ValueError('%s: view %r names an axis twice' % (what, v))
+    if len({frozenset(v) for v in vs}) != len(vs):
+        raise ValueError('%s: the same view twice in %r' % (what, tuple(vs)))
+    return tuple(tuple(sorted(v)) for v in vs)
+
+
+class ViewTable:
+    """The views of one flip test-time augmentation for images of `nd` spatial axes (check_views), as the flip masks the kernels read: bit (3 - nd + a) for spatial
+    axis a, i.e. bit 0 = the depth axis of the kernels' [B, C, ID, IH, IW] frame.  Holds the device table (int32 [V]) and the host copy the refusals are decided on;
+    like WindowTable it is built once, before a capture."""
+
+    def __init__(self, views, nd, device):
+        if nd not in (2, 3):
+            raise ValueError('ViewTable: 2 or 3 spatial axes, not %r' % (nd,))
+        self.nd, self.views = nd, check_views(views, nd, 'ViewTable')
+        self.V = len(self.views)
+        self.masks = tuple(sum(1 << (3 - nd + a) for a in v) for v in self.views)
+        self.host = (segx.c_i * self.V)(*self.masks)
+        self.dev = torch.tensor(self.masks, dtype=torch.int32, device=device)
+
+
+def _view_table(what, views, nd, device):
+    if isinstance(views, ViewTable):
+        if views.nd != nd:
+            raise TypeError('%s: `views` is a ViewTable of %d-D views' % (what, nd))
+        return views
+    return ViewTable(views, nd, device)
+
+
 def _window_geometry(what, table, nd, image_size, window, pads, canvas):
     if not isinstance(table, WindowTable) or table.nd != nd:
         raise TypeError('%s: `table` is a WindowTable of %d-D origins' % (what, nd))
@@ -2588,42 +2634,60 @@ def _window_geometry(what, table, nd, image_size, window, pads, canvas):
     return one + image_size, one + window, zero + pads, one + canvas
 
 
-def window_gather(image, table, window, patch_size=None, pads=None, canvas=None):
+def window_gather(image, table, window, patch_size=None, pads=None, canvas=None, views=None):
     """The network's input for every window: image [B, C, *spatial] -> [nwin * B, C, *patch_size], window-major then image; entry k * B + b is
     interp_linear(padded[b, :, window k], patch_size) bit for bit (the plain crop when patch_size == window), where `padded` is the image zero-padded to `canvas`
     with the left pads `pads` -- it never exists in memory.  One launch (segx_window_gather) for the crops of all windows; when the patch size differs, ONE
     interp_linear over the stacked crops follows (per-plane arithmetic: the bits of the per-window calls).  table: WindowTable; canvas defaults to
-    max(image + pads, window).  Forward only."""
+    max(image + pads, window).  Forward only.
+    views (a ViewTable, or a sequence of views -- inside a capture only the former): the crops of every view of a flip test-time augmentation in the same one launch
+    (segx_window_gather_views): [V * nwin * B, C, *patch_size], view-major, then window, then image; view v's rows are window_gather(image.flip(axes of view v))
+    bit for bit.  The flip is index arithmetic: no flipped image exists."""
     _no_grad_operands('window_gather', image)
     L = segx.lib()
     image = _c(image.detach())
     nd = image.dim() - 2
     B, C = image.shape[:2]
     i3, w3, p3, c3 = _window_geometry('window_gather', table, nd, image.shape[2:], window, pads, canvas)
-    out = _empty(image, table.nwin * B, C, *w3[3 - nd:])
-    L.window_gather(image, table.dev, table.host, out, table.nwin, B, C, i3 + p3 + w3 + c3)
+    if views is None:
+        out = _empty(image, table.nwin * B, C, *w3[3 - nd:])
+        L.window_gather(image, table.dev, table.host, out, table.nwin, B, C, i3 + p3 + w3 + c3)
+    else:
+        vt = _view_table('window_gather', views, nd, image.device)
+        out = _empty(image, vt.V * table.nwin * B, C, *w3[3 - nd:])
+        L.window_gather_views(image, table.dev, table.host, vt.dev, vt.host, out, table.nwin, vt.V, B, C, i3 + p3 + w3 + c3)
     if patch_size is not None and tuple(int(v) for v in patch_size) != w3[3 - nd:]:
         out = interp_linear(out, patch_size)
     return out
 
 
-def window_merge(scores, table, window, image_size, pads=None, canvas=None, mode=0, T=0.5):
+def window_merge(scores, table, window, image_size, pads=None, canvas=None, mode=0, T=0.5, views=None):
     """(soft, hard) [B, C, *image_size] of the whole sliding-window evaluation in one launch (segx_window_merge): scores [nwin * B, C, *s] (laid out as
     window_gather's output).  Bit for bit what window_accum per window (in the table's order, on zeroed acc / cnt) followed by harden_segmap(mode, T) leaves in
     the un-padded region of the canvas; acc and cnt never exist.  A cell that no window of a hand-built table covers is 0 / 0 = NaN, as on the eager path
-    (infer2d.sliding_windows never leaves one).  Forward only."""
+    (infer2d.sliding_windows never leaves one).  Forward only.
+    views (as window_gather): scores [V * nwin * B, C, *s] hold the views of a flip test-time augmentation; one launch (segx_window_merge_views) forms
+    soft = (((soft_0 + soft_1) + soft_2) + ...) / float(V) -- soft_v = the soft map of view v's rows flipped back along its axes, fp32 adds in the views' order, one
+    division -- and hardens it (mode, T): bit for bit the composition of window_merge per view, torch.flip, the adds, the division and harden_segmap."""
     _no_grad_operands('window_merge', scores)
     L = segx.lib()
     scores = _c(scores.detach())
     nd = scores.dim() - 2
     C = scores.shape[1]
-    if scores.shape[0] % table.nwin:
-        raise ValueError('window_merge: scores holds %d samples, no multiple of the %d windows' % (scores.shape[0], table.nwin))
-    B = scores.shape[0] // table.nwin
+    vt = None if views is None else _view_table('window_merge', views, nd, scores.device)
+    rows = table.nwin * (1 if vt is None else vt.V)
+    if scores.shape[0] % rows:
+        raise ValueError('window_merge: scores holds %d samples, no multiple of the %d windows%s' %
+                         (scores.shape[0], table.nwin, '' if vt is None else ' x %d views' % vt.V))
+    B = scores.shape[0] // rows
     i3, w3, p3, c3 = _window_geometry('window_merge', table, nd, image_size, window, pads, canvas)
     soft = _empty(scores, B, C, *i3[3 - nd:])
     hard = torch.empty_like(soft)
-    L.window_merge(scores, table.dev, table.host, soft, hard, table.nwin, B, C, (1,) * (3 - nd) + tuple(scores.shape[2:]) + w3 + c3 + p3 + i3, mode, T)
+    geom = (1,) * (3 - nd) + tuple(scores.shape[2:]) + w3 + c3 + p3 + i3
+    if vt is None:
+        L.window_merge(scores, table.dev, table.host, soft, hard, table.nwin, B, C, geom, mode, T)
+    else:
+        L.window_merge_views(scores, table.dev, table.host, vt.dev, vt.host, soft, hard, table.nwin, vt.V, B, C, geom, mode, T)
     return soft, hard
 
 

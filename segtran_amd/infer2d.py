@@ -15,7 +15,7 @@ from . import functional as SF
 from . import test_util2d as _T2
 from .test_util2d import calc_dice          # noqa: F401  (same module surface)
 from .dataloaders.datasets2d import fundus_inv_map_mask, harden_segmap2d, polyp_inv_map_mask
-from .infer_common import PRECISIONS, GraphedEvaluation, _precision, folded, inference_precision, run_chunks      # noqa: F401  (same module surface)
+from .infer_common import PRECISIONS, GraphedEvaluation, _precision, composed_tta, folded, inference_precision, run_chunks, view_chunks      # noqa: F401  (same module surface)
 
 
 def _folded(net, fold_bn):
@@ -54,8 +54,9 @@ def max_stacked_samples(net):
 class _Plan:
     """what the fused sequence needs beyond the image: the window table on the device and the geometry"""
 
-    def __init__(self, net, image_shape, orig_input_size, patch_size, stride, device, window_batch):
+    def __init__(self, net, image_shape, orig_input_size, patch_size, stride, device, window_batch, tta=None):
         self.shape = tuple(int(v) for v in image_shape)
+        self.views = None if tta is None else SF.ViewTable(tta, 2, device)          # refuses a bad tta before anything is launched
         self.window, self.patch = tuple(int(v) for v in orig_input_size), tuple(int(v) for v in patch_size)
         self.pads, self.canvas, origins = sliding_windows(self.shape[2], self.shape[3], self.window, stride)
         self.table = SF.WindowTable(origins, device)
@@ -68,26 +69,42 @@ class _Plan:
     def run(self, net, image_batch):
         """gather -> net() on chunks of window_batch windows (window_batch * B samples each) -> merge; the caller holds torch.no_grad()"""
         B, nwin = self.shape[0], self.table.nwin
-        patches = SF.window_gather(image_batch, self.table, self.window, self.patch, self.pads, self.canvas)
-        scores = run_chunks(net, patches, [(k * B, min(k + self.window_batch, nwin) * B) for k in range(0, nwin, self.window_batch)])
-        preds_soft, preds_hard = SF.window_merge(scores, self.table, self.window, self.shape[2:], self.pads, self.canvas, mode=0)
+        chunks = [(k * B, min(k + self.window_batch, nwin) * B) for k in range(0, nwin, self.window_batch)]
+        if self.views is not None:                                                  # the views are more rows of the stacked batch; a chunk never mixes two
+            chunks = view_chunks(chunks, nwin * B, self.views.V)
+        patches = SF.window_gather(image_batch, self.table, self.window, self.patch, self.pads, self.canvas, views=self.views)
+        scores = run_chunks(net, patches, chunks)
+        preds_soft, preds_hard = SF.window_merge(scores, self.table, self.window, self.shape[2:], self.pads, self.canvas, mode=0, views=self.views)
         return preds_hard.to(torch.int32), preds_soft
 
 
 def test_single_batch(net, image_batch, orig_input_size, patch_size, stride, task_name, num_classes, model_type='segtran', fold_bn=False, fused=False,
-                      window_batch=None, precision='fp32'):
+                      window_batch=None, precision='fp32', tta=None):
     """test_util2d.test_single_batch; fold_bn: with the backbone's BatchNorm layers folded into its convolutions for this call.
     fused: one window_gather launch, net() on chunks of `window_batch` windows (window_batch * B samples each; default: all windows in one call, or the largest chunks
     max_stacked_samples(net) allows), one
     window_merge launch -- no canvas copy, no per-window accumulate pass.  With window_batch=1 the forwards are the eager path's, and so are the results, bit
     for bit; stacked windows change the GEMMs' shapes, hence the summation order inside the network.
-    precision: 'fp32' (default) or 'bf16x3' -- the forwards run inside inference_precision(precision)."""
+    precision: 'fp32' (default) or 'bf16x3' -- the forwards run inside inference_precision(precision).
+    tta: None (default: exactly the call without it) or a sequence of up to 8 views for flip test-time augmentation.  A view is a tuple of distinct
+    image axes to flip, 0 = H, 1 = W -- e.g. ((), (1,), (0,), (0, 1)); the identity () has to be listed to be used.  With soft_v = this call's preds_soft for the
+    image flipped along view v's axes (the un-padded image is flipped: pads, origins and clamping are those of the un-flipped shape), flipped back,
+    preds_soft = (((soft_0 + soft_1) + soft_2) + ...) / float(V) in fp32 and preds_hard is its hardening.  fused=False runs that as a host loop
+    (infer_common.composed_tta); fused=True runs one gather launch for all views, net() on the chunks of each view in turn (a chunk never mixes views: with
+    window_batch=1 the forwards are the host loop's and the results equal it bit for bit) and one merge launch -- no flipped image, no per-view soft map, no ATen
+    add or divide.  The gather and the score buffer hold V times what they hold without tta.  A bad tta (empty, more than 8 views, an axis outside 0..1 or twice in
+    a view, the same set of axes twice) raises ValueError before anything is launched."""
     if fused and model_type not in ('segtran',):
         raise NotImplementedError("model_type '%s': only segtran is built" % model_type)
+    views = None if tta is None else SF.check_views(tta, 2)
     with _precision(precision), _folded(net, fold_bn):
         if not fused:
-            return _T2.test_single_batch(net, image_batch, orig_input_size, patch_size, stride, task_name, num_classes, model_type)
-        plan = _Plan(net, image_batch.shape, orig_input_size, patch_size, stride, image_batch.device, window_batch)
+            if views is None:
+                return _T2.test_single_batch(net, image_batch, orig_input_size, patch_size, stride, task_name, num_classes, model_type)
+            hard, soft = composed_tta(lambda x: _T2.test_single_batch(net, x, orig_input_size, patch_size, stride, task_name, num_classes, model_type),
+                                      image_batch, views, 2, 0)
+            return hard.to(torch.int32), soft
+        plan = _Plan(net, image_batch.shape, orig_input_size, patch_size, stride, image_batch.device, window_batch, views)
         with torch.no_grad():
             return plan.run(net, image_batch)
 
@@ -239,7 +256,7 @@ def calc_batch_metric_onehot(preds_soft, gt_index, num_classes):
 
 
 def test_all_cases(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, mask_prepred_mapping_func=None, fold_bn=False, fused=False,
-                   window_batch=None, precision='fp32', do_calc_vcdr_error=False, gt_is_index=False, device_tail=False, gt_map='nhot'):
+                   window_batch=None, precision='fp32', do_calc_vcdr_error=False, gt_is_index=False, device_tail=False, gt_map='nhot', tta=None):
     """test_util2d.test_all_cases; fold_bn: ONE fold for all the batches; fused / window_batch / precision: as test_single_batch; do_calc_vcdr_error: the vCDR
     error as one more entry (both returned vectors then have num_classes entries, as in the reference).
     gt_is_index (one-hot tasks: oct): the masks are index masks [B, H, W] / [B, 1, H, W] and stay so -- no mapping function, no one-hot mask, no hardened map; each
@@ -248,24 +265,27 @@ def test_all_cases(net, batches, task_name, num_classes, orig_input_size, patch_
     device_tail (n-hot tasks: fundus, polyp): the same for n-hot masks -- ONE tail launch per batch (SF.nhot_case_tail) forms the Dice rows and, with
     do_calc_vcdr_error, the vCDR-error column on the device; they are read ONCE after the last batch and summed in the default path's order, so (mean, count)
     equals the default's.  gt_map ('fundus', 'fundus_exclusive', 'polyp'; needs device_tail): the batches hold the RAW uint8 masks, mapped inside the tail launch
-    -- the n-hot mask never exists; it excludes mask_prepred_mapping_func."""
+    -- the n-hot mask never exists; it excludes mask_prepred_mapping_func.
+    tta: flip test-time augmentation of every batch's evaluation, as test_single_batch takes it, in every form above."""
+    views = None if tta is None else SF.check_views(tta, 2)
     if gt_is_index and (do_calc_vcdr_error or mask_prepred_mapping_func is not None or device_tail):
         raise ValueError('test_all_cases: gt_is_index takes the index masks as they are (no mask_prepred_mapping_func, no device_tail) and has no vCDR column')
     if gt_map != 'nhot' and (not device_tail or mask_prepred_mapping_func is not None):
         raise ValueError('test_all_cases: gt_map=%r reads the raw masks in the tail launch: it needs device_tail=True and excludes mask_prepred_mapping_func' % (gt_map,))
     with _precision(precision), _folded(net, fold_bn):
         if gt_is_index:
-            return _test_all_cases_index(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, fused, window_batch)
+            return _test_all_cases_index(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, fused, window_batch, views)
         if device_tail:
             return _test_all_cases_tail(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, mask_prepred_mapping_func, fused, window_batch,
-                                        do_calc_vcdr_error, gt_map)
-        if not fused and not do_calc_vcdr_error:
+                                        do_calc_vcdr_error, gt_map, views)
+        if not fused and not do_calc_vcdr_error and views is None:
             return _T2.test_all_cases(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, mask_prepred_mapping_func)
         np = _T2.np
         total, count = (np.zeros(num_classes), np.zeros(num_classes)) if do_calc_vcdr_error else (np.zeros(num_classes - 1), 0)
         for image_batch, mask_batch in batches:
             gt = mask_prepred_mapping_func(mask_batch) if mask_prepred_mapping_func else mask_batch
-            _, preds_soft = test_single_batch(net, image_batch, orig_input_size, patch_size, stride, task_name, num_classes, fused=fused, window_batch=window_batch)
+            _, preds_soft = test_single_batch(net, image_batch, orig_input_size, patch_size, stride, task_name, num_classes, fused=fused, window_batch=window_batch,
+                                              tta=views)
             m = calc_batch_metric(preds_soft, gt, num_classes, do_calc_vcdr_error=do_calc_vcdr_error)
             total += m.sum(axis=0); count += len(m)
         return total / np.maximum(count, 1), count
@@ -284,22 +304,24 @@ def _sum_tables(rows, ncols, count):
 
 
 def _test_all_cases_tail(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, mask_prepred_mapping_func, fused, window_batch,
-                         do_calc_vcdr_error, gt_map):
+                         do_calc_vcdr_error, gt_map, tta=None):
     rows = []
     for image_batch, mask_batch in batches:
         gt = mask_prepred_mapping_func(mask_batch) if mask_prepred_mapping_func else mask_batch
-        _, preds_soft = test_single_batch(net, image_batch, orig_input_size, patch_size, stride, task_name, num_classes, fused=fused, window_batch=window_batch)
+        _, preds_soft = test_single_batch(net, image_batch, orig_input_size, patch_size, stride, task_name, num_classes, fused=fused, window_batch=window_batch,
+                                          tta=tta)
         with torch.no_grad():
             rows.append(_nhot_metric_rows(preds_soft, gt, num_classes, do_calc_vcdr_error, gt_map))
     np = _T2.np
     return _sum_tables(rows, num_classes, np.zeros(num_classes)) if do_calc_vcdr_error else _sum_tables(rows, num_classes - 1, 0)
 
 
-def _test_all_cases_index(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, fused, window_batch):
+def _test_all_cases_index(net, batches, task_name, num_classes, orig_input_size, patch_size, stride, fused, window_batch, tta=None):
     np = _T2.np
     rows, smooth = [], 1e-5
     for image_batch, mask_batch in batches:
-        _, preds_soft = test_single_batch(net, image_batch, orig_input_size, patch_size, stride, task_name, num_classes, fused=fused, window_batch=window_batch)
+        _, preds_soft = test_single_batch(net, image_batch, orig_input_size, patch_size, stride, task_name, num_classes, fused=fused, window_batch=window_batch,
+                                          tta=tta)
         with torch.no_grad():
             c = _onehot_counts(preds_soft, _index_mask('test_all_cases', preds_soft, mask_batch), num_classes).float()
             rows.append((2 * c[..., 0] + smooth) / (c[..., 1] + c[..., 2] + smooth))          # SF.dice_scores' expression on the same sums
@@ -360,13 +382,16 @@ class GraphedSlidingWindow(GraphedEvaluation):
     a call raises RuntimeError once the net was put in train mode or its fold state differs from the one captured (train(), load_state_dict() and in-place edits
     of a folded tensor all drop the fold).
     precision ('fp32' default, 'bf16x3'): warm-up and capture run inside inference_precision(precision); a GEMM's route is fixed when it is captured, so a
-    replay needs no setting and leaves none behind.  The object reports it as .precision."""
+    replay needs no setting and leaves none behind.  The object reports it as .precision.
+    tta: flip test-time augmentation as test_single_batch(fused=True, tta=) runs it -- the view table is built before the capture, and the graph holds the one
+    gather, the forwards of every view and the one merge; a replay equals that call bit for bit.  The static gather and score buffers hold V times as much."""
 
-    def __init__(self, net, image_shape, orig_input_size, patch_size, stride, num_classes, fold_bn=True, window_batch=None, warmup=2, precision='fp32'):
-        super().__init__(net, num_classes, fold_bn, warmup, precision, image_shape, orig_input_size, patch_size, stride, window_batch)
+    def __init__(self, net, image_shape, orig_input_size, patch_size, stride, num_classes, fold_bn=True, window_batch=None, warmup=2, precision='fp32', tta=None):
+        views = None if tta is None else SF.check_views(tta, 2)                      # refused before the net is folded or anything is launched
+        super().__init__(net, num_classes, fold_bn, warmup, precision, image_shape, orig_input_size, patch_size, stride, window_batch, views)
 
-    def _build(self, device, image_shape, orig_input_size, patch_size, stride, window_batch):
-        self.plan = _Plan(self.net, image_shape, orig_input_size, patch_size, stride, device, window_batch)
+    def _build(self, device, image_shape, orig_input_size, patch_size, stride, window_batch, tta=None):
+        self.plan = _Plan(self.net, image_shape, orig_input_size, patch_size, stride, device, window_batch, tta)
 
     def _sequence(self):
         return self.plan.run(self.net, self.image)
@@ -389,16 +414,17 @@ class GraphedBatchEvaluation(GraphedSlidingWindow):
     pixel values of the classes for the label images (e.g. (255, 128, 0) for fundus), None for none; with_extents: the row extents vcdr_from_extents reads.
     __call__(image_batch, mask) copies both into static buffers, replays and returns (preds_hard, preds_soft, counts, ext, labels): counts int32
     [B, num_classes - 1, 3], ext int32 [B, 2, 2, 2] or None, labels uint8 [B, H, W] or None -- STATIC tensors that the next call overwrites, nothing is read from the
-    device.  A mask of another shape or dtype raises ValueError; the other guards are GraphedSlidingWindow's."""
+    device.  A mask of another shape or dtype raises ValueError; the other guards are GraphedSlidingWindow's.  tta: as GraphedSlidingWindow; the tail reads the
+    averaged soft map."""
 
     def __init__(self, net, image_shape, orig_input_size, patch_size, stride, num_classes, fold_bn=True, window_batch=None, warmup=2, precision='fp32',
-                 mask_size=None, gt_map='nhot', values=None, with_extents=False):
+                 mask_size=None, gt_map='nhot', values=None, with_extents=False, tta=None):
         from .segx import SegxLib
         if gt_map not in SegxLib.NHOT_GT_MAPS:
             raise ValueError('GraphedBatchEvaluation: gt_map %r is not one of %s' % (gt_map, sorted(SegxLib.NHOT_GT_MAPS)))
         self.mask_size = None if mask_size is None else tuple(int(v) for v in mask_size)
         self.gt_map, self.values, self.with_extents = gt_map, (None if values is None else tuple(values)), bool(with_extents)
-        super().__init__(net, image_shape, orig_input_size, patch_size, stride, num_classes, fold_bn, window_batch, warmup, precision)
+        super().__init__(net, image_shape, orig_input_size, patch_size, stride, num_classes, fold_bn, window_batch, warmup, precision, tta)
 
     def _build(self, device, *plan_args):
         super()._build(device, *plan_args)

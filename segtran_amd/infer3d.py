@@ -18,7 +18,7 @@ import torch
 
 from . import functional as SF
 from . import test_util3d as _T3
-from .infer_common import PRECISIONS, GraphedEvaluation, _precision, folded, inference_precision, run_chunks      # noqa: F401  (inference_precision: re-exported)
+from .infer_common import PRECISIONS, GraphedEvaluation, _precision, composed_tta, folded, inference_precision, run_chunks, view_chunks      # noqa: F401  (inference_precision: re-exported)
 
 
 def fold_batchnorm(net):
@@ -64,19 +64,22 @@ def sliding_windows(H, W, D, orig_patch_size, stride_xy, stride_z, batch_size):
 class _Plan3d:
     """what the fused 3-D sequence needs beyond the image: the window table on the device, the geometry and the eager loop's chunks"""
 
-    def __init__(self, image_shape, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, device):
+    def __init__(self, image_shape, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, device, tta=None):
         self.shape = tuple(int(v) for v in image_shape)
+        self.views = None if tta is None else SF.ViewTable(tta, 3, device)          # refuses a bad tta before anything is launched
         if len(self.shape) != 4:
             raise ValueError('a [C, H, W, D] image, not %r' % (self.shape,))
         self.window, self.patch = tuple(int(v) for v in orig_patch_size), tuple(int(v) for v in input_patch_size)
         self.pads, self.canvas, origins, self.chunks = sliding_windows(*self.shape[1:], self.window, stride_xy, stride_z, batch_size)
         self.table = SF.WindowTable(origins, device)
+        if self.views is not None:                                                  # every view runs the eager loop's chunks, view after view
+            self.chunks = view_chunks(self.chunks, self.table.nwin, self.views.V)
 
     def run(self, net, image):
         """gather -> net() per chunk of the eager loop -> merge; the caller holds torch.no_grad().  (preds_hard, preds_soft) [num_classes, H, W, D]"""
-        patches = SF.window_gather(image.unsqueeze(0), self.table, self.window, self.patch, self.pads, self.canvas)
+        patches = SF.window_gather(image.unsqueeze(0), self.table, self.window, self.patch, self.pads, self.canvas, views=self.views)
         scores = run_chunks(net, patches, self.chunks)
-        preds_soft, preds_hard = SF.window_merge(scores, self.table, self.window, self.shape[1:], self.pads, self.canvas, mode=1)
+        preds_soft, preds_hard = SF.window_merge(scores, self.table, self.window, self.shape[1:], self.pads, self.canvas, mode=1, views=self.views)
         return preds_hard[0], preds_soft[0]
 
 
@@ -89,21 +92,30 @@ def _check_task(net_type, task_name):
 
 
 def test_single_case(net, image, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, task_name, net_type='segtran', num_classes=4,
-                     precision='fp32', fold_bn=False, fused=False):
-    """test_util3d.test_single_case with three more arguments.  precision: 'fp32' (default) -- exactly that function's results -- or 'bf16x3' -- the same loop under
+                     precision='fp32', fold_bn=False, fused=False, tta=None):
+    """test_util3d.test_single_case with four more arguments.  precision: 'fp32' (default) -- exactly that function's results -- or 'bf16x3' -- the same loop under
     torch.no_grad() inside inference_precision('bf16x3'); the setting the process had comes back at the end, also after an exception.  Any other name: ValueError.
     fold_bn: with the backbone's BatchNorm3d layers folded into its convolutions for this call (fold_batchnorm; a net the caller folded stays folded).
     fused: one window_gather launch on the image (the padded canvas never exists), net() once per chunk of sliding_windows() -- exactly the samples the eager loop
     stacks, so the forwards see the eager shapes --, the scores side by side in one buffer, one window_merge launch (no acc / cnt canvas, no accumulate pass per
     window, no clone of the un-padded region).  The merge is the accumulate + harden arithmetic bit for bit, so (preds_hard, preds_soft) equal the eager ones
     bit for bit for every batch_size.  The gather and the score buffer hold ALL windows at once: for a BraTS case (240 x 240 x 155, window 112 x 112 x 96 at
-    stride 56 / 48: 48 windows x 4 channels x 112 x 112 x 96 floats) about 0.93 GB each."""
+    stride 56 / 48: 48 windows x 4 channels x 112 x 112 x 96 floats) about 0.93 GB each.
+    tta: None (default: exactly the call without it) or a sequence of up to 8 views for flip test-time augmentation.  A view is a tuple of distinct
+    image axes to flip, 0 = H, 1 = W, 2 = D -- e.g. ((), (0,)); the identity () has to be listed to be used.  With soft_v = this call's preds_soft (the consistent
+    map) for the image flipped along view v's axes, flipped back, preds_soft = (((soft_0 + soft_1) + soft_2) + ...) / float(V) in fp32 made consistent again, and
+    preds_hard its hardening (SF.harden_segmap(mean, mode=1)).  fused=False runs that as a host loop (infer_common.composed_tta); fused=True runs one gather launch
+    for all views, the chunks of sliding_windows() for each view in turn and one merge launch, and equals the host loop bit for bit for every batch_size.  The
+    gather and the score buffer hold V times the figure above.  A bad tta raises ValueError before anything is launched."""
+    views = None if tta is None else SF.check_views(tta, 3)
     with _precision(precision), _folded(net, fold_bn):
         if not fused:
-            return _T3.test_single_case(net, image, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, task_name, net_type=net_type,
-                                        num_classes=num_classes)
+            def eager(x):
+                return _T3.test_single_case(net, x, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, task_name, net_type=net_type,
+                                            num_classes=num_classes)
+            return eager(image) if views is None else composed_tta(eager, image, views, 1, 1)
         _check_task(net_type, task_name)
-        plan = _Plan3d(image.shape, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, image.device)
+        plan = _Plan3d(image.shape, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, image.device, views)
         with torch.no_grad():
             return plan.run(net, image)
 
@@ -199,17 +211,20 @@ class GraphedSlidingWindow3d(GraphedEvaluation):
     STATIC tensors that the next call overwrites -- clone what must outlive it; entries that were not asked for are None.  A call raises RuntimeError once the net
     was put in train mode or its fold state differs from the one captured, ValueError on another shape.
     precision ('fp32' default, 'bf16x3'): warm-up and capture run inside inference_precision(precision); a replay needs no setting and leaves none behind.
-    The gather and score buffers hold all windows (test_single_case: about 0.93 GB each for a BraTS case) for the life of the object."""
+    The gather and score buffers hold all windows (test_single_case: about 0.93 GB each for a BraTS case) for the life of the object.
+    tta: flip test-time augmentation as test_single_case(fused=True, tta=) runs it, inside the capture; the buffers then hold V times as much, and the case tail reads
+    the averaged map."""
 
     _fold, _unfold = staticmethod(fold_batchnorm), staticmethod(unfold_batchnorm)
 
     def __init__(self, net, image_shape, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, num_classes=4, fold_bn=True, warmup=2,
-                 precision='fp32', with_labels=True, with_mask=False):
+                 precision='fp32', with_labels=True, with_mask=False, tta=None):
         self.with_labels, self.with_mask = bool(with_labels), bool(with_mask)
-        super().__init__(net, num_classes, fold_bn, warmup, precision, image_shape, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z)
+        views = None if tta is None else SF.check_views(tta, 3)                      # refused before the net is folded or anything is launched
+        super().__init__(net, num_classes, fold_bn, warmup, precision, image_shape, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, views)
 
     def _build(self, device, *plan_args):
-        self.plan = _Plan3d(*plan_args, device)
+        self.plan = _Plan3d(*plan_args[:-1], device, plan_args[-1])
         spatial = self.plan.shape[1:]
         self.mask = torch.zeros(spatial, dtype=torch.int32, device=device) if self.with_mask else None
         self.counts = torch.zeros(3, 3, dtype=torch.int32, device=device) if self.with_mask else None
@@ -244,7 +259,7 @@ class GraphedSlidingWindow3d(GraphedEvaluation):
 
 def test_all_cases(net, db_test, task_name='brats', net_type='segtran', num_classes=4, batch_size=8, orig_patch_size=(128, 112, 80),
                    input_patch_size=(128, 112, 64), stride_xy=56, stride_z=40, has_mask=True, on_labels=None, fused=True, graph=False, surface=False, hd95=False,
-                   precision='fp32', fold_bn=False):
+                   precision='fp32', fold_bn=False, tta=None):
     """The reference's evaluation loop over the cases of a dataset (test_util3d.py:15-91) for the BraTS task, without its file I/O; returns avg_metric
     [num_classes - 1, 4] (columns dice, jc, hd, asd) = the sum of the cases' metrics over the number of cases in which each entry is valid, as the reference does
     (an entry valid in no case is 0 / 0 = NaN).
@@ -257,8 +272,10 @@ def test_all_cases(net, db_test, task_name='brats', net_type='segtran', num_clas
     NIfTI is the caller's.  has_mask=False: no metrics (every entry 0 over ncases, as in the reference).
     surface=True (hd95=True implies it): columns 2 and 3 through surface_metrics on the float ground truth of SF.label_nhot(., 'brats') -- that builds the
     [4, S] maps and reads its histograms from the device once per case.
-    fold_bn: ONE fold for all the cases; precision: as test_single_case.  The reference's test_interp is not built."""
+    fold_bn: ONE fold for all the cases; precision: as test_single_case.  The reference's test_interp is not built.
+    tta: flip test-time augmentation of every case's evaluation, as test_single_case takes it (fused, eager or graph)."""
     _check_task(net_type, task_name)
+    views = None if tta is None else SF.check_views(tta, 3)
     if num_classes != 4:
         raise NotImplementedError('num_classes %r: only the 4-class BraTS task is built' % (num_classes,))
     surface = bool(surface or hd95)
@@ -279,7 +296,7 @@ def test_all_cases(net, db_test, task_name='brats', net_type='segtran', num_clas
                     if g is None:
                         g = graphs[tuple(image.shape)] = GraphedSlidingWindow3d(net, image.shape, orig_patch_size, input_patch_size, batch_size, stride_xy,
                                                                                 stride_z, num_classes, fold_bn=False, precision=precision,
-                                                                                with_labels=want_labels, with_mask=has_mask)
+                                                                                with_labels=want_labels, with_mask=has_mask, tta=views)
                     preds_hard, _, labels, counts = g(image, mask) if has_mask else g(image)
                     if has_mask:
                         counts_all[i].copy_(counts)
@@ -287,7 +304,7 @@ def test_all_cases(net, db_test, task_name='brats', net_type='segtran', num_clas
                         labels = labels.clone()                 # the graph's static volume: the next replay overwrites it
                 else:
                     preds_hard, preds_soft = test_single_case(net, image, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, task_name,
-                                                              net_type=net_type, num_classes=num_classes, fused=fused)
+                                                              net_type=net_type, num_classes=num_classes, fused=fused, tta=views)
                     labels = None
                     if has_mask or want_labels:
                         _, labels = SF.brats_case_tail(preds_soft, preds_hard, mask, want_labels=want_labels, counts=counts_all[i] if has_mask else None)

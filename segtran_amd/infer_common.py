@@ -64,6 +64,32 @@ def run_chunks(net, patches, chunks):
     return scores
 
 
+def view_chunks(chunks, rows_per_view, V):
+    """the row ranges `chunks` of one view's patches repeated for V views, view after view: a net() call never mixes views, so the forwards keep the shapes (and the
+    bits) they have without test-time augmentation"""
+    return [(v * rows_per_view + r0, v * rows_per_view + r1) for v in range(V) for r0, r1 in chunks]
+
+
+def composed_tta(evaluate, image, views, first_axis, mode):
+    """Flip test-time augmentation as a host loop over an existing evaluation -- the definition the fused form (SF.window_gather / SF.window_merge with views=) is
+    held to, bit for bit.  evaluate(image) -> (preds_hard, preds_soft) of one image or batch; views: check_views()' tuples of spatial axes, spatial
+    axis a being dimension first_axis + a of both the image and preds_soft.  Per view, in order: torch.flip the image, evaluate, flip preds_soft back;
+    preds_soft = (((soft_0 + soft_1) + soft_2) + ...) / float(V) in fp32 -- the divisor is a device tensor, so the division is a division and not ATen's product
+    with a reciprocal --, then SF.harden_segmap(mode) on the mean.  Returns (hard, soft) as harden_segmap leaves them (float 0 / 1 hard)."""
+    from . import functional as SF
+    with torch.no_grad():
+        total = None
+        for view in views:
+            dims = tuple(first_axis + a for a in view)
+            _, soft = evaluate(torch.flip(image, dims) if dims else image)
+            soft = torch.flip(soft, dims) if dims else soft
+            total = soft if total is None else total + soft
+        mean = total / total.new_full((), float(len(views)))
+        batched = mean if first_axis == 2 else mean.unsqueeze(0)
+        soft, hard = SF.harden_segmap(batched, mode=mode)
+        return (hard, soft) if first_axis == 2 else (hard[0], soft[0])
+
+
 class GraphedEvaluation:
     """The captured-evaluation core: one evaluation sequence of one input shape, warmed up, captured into a hipGraph and replayed.  A subclass supplies
     `_build(device, *args)` (self.plan, whose .shape is the input's, and its own static buffers; self.image is made here), `_sequence()` -> (preds_hard, preds_soft)

@@ -638,6 +638,19 @@ class SegxLib:
         self.check(self.c.segx_window_merge(_ptr(scores), _ptr(origins), origins_host, _ptr(soft), _ptr(hard), nwin, B, C, g, mode, T, self.stream(hard)),
                    'segx_window_merge')
 
+    def window_gather_views(self, image, origins, origins_host, views, views_host, out, nwin, V, B, C, geom):
+        """window_gather for V flipped views in one launch; views: device int32 [V] flip masks, views_host: a ctypes int32 array holding the same"""
+        self._chk_t(image, origins, views, out)
+        g = (c_i * 12)(*[int(v) for v in geom])
+        self.check(self.c.segx_window_gather_views(_ptr(image), _ptr(origins), origins_host, _ptr(views), views_host, _ptr(out), nwin, V, B, C, g,
+                                                   self.stream(out)), 'segx_window_gather_views')
+
+    def window_merge_views(self, scores, origins, origins_host, views, views_host, soft, hard, nwin, V, B, C, geom, mode, T=0.5):
+        self._chk_t(scores, origins, views, soft, hard)
+        g = (c_i * 15)(*[int(v) for v in geom])
+        self.check(self.c.segx_window_merge_views(_ptr(scores), _ptr(origins), origins_host, _ptr(views), views_host, _ptr(soft), _ptr(hard), nwin, V, B, C, g,
+                                                  mode, T, self.stream(hard)), 'segx_window_merge_views')
+
     def dice_sums(self, pred, gt, planes, S):
         n = int(self.c.segx_dice_ws_floats(planes, S))
         part = torch.empty(n, dtype=torch.float32, device=pred.device)
@@ -898,7 +911,7 @@ _SIGS = {
     'segx_axis_gather': 'pplpp', 'segx_pixel_shuffle2': 'ppliiip', 'segx_add_noise': 'ppplffiuup', 'segx_resize2d': 'ppliiiiiip', 'segx_color_blend': 'ppilippip',
     'segx_gray_mean_ws_floats': 'il', 'segx_gray_mean': 'pppilip', 'segx_normalize': 'ppiilfppp',
     'segx_x6_presplit_elems': 'iiii', 'segx_x6_presplit': 'piilliillpp',
-    'segx_tune': 'ii', 'segx_tune_get': 'i', 'segx_x3_launches': '', 'segx_gemm_route': 'pppp', 'segx_set_rng_base': 'p', 'segx_rng_advance': 'pup', 'segx_resized_crop3d': 'pplpp', 'segx_stem_compose_fwd': 'ppppiiiiip', 'segx_stem_compose_bwd': 'pppppppiiiiip', 'segx_bridge_input': 'ppiiiiiip', 'segx_stem_s2d_input': 'ppiiiiiip', 'segx_conv2d_stem_fwd': 'pppiiiiiiiiiiip', 'segx_conv2d_stem_im2col': 'ppiiiiiiiiiiip', 'segx_dropout': 'pplfuup', 'segx_avgpool2_fwd': 'ppliip', 'segx_avgpool2_bwd': 'ppliip', 'segx_transpose': 'ppliip', 'segx_interp_linear_fwd_axis': 'pppliilfp', 'segx_window_accum': 'pppiipp', 'segx_harden_segmap': 'ppppiilifp', 'segx_window_gather': 'ppppiiipp', 'segx_window_merge': 'pppppiiipifp', 'segx_dice_ws_floats': 'll', 'segx_dice_sums': 'pppllp',
+    'segx_tune': 'ii', 'segx_tune_get': 'i', 'segx_x3_launches': '', 'segx_gemm_route': 'pppp', 'segx_set_rng_base': 'p', 'segx_rng_advance': 'pup', 'segx_resized_crop3d': 'pplpp', 'segx_stem_compose_fwd': 'ppppiiiiip', 'segx_stem_compose_bwd': 'pppppppiiiiip', 'segx_bridge_input': 'ppiiiiiip', 'segx_stem_s2d_input': 'ppiiiiiip', 'segx_conv2d_stem_fwd': 'pppiiiiiiiiiiip', 'segx_conv2d_stem_im2col': 'ppiiiiiiiiiiip', 'segx_dropout': 'pplfuup', 'segx_avgpool2_fwd': 'ppliip', 'segx_avgpool2_bwd': 'ppliip', 'segx_transpose': 'ppliip', 'segx_interp_linear_fwd_axis': 'pppliilfp', 'segx_window_accum': 'pppiipp', 'segx_harden_segmap': 'ppppiilifp', 'segx_window_gather': 'ppppiiipp', 'segx_window_merge': 'pppppiiipifp', 'segx_window_gather_views': 'ppppppiiiipp', 'segx_window_merge_views': 'pppppppiiiipifp', 'segx_dice_ws_floats': 'll', 'segx_dice_sums': 'pppllp',
     'segx_surface_border': 'ppliiiip', 'segx_edt_sq': 'ppliiip', 'segx_surface_hist': 'pppliiiip', 'segx_brats_case_tail': 'ppppplp',
     'segx_index_onehot': 'piplilp', 'segx_onehot_colormap': 'ppplilp', 'segx_onehot_case_tail': 'ppppppiilfp', 'segx_nhot_case_tail': 'ppiipppppiiiiiifp',
     'segx_ccl2d': 'pippliip', 'segx_frag_keep2': 'ppliip', 'segx_frag_apply': 'ppppliiip', 'segx_row_extent': 'ppliifp', 'segx_nhot_to_values': 'ppplilp',
