@@ -825,6 +825,36 @@ int segx_row_extent(const float* mask, int32_t* ext, int64_t planes, int H, int 
 /* out[b][s] = values[c] of the LAST class c with nhot[b][c][s] == 1, 0 where no class is on (the reference assigns class by class, ascending). */
 int segx_nhot_to_values(const float* nhot, const int32_t* values, uint8_t* out, int64_t B, int C, int64_t S, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Connected-component post-processing of 3-D predictions (components.hip; the usual BraTS post-processing, Isensee et al. 2018 -- the reference has no counterpart).
+ * Stacks of volumes [V][X][Y][Z], Z contiguous -- one channel of preds_hard [C][H][W][D] is one such volume --, S = X * Y * Z < SEGX_CCL_MAX_PLANE.
+ * Integer results, exact and independent of the order of execution.  No call copies to the host or synchronises the stream: every call can be captured.
+ * ------------------------------------------------------------------------------------------- */
+#define SEGX_CCL3_TILE_X 8              /* the tile one workgroup labels in LDS; tests place their seams by these */
+#define SEGX_CCL3_TILE_Y 8
+#define SEGX_CCL3_TILE_Z 32
+/* 6- or 26-connected components (connectivity = 6 / 26) of every volume of fg, with segx_ccl2d's definitions: fg holds uint8 (fg_bytes = 1) or float32 (fg_bytes = 4)
+ * values and a voxel is background iff it equals bg_value (a NaN is set); labels: 0 on the background, else 1 + the raster index inside the volume of the
+ * component's first voxel; sizes: the component's voxel count at the cell of its first voxel, 0 everywhere else.  Both are written in full; no workspace.  One
+ * workgroup per tile in one grid: volumes * tiles per volume < 2^24. */
+int segx_ccl3d(const void* fg, int fg_bytes, int bg_value, int32_t* labels, int32_t* sizes, int64_t volumes, int X, int Y, int Z, int connectivity, void* stream);
+/* keep[v][s] (uint8) = 1 where voxel s of volume v belongs to a component that stays, else 0 (the background too).  A component stays iff its size >= min_voxels
+ * and (largest_only == 0 or it is the largest of its volume; among equals the one whose first voxel comes first in raster order).  A volume without foreground keeps
+ * nothing.  labels, sizes: as segx_ccl3d leaves them; stats: int32 [volumes][2] workspace (with largest_only: the largest size and 0x7fffffff - the first index of
+ * the component that has it; not touched otherwise). */
+int segx_cc3d_keep(const int32_t* labels, const int32_t* sizes, int32_t* stats, uint8_t* keep, int64_t volumes, int64_t S, int min_voxels, int largest_only,
+                   void* stream);
+/* out[i] = keep[i] ? src[i] : 0 for n elements of elem_bytes = 1, 2, 4 or 8 (bool / uint8, half / bfloat16, float32, float64), moved bit for bit */
+int segx_mask_apply(const void* src, int elem_bytes, const uint8_t* keep, void* out, int64_t n, void* stream);
+/* The BraTS rule on hard [4][S] = (background, ET, WT, TC -- brats_map_label's order) as 0 / 1 floats, into out [4][S] (another buffer):
+ *   WT' = keep ? WT : 0 (keep [S] bytes as segx_cc3d_keep leaves them for the WT channel; NULL = every voxel);  ET' = ET . WT', TC' = TC . WT';
+ *   if ET' has fewer than et_min_voxels voxels, ET' = 0 (TC stays);  background' = 1 exactly where ET' + WT' + TC' == 0.
+ * flag: int32 [2], written here: flag[0] = the voxel count of ET . WT', flag[1] = 1 iff ET was dropped -- the count and the decision stay on the device. */
+int segx_brats_postprocess(const float* hard, const uint8_t* keep, float* out, int32_t* flag, int64_t S, int et_min_voxels, void* stream);
+/* The export label volume after the rule: out[s] = 0 where wt[s] == 0 (wt = plane 2 of segx_brats_postprocess's out), else 1 where labels[s] == 4 and flag[1] is
+ * set, else labels[s].  labels: as segx_brats_case_tail writes them; out may be labels. */
+int segx_brats_relabel(const uint8_t* labels, const float* wt, const int32_t* flag, uint8_t* out, int64_t S, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

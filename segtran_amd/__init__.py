@@ -16,6 +16,24 @@ def inference_precision(name):
     return f(name)
 
 
+def connected_components(mask, connectivity=26):
+    """6- / 26-connected components of a device mask [X, Y, Z] or [V, X, Y, Z] on the device (infer3d.connected_components): (labels, sizes)."""
+    from .infer3d import connected_components as f
+    return f(mask, connectivity)
+
+
+def remove_small_components(mask, min_voxels=0, largest_only=False, connectivity=26):
+    """A new mask without the components below min_voxels / other than the largest (infer3d.remove_small_components)."""
+    from .infer3d import remove_small_components as f
+    return f(mask, min_voxels, largest_only, connectivity)
+
+
+def postprocess_brats(preds_hard, labels=None, **kw):
+    """The usual BraTS post-processing of a hard prediction [4, H, W, D] on the device (infer3d.postprocess_brats)."""
+    from .infer3d import postprocess_brats as f
+    return f(preds_hard, labels, **kw)
+
+
 def __getattr__(name):
     # all three take tta= (flip test-time augmentation inside the captured gather and merge launches: DESIGN.md 5z)
     if name == 'GraphedSlidingWindow':          # infer2d.GraphedSlidingWindow: the whole sliding-window evaluation of one image shape as one replayable hipGraph

@@ -1,6 +1,7 @@
 // components.hip -- the tail of the 2-D (fundus / polyp) evaluation on the device: 8-connected component labelling, removal of fragmentary segments
 // (test_util2d.py:267-289), the row extents behind the vertical cup/disc ratio (utils/losses.py:76-127) and the n-hot -> pixel-value maps
-// (datasets2d.py:144-171, 225-...).  Integer kernels with exact, order-independent results; no host round trip, no stream synchronisation.
+// (datasets2d.py:144-171, 225-...); further down the connected-component post-processing of 3-D predictions (6- / 26-connected labelling of volumes, the keep rule,
+// the BraTS rule).  Integer kernels with exact, order-independent results; no host round trip, no stream synchronisation.
 //
 // Labelling of uint8 planes [P][H][W] in three launches.  A label is 1 + the raster index (inside its plane) of another pixel of the same component that is
 // NOT LATER in raster order -- a parent pointer -- and 0 on the background; a pixel whose label is 1 + its own index is a root.
@@ -168,6 +169,239 @@ __global__ __launch_bounds__(256) void ccl_flatten_kernel(int* __restrict__ labe
     }
 }
 
+// ---- 3-D components ---------------------------------------------------------------------------------------------------------------------------
+// Stacks of volumes [V][X][Y][Z], Z contiguous; 6- or 26-connectivity.  The three launches of the planes carry over: (a) ccl3_tile_kernel labels a
+// C3_TX x C3_TY x C3_TZ tile in LDS to its fixed point (the tile's raster order is the volume's, so a tile-local root is the tile's first voxel of the component),
+// (b) ccl3_seam_kernel unites across tile boundaries, (c) ccl_flatten_kernel -- the planes' own, a volume being a plane of X * Y * Z cells to it.
+//
+// The seam pass.  One thread per (axis A, voxel p on the last layer of a tile along A that has a layer p.A + 1 in the volume): if the straight neighbour s = p + e_A is
+// set, unite(p, s) and nothing else; otherwise (26-connectivity) unite p with every set voxel among the other eight of the 3 x 3 patch around s in the layer p.A + 1.
+// Every pair of adjacent set voxels in different tiles ends up united, by induction on the number d of coordinates in which the pair differs.  d = 1: the pair is
+// straight across a seam, some thread's (p, s).  d > 1: the pair (p, q) crosses a seam along some axis A, p on the lower side; p's thread for A either finds s unset
+// and unites (p, q) itself, or unites (p, s) -- and (s, q) are adjacent set voxels that differ in d - 1 coordinates: united inside their tile by (a), or by the
+// induction.  Under 6-connectivity only d = 1 pairs are adjacent.  Pairs that touch only across a tile EDGE (d = 2, two seams) or a tile CORNER (d = 3, three seams) fall
+// under the same rule.
+// Termination is the argument at the head of this file word for word: the only writes are atomicMin(&L[a], b + 1) with b < a inside one volume's label array, labels only
+// decrease, ccl_find walks a strictly decreasing sequence of indices of that volume, every round of ccl_union ends or lowers one of two positive integers, and the
+// number of unions a thread attempts (at most 8) is fixed before it starts.  No thread waits for a value another thread has yet to write: there is no spin loop of
+// any kind and no workgroup ever waits for another.
+constexpr int C3_TX = SEGX_CCL3_TILE_X, C3_TY = SEGX_CCL3_TILE_Y, C3_TZ = SEGX_CCL3_TILE_Z;       // 8 x 8 x 32: rows of 128 bytes of float input
+constexpr int C3_PZ = C3_TZ + 2, C3_SX = (C3_TY + 2) * C3_PZ, C3_PN = (C3_TX + 2) * C3_SX;       // the LDS tile with its one-voxel unset rim
+static_assert(C3_TY * C3_TZ == 256, "a thread owns the column (y, z) of a tile: C3_TX voxels");
+
+template <typename T, bool FULL>
+__global__ __launch_bounds__(256) void ccl3_tile_kernel(const T* __restrict__ fg, int bg, int* __restrict__ labels, int* __restrict__ sizes, int X, int Y, int Z,
+                                                        int tiles_y, int tiles_z, int per_volume) {
+    __shared__ int lab[C3_PN], cnt[C3_PN];
+    __shared__ int changed[2];
+    const int tid = threadIdx.x, lz = tid % C3_TZ, ly = tid / C3_TZ;
+    const int64_t blk = blockIdx.x, vol = blk / per_volume;
+    const int t = (int)(blk - vol * per_volume);
+    const int x0 = (t / (tiles_y * tiles_z)) * C3_TX, y0 = ((t / tiles_z) % tiles_y) * C3_TY, z0 = (t % tiles_z) * C3_TZ;
+    const int64_t base = vol * X * Y * Z;
+    const int gy = y0 + ly, gz = z0 + lz, c0 = (ly + 1) * C3_PZ + lz + 1;
+    const bool inside = gy < Y && gz < Z;
+    const T bgv = (T)bg;
+    for (int i = tid; i < C3_PN; i += 256) { lab[i] = -1; cnt[i] = 0; }
+    if (tid < 2) changed[tid] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < C3_TX; ++k) {
+        const int c = (k + 1) * C3_SX + c0;
+        if (inside && x0 + k < X && fg[base + ((int64_t)(x0 + k) * Y + gy) * Z + gz] != bgv) lab[c] = c;
+    }
+    __syncthreads();
+    // label equivalence as in ccl_tile_kernel, over the 26 neighbours (FULL) or the 6 face neighbours
+    for (int it = 0;; ++it) {
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < C3_TX; ++k) {
+            const int c = (k + 1) * C3_SX + c0, r = lab[c];
+            if (r < 0) continue;
+            int m = r;
+            if (FULL) {
+#pragma unroll
+                for (int dx = -1; dx <= 1; ++dx)
+#pragma unroll
+                    for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+                        for (int dz = -1; dz <= 1; ++dz) {
+                            const int v = lab[c + dx * C3_SX + dy * C3_PZ + dz];
+                            if (v >= 0 && v < m) m = v;
+                        }
+            } else {
+#pragma unroll
+                for (int n = 0; n < 6; ++n) {
+                    const int v = lab[c + (n == 0 ? -C3_SX : n == 1 ? C3_SX : n == 2 ? -C3_PZ : n == 3 ? C3_PZ : n == 4 ? -1 : 1)];
+                    if (v >= 0 && v < m) m = v;
+                }
+            }
+            if (m < r) { atomicMin(&lab[r], m); any = true; }
+        }
+        if (any) changed[it & 1] = 1;
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < C3_TX; ++k) {
+            const int c = (k + 1) * C3_SX + c0;
+            int r = lab[c];
+            if (r < 0) continue;
+            for (int v = lab[r]; v < r; v = lab[r]) r = v;       // cells hold values <= their own index: strictly down to a root
+            lab[c] = r;
+        }
+        if (tid == 0) changed[(it + 1) & 1] = 0;                  // the other flag: nobody reads or sets it before the next barrier
+        const int again = changed[it & 1];
+        __syncthreads();
+        if (!again) break;
+    }
+#pragma unroll
+    for (int k = 0; k < C3_TX; ++k) {
+        const int r = lab[(k + 1) * C3_SX + c0];
+        if (r >= 0) atomicAdd(&cnt[r], 1);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < C3_TX; ++k) {
+        const int c = (k + 1) * C3_SX + c0;
+        if (!inside || x0 + k >= X) continue;
+        const int r = lab[c];
+        const int64_t g = base + ((int64_t)(x0 + k) * Y + gy) * Z + gz;
+        int label = 0;
+        if (r >= 0) {
+            const int rx = r / C3_SX - 1, ry = (r % C3_SX) / C3_PZ - 1, rz = r % C3_PZ - 1;
+            label = 1 + ((x0 + rx) * Y + y0 + ry) * Z + z0 + rz;
+        }
+        labels[g] = label;
+        sizes[g] = r == c ? cnt[c] : 0;
+    }
+}
+
+template <bool FULL>
+__global__ __launch_bounds__(256) void ccl3_seam_kernel(int* __restrict__ labels, int64_t volumes, int X, int Y, int Z) {
+    const int64_t nx = (int64_t)((X - 1) / C3_TX) * Y * Z, ny = (int64_t)((Y - 1) / C3_TY) * X * Z, nz = (int64_t)((Z - 1) / C3_TZ) * X * Y;
+    const int64_t per = nx + ny + nz, total = volumes * per, S = (int64_t)X * Y * Z;
+    for (int64_t it = (int64_t)blockIdx.x * 256 + threadIdx.x; it < total; it += (int64_t)gridDim.x * 256) {
+        const int64_t vol = it / per;
+        int64_t r = it - vol * per;
+        int* L = labels + vol * S;
+        // a: the voxel; sA the stride along the seam's axis; (cB, cC), (sB, sC), (nB, nC): its coordinates, the strides and the extents along the two other axes
+        int a, sA, sB, sC, cB, cC, nB, nC;
+        if (r < nx) {
+            const int k = (int)(r / ((int64_t)Y * Z)), rem = (int)(r - (int64_t)k * Y * Z);
+            cB = rem / Z; cC = rem - cB * Z; nB = Y; nC = Z; sA = Y * Z; sB = Z; sC = 1;
+            a = (((k + 1) * C3_TX - 1) * Y + cB) * Z + cC;
+        } else if (r < nx + ny) {
+            r -= nx;
+            const int k = (int)(r / ((int64_t)X * Z)), rem = (int)(r - (int64_t)k * X * Z);
+            cB = rem / Z; cC = rem - cB * Z; nB = X; nC = Z; sA = Z; sB = Y * Z; sC = 1;
+            a = (cB * Y + (k + 1) * C3_TY - 1) * Z + cC;
+        } else {
+            r -= nx + ny;
+            const int k = (int)(r / ((int64_t)X * Y)), rem = (int)(r - (int64_t)k * X * Y);
+            cB = rem / Y; cC = rem - cB * Y; nB = X; nC = Y; sA = 1; sB = Y * Z; sC = Z;
+            a = (cB * Y + cC) * Z + (k + 1) * C3_TZ - 1;
+        }
+        if (!ccl_set(L, a)) continue;
+        const int s = a + sA;                                                       // inside the volume: k counts only the seams with a layer behind them
+        if (ccl_set(L, s)) { ccl_union(L, a, s); continue; }
+        if (!FULL) continue;
+        for (int db = -1; db <= 1; ++db) {
+            if ((unsigned)(cB + db) >= (unsigned)nB) continue;
+            for (int dc = -1; dc <= 1; ++dc) {
+                if ((db | dc) == 0 || (unsigned)(cC + dc) >= (unsigned)nC) continue;
+                const int n = s + db * sB + dc * sC;
+                if (ccl_set(L, n)) ccl_union(L, a, n);
+            }
+        }
+    }
+}
+
+// ---- which components stay (3-D) ------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void cc3_zero_kernel(int* __restrict__ p, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = 0;
+}
+
+constexpr int C3_KEEP_MAX_CHUNKS = 1024;  // workgroups per volume of the largest-component reduction
+constexpr int C3_FIRST = 0x7fffffff;      // stats[v][1] holds C3_FIRST - (first index of the largest component): a maximum again, so both words start at 0
+// phase 0: stats[v][0] = the largest size of volume v; phase 1 (the next launch): stats[v][1] = the maximum of C3_FIRST - index over the cells whose size reaches it.
+// A thread folds its share, the workgroup folds in LDS, ONE global atomicMax per workgroup.
+__global__ __launch_bounds__(256) void cc3_largest_kernel(const int* __restrict__ sizes, int* __restrict__ stats, int S, int chunks, int phase) {
+    __shared__ int best;
+    const int64_t vol = blockIdx.x / chunks;
+    const int chunk = blockIdx.x % chunks;
+    const int* s = sizes + vol * S;
+    if (threadIdx.x == 0) best = 0;
+    __syncthreads();
+    const int top = phase ? stats[2 * vol] : 0;
+    int m = 0;
+    for (int64_t i = (int64_t)chunk * 256 + threadIdx.x; i < S; i += (int64_t)chunks * 256) {
+        const int v = s[i];
+        if (!phase) m = max(m, v);
+        else if (v > 0 && v == top) m = max(m, C3_FIRST - (int)i);
+    }
+    if (m > 0) atomicMax(&best, m);
+    __syncthreads();
+    if (threadIdx.x == 0 && best > 0) atomicMax(stats + 2 * vol + phase, best);
+}
+
+__global__ __launch_bounds__(256) void cc3_keep_kernel(const int* __restrict__ labels, const int* __restrict__ sizes, const int* __restrict__ stats,
+                                                       uint8_t* __restrict__ keep, int64_t volumes, int S, int min_voxels, int largest_only) {
+    const int64_t total = volumes * S;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        const int64_t vol = idx / S;
+        const int l = labels[idx];
+        bool k = false;
+        if (l > 0 && l <= S) {                                                      // anything else is no label of this volume: not kept, and no read through it
+            const int root = l - 1;
+            k = sizes[vol * S + root] >= min_voxels && (!largest_only || root == C3_FIRST - stats[2 * vol + 1]);
+        }
+        keep[idx] = k ? 1 : 0;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void mask_apply_kernel(const T* __restrict__ src, const uint8_t* __restrict__ keep, T* __restrict__ out, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = keep[i] ? src[i] : (T)0;
+}
+
+// ---- the BraTS post-processing rule ---------------------------------------------------------------------------------------------------------------------------
+// hard [4][S] = (bg, ET, WT, TC) as 0 / 1 floats; keep [S] bytes or NULL (= every voxel).  flag[0] += the number of voxels of ET . WT . keep: one LDS add per wave,
+// one global add per workgroup.  The trip count is uniform over the wave only up to the tail, so the shuffles come after the loop.
+__global__ __launch_bounds__(256) void brats_pp_count_kernel(const float* __restrict__ hard, const uint8_t* __restrict__ keep, int* __restrict__ flag, int64_t S) {
+    __shared__ int total;
+    if (threadIdx.x == 0) total = 0;
+    __syncthreads();
+    int n = 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < S; i += (int64_t)gridDim.x * 256)
+        n += (hard[S + i] != 0.0f && hard[2 * S + i] != 0.0f && (!keep || keep[i])) ? 1 : 0;
+    for (int m = 32; m > 0; m >>= 1) n += __shfl_xor(n, m);
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(&total, n);
+    __syncthreads();
+    if (threadIdx.x == 0 && total) atomicAdd(flag, total);
+}
+
+// flag[0] is final (launch boundary): every thread forms the same decision from it, and one of them leaves it in flag[1] for the relabel pass and the caller.
+__global__ __launch_bounds__(256) void brats_pp_apply_kernel(const float* __restrict__ hard, const uint8_t* __restrict__ keep, float* __restrict__ out,
+                                                             int* __restrict__ flag, int64_t S, int et_min_voxels) {
+    const bool drop = flag[0] < et_min_voxels;
+    if (blockIdx.x == 0 && threadIdx.x == 0) flag[1] = drop ? 1 : 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < S; i += (int64_t)gridDim.x * 256) {
+        const float wt = (!keep || keep[i]) ? hard[2 * S + i] : 0.0f;
+        const bool in = wt != 0.0f;
+        const float et = in && !drop ? hard[S + i] : 0.0f, tc = in ? hard[3 * S + i] : 0.0f;
+        out[i] = et + wt + tc == 0.0f ? 1.0f : 0.0f;
+        out[S + i] = et; out[2 * S + i] = wt; out[3 * S + i] = tc;
+    }
+}
+
+__global__ __launch_bounds__(256) void brats_pp_relabel_kernel(const uint8_t* labels, const float* __restrict__ wt, const int* __restrict__ flag, uint8_t* out,
+                                                               int64_t S) {                  // out may be labels: a thread reads a cell before it writes it
+    const bool drop = flag[1] != 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < S; i += (int64_t)gridDim.x * 256) {
+        const uint8_t l = labels[i];
+        out[i] = wt[i] == 0.0f ? (uint8_t)0 : (l == 4 && drop ? (uint8_t)1 : l);
+    }
+}
+
 // ---- which labels stay ---------------------------------------------------------------------------------------------------------------------------------------
 struct Top2 { int c1, l1, c2, l2; };                         // the best and the second candidate (count, label); count -1 = none
 __device__ __forceinline__ bool frag_better(int ca, int la, int cb, int lb) { return ca > cb || (ca == cb && la < lb); }     // ties: the lower label (background = 0) first
@@ -292,6 +526,85 @@ extern "C" int segx_ccl2d(const uint8_t* fg, int bg_value, int32_t* labels, int3
         hipLaunchKernelGGL(ccl_flatten_kernel, dim3(grid_for(planes * H * W)), dim3(256), 0, stream, labels, sizes, planes, H * W);
     }
     return check_launch("segx_ccl2d");
+}
+
+template <typename T>
+static void ccl3_launch_tile(bool full, unsigned tiles, hipStream_t stream, const void* fg, int bg, int32_t* labels, int32_t* sizes, int X, int Y, int Z, int ty,
+                             int tz, int per) {
+    if (full) hipLaunchKernelGGL((ccl3_tile_kernel<T, true>), dim3(tiles), dim3(256), 0, stream, (const T*)fg, bg, labels, sizes, X, Y, Z, ty, tz, per);
+    else hipLaunchKernelGGL((ccl3_tile_kernel<T, false>), dim3(tiles), dim3(256), 0, stream, (const T*)fg, bg, labels, sizes, X, Y, Z, ty, tz, per);
+}
+
+extern "C" int segx_ccl3d(const void* fg, int fg_bytes, int bg_value, int32_t* labels, int32_t* sizes, int64_t volumes, int X, int Y, int Z, int connectivity,
+                          void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(fg && labels && sizes, "segx_ccl3d: null pointer");
+    SEGX_REQUIRE(volumes > 0 && X > 0 && Y > 0 && Z > 0, "segx_ccl3d: volumes, X, Y and Z must be positive");
+    const int64_t S = (int64_t)X * Y * Z;
+    SEGX_REQUIRE(S < SEGX_CCL_MAX_PLANE, "segx_ccl3d: X * Y * Z = %lld is not below the limit of 2^30 voxels per volume", (long long)S);
+    SEGX_REQUIRE(fg_bytes == 1 || fg_bytes == 4, "segx_ccl3d: fg_bytes %d is neither 1 (uint8) nor 4 (float32)", fg_bytes);
+    SEGX_REQUIRE(connectivity == 6 || connectivity == 26, "segx_ccl3d: connectivity %d is neither 6 nor 26", connectivity);
+    SEGX_REQUIRE(bg_value >= 0 && bg_value <= 255, "segx_ccl3d: bg_value %d is no uint8 value", bg_value);
+    const int tx = (X + C3_TX - 1) / C3_TX, ty = (Y + C3_TY - 1) / C3_TY, tz = (Z + C3_TZ - 1) / C3_TZ;
+    const int64_t per = (int64_t)tx * ty * tz, tiles = volumes * per;
+    SEGX_REQUIRE(tiles < ((int64_t)1 << 24), "segx_ccl3d: %lld tiles exceed one grid (2^24 workgroups of 256 threads)", (long long)tiles);
+    const bool full = connectivity == 26;
+    if (fg_bytes == 1) ccl3_launch_tile<uint8_t>(full, (unsigned)tiles, stream, fg, bg_value, labels, sizes, X, Y, Z, ty, tz, (int)per);
+    else ccl3_launch_tile<float>(full, (unsigned)tiles, stream, fg, bg_value, labels, sizes, X, Y, Z, ty, tz, (int)per);
+    const int64_t seam = volumes * ((int64_t)((X - 1) / C3_TX) * Y * Z + (int64_t)((Y - 1) / C3_TY) * X * Z + (int64_t)((Z - 1) / C3_TZ) * X * Y);
+    if (seam > 0) {
+        if (full) hipLaunchKernelGGL(ccl3_seam_kernel<true>, dim3(grid_for(seam)), dim3(256), 0, stream, labels, volumes, X, Y, Z);
+        else hipLaunchKernelGGL(ccl3_seam_kernel<false>, dim3(grid_for(seam)), dim3(256), 0, stream, labels, volumes, X, Y, Z);
+        hipLaunchKernelGGL(ccl_flatten_kernel, dim3(grid_for(volumes * S)), dim3(256), 0, stream, labels, sizes, volumes, (int)S);
+    }
+    return check_launch("segx_ccl3d");
+}
+
+extern "C" int segx_cc3d_keep(const int32_t* labels, const int32_t* sizes, int32_t* stats, uint8_t* keep, int64_t volumes, int64_t S, int min_voxels,
+                              int largest_only, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(labels && sizes && stats && keep, "segx_cc3d_keep: null pointer");
+    SEGX_REQUIRE(volumes > 0 && S > 0, "segx_cc3d_keep: volumes and S must be positive");
+    SEGX_REQUIRE(S < SEGX_CCL_MAX_PLANE, "segx_cc3d_keep: S = %lld is not below the limit of 2^30 voxels per volume", (long long)S);
+    SEGX_REQUIRE(min_voxels >= 0, "segx_cc3d_keep: min_voxels %d is negative", min_voxels);
+    const int chunks = (int)i64max(1, i64min(C3_KEEP_MAX_CHUNKS, (S + 2047) / 2048));         // a thread folds about eight cells
+    SEGX_REQUIRE(volumes * chunks < ((int64_t)1 << 24), "segx_cc3d_keep: %lld volumes exceed one grid", (long long)volumes);
+    if (largest_only) {
+        hipLaunchKernelGGL(cc3_zero_kernel, dim3(grid_for(volumes * 2)), dim3(256), 0, stream, stats, volumes * 2);
+        hipLaunchKernelGGL(cc3_largest_kernel, dim3((unsigned)(volumes * chunks)), dim3(256), 0, stream, sizes, stats, (int)S, chunks, 0);
+        hipLaunchKernelGGL(cc3_largest_kernel, dim3((unsigned)(volumes * chunks)), dim3(256), 0, stream, sizes, stats, (int)S, chunks, 1);
+    }
+    hipLaunchKernelGGL(cc3_keep_kernel, dim3(grid_for(volumes * S)), dim3(256), 0, stream, labels, sizes, stats, keep, volumes, (int)S, min_voxels,
+                       largest_only ? 1 : 0);
+    return check_launch("segx_cc3d_keep");
+}
+
+extern "C" int segx_mask_apply(const void* src, int elem_bytes, const uint8_t* keep, void* out, int64_t n, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(src && keep && out, "segx_mask_apply: null pointer");
+    SEGX_REQUIRE(n > 0, "segx_mask_apply: n must be positive");
+    SEGX_REQUIRE(elem_bytes == 1 || elem_bytes == 2 || elem_bytes == 4 || elem_bytes == 8, "segx_mask_apply: elem_bytes %d is not 1, 2, 4 or 8", elem_bytes);
+    const dim3 grid(grid_for(n));                       // the elements move as integers of their width: an all-zero pattern is 0 in every type this serves
+    if (elem_bytes == 1) hipLaunchKernelGGL(mask_apply_kernel<uint8_t>, grid, dim3(256), 0, stream, (const uint8_t*)src, keep, (uint8_t*)out, n);
+    else if (elem_bytes == 2) hipLaunchKernelGGL(mask_apply_kernel<uint16_t>, grid, dim3(256), 0, stream, (const uint16_t*)src, keep, (uint16_t*)out, n);
+    else if (elem_bytes == 4) hipLaunchKernelGGL(mask_apply_kernel<uint32_t>, grid, dim3(256), 0, stream, (const uint32_t*)src, keep, (uint32_t*)out, n);
+    else hipLaunchKernelGGL(mask_apply_kernel<uint64_t>, grid, dim3(256), 0, stream, (const uint64_t*)src, keep, (uint64_t*)out, n);
+    return check_launch("segx_mask_apply");
+}
+
+extern "C" int segx_brats_postprocess(const float* hard, const uint8_t* keep, float* out, int32_t* flag, int64_t S, int et_min_voxels, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(hard && out && flag, "segx_brats_postprocess: null pointer");
+    SEGX_REQUIRE(hard != out, "segx_brats_postprocess: out must not be hard");
+    SEGX_REQUIRE(S > 0 && S < ((int64_t)1 << 31), "segx_brats_postprocess: S = %lld is not in 1 .. 2^31 - 1", (long long)S);
+    SEGX_REQUIRE(et_min_voxels >= 0, "segx_brats_postprocess: et_min_voxels %d is negative", et_min_voxels);
+    hipLaunchKernelGGL(cc3_zero_kernel, dim3(1), dim3(256), 0, stream, flag, (int64_t)2);
+    hipLaunchKernelGGL(brats_pp_count_kernel, dim3((unsigned)i64min(4096, (S + 255) / 256)), dim3(256), 0, stream, hard, keep, flag, S);
+    hipLaunchKernelGGL(brats_pp_apply_kernel, dim3(grid_for(S)), dim3(256), 0, stream, hard, keep, out, flag, S, et_min_voxels);
+    return check_launch("segx_brats_postprocess");
+}
+
+extern "C" int segx_brats_relabel(const uint8_t* labels, const float* wt, const int32_t* flag, uint8_t* out, int64_t S, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(labels && wt && flag && out, "segx_brats_relabel: null pointer");
+    SEGX_REQUIRE(S > 0 && S < ((int64_t)1 << 31), "segx_brats_relabel: S = %lld is not in 1 .. 2^31 - 1", (long long)S);
+    hipLaunchKernelGGL(brats_pp_relabel_kernel, dim3(grid_for(S)), dim3(256), 0, stream, labels, wt, flag, out, S);
+    return check_launch("segx_brats_relabel");
 }
 
 extern "C" int segx_frag_keep2(const int32_t* sizes, int32_t* keep, int64_t planes, int H, int W, void* stream_) {

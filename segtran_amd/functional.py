@@ -2965,6 +2965,141 @@ def remove_fragments(seg_u8, bg_value):
     return out
 
 
+# -------------------------------------------------------------------------------------------------
+# Connected-component post-processing of 3-D predictions (components.hip): 6- / 26-connected labelling of volumes [X, Y, Z] or stacks [V, X, Y, Z],
+# the keep rule and the BraTS rule.  Integer-exact; no copy to the host and no synchronisation, so the calls can be captured into a graph.  Forward only.
+# -------------------------------------------------------------------------------------------------
+CONNECTIVITIES3D = (6, 26)
+
+
+def check_connectivity3d(what, connectivity):
+    if connectivity not in CONNECTIVITIES3D or isinstance(connectivity, bool):
+        raise ValueError('%s: connectivity %r is neither 6 nor 26' % (what, connectivity))
+    return int(connectivity)
+
+
+def check_voxel_count(what, name, v):
+    """a threshold in voxels: a non-negative integer below 2^31"""
+    try:
+        ok = not isinstance(v, bool) and int(v) == v and 0 <= int(v) < 1 << 31
+    except (TypeError, ValueError, OverflowError):             # None, a string, inf, nan
+        ok = False
+    if not ok:
+        raise ValueError('%s: %s = %r is not a non-negative voxel count' % (what, name, v))
+    return int(v)
+
+
+def _volumes_operand(what, t):
+    """(tensor the labelling reads: uint8 or float32, contiguous -- bool viewed as uint8, uint8 and float32 as they are, any other float type as the uint8 map
+    (t != 0), one extra pass, taken in the type itself so that no non-zero value rounds to 0; V, X, Y, Z) of a bool / uint8 / float mask [X, Y, Z] or [V, X, Y, Z]"""
+    if torch.is_grad_enabled() and t.requires_grad:
+        raise RuntimeError(what + ' is forward-only: call it under torch.no_grad() or on tensors without gradient')
+    if t.dim() not in (3, 4):
+        raise ValueError('%s: an [X, Y, Z] or [V, X, Y, Z] tensor, not rank %d' % (what, t.dim()))
+    if not (t.dtype in (torch.bool, torch.uint8) or t.is_floating_point()):
+        raise TypeError('%s: a bool, uint8 or float tensor, not %s' % (what, t.dtype))
+    V, X, Y, Z = (1,) * (4 - t.dim()) + tuple(t.shape)
+    if V < 1 or X < 1 or Y < 1 or Z < 1:
+        raise ValueError('%s: empty tensor %s' % (what, tuple(t.shape)))
+    if X * Y * Z >= segx.SegxLib.CCL_MAX_PLANE:
+        raise ValueError('%s: X * Y * Z = %d is not below the limit of 2^30 voxels per volume' % (what, X * Y * Z))
+    t = _c(t.detach())
+    if t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    elif t.is_floating_point() and t.dtype != torch.float32:
+        t = (t != 0).view(torch.uint8)
+    return t, V, X, Y, Z
+
+
+def label_components3d(mask, connectivity=26):
+    """6- or 26-connected components of every volume of a bool / uint8 / float mask [V, X, Y, Z] or [X, Y, Z] (segx_ccl3d; a bool, uint8 or float32 mask is read as
+    it is, no conversion pass; another float type through one (mask != 0) pass); a voxel is set iff it is not 0.  Returns (labels, sizes), int32 of the mask's shape, with label_components' definitions: labels = 0 on the
+    background, else 1 + the raster index inside the volume of the component's first voxel; sizes = the component's voxel count at that first voxel, 0 elsewhere."""
+    conn = check_connectivity3d('label_components3d', connectivity)
+    m, V, X, Y, Z = _volumes_operand('label_components3d', mask)
+    labels = torch.empty(m.shape, dtype=torch.int32, device=m.device)
+    sizes = torch.empty(m.shape, dtype=torch.int32, device=m.device)
+    segx.lib().ccl3d(m, 0, labels, sizes, V, X, Y, Z, conn)
+    return labels, sizes
+
+
+def keep_components3d(labels, sizes, min_voxels=0, largest_only=False):
+    """uint8 keep mask of label_components3d's (labels, sizes) (segx_cc3d_keep): 1 on the voxels of every component with size >= min_voxels that, with largest_only,
+    is also the largest of its volume (ties: the one whose first voxel comes first in raster order); 0 elsewhere.  A volume without foreground keeps nothing."""
+    nmin = check_voxel_count('keep_components3d', 'min_voxels', min_voxels)
+    if labels.dim() not in (3, 4) or labels.shape != sizes.shape or labels.dtype != torch.int32 or sizes.dtype != torch.int32:
+        raise ValueError('keep_components3d: labels %s and sizes %s must be int32 [X, Y, Z] or [V, X, Y, Z] tensors of one shape' % (tuple(labels.shape), tuple(sizes.shape)))
+    labels, sizes = _c(labels), _c(sizes)
+    V = labels.shape[0] if labels.dim() == 4 else 1
+    S = labels.numel() // max(V, 1)
+    if V < 1 or S < 1:
+        raise ValueError('keep_components3d: empty tensor %s' % (tuple(labels.shape),))
+    keep = torch.empty(labels.shape, dtype=torch.uint8, device=labels.device)
+    stats = torch.empty(V, 2, dtype=torch.int32, device=labels.device)
+    segx.lib().cc3d_keep(labels, sizes, stats, keep, V, S, nmin, largest_only)
+    return keep
+
+
+def remove_small_components3d(mask, min_voxels=0, largest_only=False, connectivity=26):
+    """A NEW tensor of mask's shape and dtype: mask where keep_components3d(label_components3d(mask, connectivity), min_voxels, largest_only) is set, 0 elsewhere
+    (segx_ccl3d, segx_cc3d_keep, segx_mask_apply)."""
+    conn = check_connectivity3d('remove_small_components3d', connectivity)
+    check_voxel_count('remove_small_components3d', 'min_voxels', min_voxels)
+    m, V, X, Y, Z = _volumes_operand('remove_small_components3d', mask)
+    labels, sizes = label_components3d(m, conn)
+    keep = keep_components3d(labels, sizes, min_voxels, largest_only)
+    src = _c(mask.detach())
+    out = torch.empty_like(src)                                 # the mask's own dtype: the elements move bit for bit at their width
+    segx.lib().mask_apply(src, keep, out, src.numel())
+    return out
+
+
+def brats_postprocess(hard, wt_min_voxels=0, wt_largest_only=False, et_min_voxels=0, connectivity=26, out=None, flag=None):
+    """The BraTS post-processing rule on hard float32 [4, X, Y, Z] (background, ET, WT, TC -- brats_map_label's order -- as 0 / 1 floats):
+      1. WT' = WT . keep_components3d(label_components3d(WT, connectivity), wt_min_voxels, wt_largest_only);  2. ET' = ET . WT', TC' = TC . WT';
+      3. ET' = 0 if it has fewer than et_min_voxels voxels (TC stays);  4. background' = 1 exactly where ET' + WT' + TC' == 0.
+    Returns (hard', flag): a new tensor (or `out`), hard itself is not modified; flag int32 [2] on the device = (voxel count of ET . WT', 1 iff ET was dropped),
+    which brats_relabel reads.  With wt_min_voxels <= 1 and no wt_largest_only every WT component stays and no labelling runs."""
+    what = 'brats_postprocess'
+    conn = check_connectivity3d(what, connectivity)
+    wt_min, et_min = check_voxel_count(what, 'wt_min_voxels', wt_min_voxels), check_voxel_count(what, 'et_min_voxels', et_min_voxels)
+    _no_grad_operands(what, hard)
+    if hard.dim() != 4 or hard.shape[0] != 4 or hard.dtype != torch.float32:
+        raise ValueError('%s: hard %s %s must be a float32 [4, X, Y, Z] tensor (the 4-class BraTS task)' % (what, hard.dtype, tuple(hard.shape)))
+    hard = _c(hard.detach())
+    S = hard[0].numel()
+    if S < 1:
+        raise ValueError('%s: empty tensor %s' % (what, tuple(hard.shape)))
+    if out is None:
+        out = torch.empty_like(hard)
+    elif out.dtype != torch.float32 or out.shape != hard.shape or not out.is_contiguous() or out.data_ptr() == hard.data_ptr():
+        raise ValueError('%s: out is another contiguous float32 %s tensor' % (what, tuple(hard.shape)))
+    if flag is None:
+        flag = torch.empty(2, dtype=torch.int32, device=hard.device)
+    elif flag.dtype != torch.int32 or tuple(flag.shape) != (2,):
+        raise ValueError('%s: flag is an int32 [2] tensor' % what)
+    keep = None
+    if wt_min > 1 or wt_largest_only:
+        labels, sizes = label_components3d(hard[2], conn)
+        keep = keep_components3d(labels, sizes, wt_min, wt_largest_only)
+    segx.lib().brats_postprocess(hard, keep, out, flag, S, et_min)
+    return out, flag
+
+
+def brats_relabel(labels, hard_pp, flag, out=None):
+    """The export label volume (brats_case_tail's uint8 labels) after brats_postprocess: 0 where WT' (hard_pp[2]) is 0, a 4 becomes 1 where flag says ET was dropped.
+    Returns a new tensor, or `out` (which may be labels itself)."""
+    if labels.dtype != torch.uint8 or hard_pp.dim() < 2 or hard_pp.shape[0] != 4 or tuple(labels.shape) != tuple(hard_pp.shape[1:]) or hard_pp.dtype != torch.float32:
+        raise ValueError('brats_relabel: labels uint8 %s do not match hard_pp float32 %s' % (tuple(labels.shape), tuple(hard_pp.shape)))
+    labels, hard_pp = _c(labels), _c(hard_pp)
+    if out is None:
+        out = torch.empty_like(labels)
+    elif out.dtype != torch.uint8 or out.shape != labels.shape or not out.is_contiguous():
+        raise ValueError('brats_relabel: out is a contiguous uint8 %s tensor' % (tuple(labels.shape),))
+    segx.lib().brats_relabel(labels, hard_pp[2], flag, out, labels.numel())
+    return out
+
+
 def row_extent(mask, thres):
     """int32 [P, 2] (or [2] for one [H, W] plane): the lowest and the highest row index of each plane of the float mask that holds a value >= thres; (H, -1) where
     none does."""

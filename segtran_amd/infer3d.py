@@ -9,7 +9,10 @@ the device in integers (metrics.hip, DESIGN.md 5o) and finished here in float64;
 
 And the case evaluation in one pass: sliding_windows (the eager loops' geometry and batches), test_single_case(fused=True) (one gather launch, net() on the
 eager loop's batches, one merge launch), GraphedSlidingWindow3d (that sequence with the BraTS case tail, SF.brats_case_tail, as one replayable hipGraph), case_metrics
-and test_all_cases (the reference's loop over the cases of a dataset, test_util3d.py:15-91, without its file I/O)."""
+and test_all_cases (the reference's loop over the cases of a dataset, test_util3d.py:15-91, without its file I/O).
+
+And the step a BraTS user runs on the prediction: connected_components, remove_small_components and postprocess_brats on the device, and the
+`postprocess=` argument that places the rule between the merge and the case tail of test_single_case, GraphedSlidingWindow3d and test_all_cases."""
 import math
 import os
 
@@ -83,6 +86,71 @@ class _Plan3d:
         return preds_hard[0], preds_soft[0]
 
 
+# ---- connected-component post-processing ----------------------------------------------------------------------------------------------------
+POSTPROCESS_KEYS = ('wt_min_voxels', 'wt_largest_only', 'et_min_voxels', 'connectivity')
+
+
+def _device_operand(what, t):
+    if not isinstance(t, torch.Tensor) or t.device.type == 'cpu':
+        raise ValueError('%s: a device tensor, not %s' % (what, 'a host tensor' if isinstance(t, torch.Tensor) else type(t).__name__))
+
+
+def check_postprocess(postprocess, num_classes=4):
+    """the `postprocess` argument of the evaluation entry points: None, or a dict of postprocess_brats' keyword arguments made complete and checked -- ValueError on an
+    unknown key, a connectivity other than 6 / 26, a negative threshold or num_classes != 4, before anything is launched"""
+    if postprocess is None:
+        return None
+    if not isinstance(postprocess, dict):
+        raise ValueError('postprocess: None or a dict of %s, not %r' % (POSTPROCESS_KEYS, postprocess))
+    unknown = sorted(set(postprocess) - set(POSTPROCESS_KEYS))
+    if unknown:
+        raise ValueError('postprocess: unknown keys %s (known: %s)' % (unknown, POSTPROCESS_KEYS))
+    if num_classes != 4:
+        raise ValueError('postprocess: the BraTS rule needs num_classes == 4, not %r' % (num_classes,))
+    p = dict(wt_min_voxels=0, wt_largest_only=False, et_min_voxels=0, connectivity=26)
+    p.update(postprocess)
+    p['connectivity'] = SF.check_connectivity3d('postprocess', p['connectivity'])
+    for k in ('wt_min_voxels', 'et_min_voxels'):
+        p[k] = SF.check_voxel_count('postprocess', k, p[k])
+    p['wt_largest_only'] = bool(p['wt_largest_only'])
+    return p
+
+
+def connected_components(mask, connectivity=26):
+    """(labels, sizes) int32 of the 6- or 26-connected components of a device mask [X, Y, Z] or a stack [V, X, Y, Z] (bool, uint8 or float; set = not 0), on the
+    device (SF.label_components3d): labels = 0 on the background, else 1 + the raster index inside its volume of the component's first voxel; sizes = the
+    component's voxel count at that first voxel, 0 elsewhere.  ValueError for a connectivity other than 6 / 26 or a host tensor, before anything is launched."""
+    SF.check_connectivity3d('connected_components', connectivity)
+    _device_operand('connected_components', mask)
+    with torch.no_grad():
+        return SF.label_components3d(mask, connectivity)
+
+
+def remove_small_components(mask, min_voxels=0, largest_only=False, connectivity=26):
+    """A NEW tensor of mask's shape, dtype and device (as infer2d.remove_fragmentary_segs returns one) that holds only the components of at least min_voxels voxels
+    and, with largest_only, of those only the largest of each volume (ties: the one that starts first in raster order).  A volume without foreground stays empty."""
+    SF.check_connectivity3d('remove_small_components', connectivity)
+    SF.check_voxel_count('remove_small_components', 'min_voxels', min_voxels)
+    _device_operand('remove_small_components', mask)
+    with torch.no_grad():
+        return SF.remove_small_components3d(mask, min_voxels, largest_only, connectivity)
+
+
+def postprocess_brats(preds_hard, labels=None, *, wt_min_voxels=0, wt_largest_only=False, et_min_voxels=0, connectivity=26):
+    """The usual BraTS post-processing (Isensee et al., "No New-Net", 2018) of preds_hard [4, H, W, D] (background, ET, WT, TC) on the device (SF.brats_postprocess):
+    WT loses its components below wt_min_voxels (with wt_largest_only: all but the largest), ET and TC are cut to what is left of WT, ET is dropped when fewer than
+    et_min_voxels voxels remain, the background is recomputed.  Returns preds_hard' (a new tensor), and (preds_hard', labels') when the export label volume `labels`
+    (uint8 [H, W, D], SF.brats_case_tail's) is given: 0 outside WT', a 4 turned into 1 where ET was dropped.  The inputs are not modified."""
+    p = check_postprocess(dict(wt_min_voxels=wt_min_voxels, wt_largest_only=wt_largest_only, et_min_voxels=et_min_voxels, connectivity=connectivity),
+                          preds_hard.shape[0] if isinstance(preds_hard, torch.Tensor) and preds_hard.dim() == 4 else None)
+    _device_operand('postprocess_brats', preds_hard)
+    if labels is not None:
+        _device_operand('postprocess_brats', labels)
+    with torch.no_grad():
+        hard, flag = SF.brats_postprocess(preds_hard, **p)
+        return hard if labels is None else (hard, SF.brats_relabel(labels, hard, flag))
+
+
 def _check_task(net_type, task_name):
     """the refusals of test_util3d.test_single_case"""
     if net_type != 'segtran':
@@ -92,8 +160,8 @@ def _check_task(net_type, task_name):
 
 
 def test_single_case(net, image, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, task_name, net_type='segtran', num_classes=4,
-                     precision='fp32', fold_bn=False, fused=False, tta=None):
-    """test_util3d.test_single_case with four more arguments.  precision: 'fp32' (default) -- exactly that function's results -- or 'bf16x3' -- the same loop under
+                     precision='fp32', fold_bn=False, fused=False, tta=None, postprocess=None):
+    """test_util3d.test_single_case with five more arguments.  precision: 'fp32' (default) -- exactly that function's results -- or 'bf16x3' -- the same loop under
     torch.no_grad() inside inference_precision('bf16x3'); the setting the process had comes back at the end, also after an exception.  Any other name: ValueError.
     fold_bn: with the backbone's BatchNorm3d layers folded into its convolutions for this call (fold_batchnorm; a net the caller folded stays folded).
     fused: one window_gather launch on the image (the padded canvas never exists), net() once per chunk of sliding_windows() -- exactly the samples the eager loop
@@ -106,18 +174,26 @@ def test_single_case(net, image, orig_patch_size, input_patch_size, batch_size, 
     map) for the image flipped along view v's axes, flipped back, preds_soft = (((soft_0 + soft_1) + soft_2) + ...) / float(V) in fp32 made consistent again, and
     preds_hard its hardening (SF.harden_segmap(mean, mode=1)).  fused=False runs that as a host loop (infer_common.composed_tta); fused=True runs one gather launch
     for all views, the chunks of sliding_windows() for each view in turn and one merge launch, and equals the host loop bit for bit for every batch_size.  The
-    gather and the score buffer hold V times the figure above.  A bad tta raises ValueError before anything is launched."""
+    gather and the score buffer hold V times the figure above.  A bad tta raises ValueError before anything is launched.
+    postprocess: None (default: exactly the call without it) or a dict of postprocess_brats' keyword arguments: preds_hard is what that function makes of the
+    merged prediction (on the device); preds_soft is returned unchanged.  A bad dict raises ValueError before anything is launched."""
     views = None if tta is None else SF.check_views(tta, 3)
+    post = check_postprocess(postprocess, num_classes)
     with _precision(precision), _folded(net, fold_bn):
         if not fused:
             def eager(x):
                 return _T3.test_single_case(net, x, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, task_name, net_type=net_type,
                                             num_classes=num_classes)
-            return eager(image) if views is None else composed_tta(eager, image, views, 1, 1)
-        _check_task(net_type, task_name)
-        plan = _Plan3d(image.shape, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, image.device, views)
-        with torch.no_grad():
-            return plan.run(net, image)
+            hard, soft = eager(image) if views is None else composed_tta(eager, image, views, 1, 1)
+        else:
+            _check_task(net_type, task_name)
+            plan = _Plan3d(image.shape, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, image.device, views)
+            with torch.no_grad():
+                hard, soft = plan.run(net, image)
+        if post is not None:
+            with torch.no_grad():
+                hard = SF.brats_postprocess(hard, **post)[0]
+        return hard, soft
 
 
 # reference function name; not a pytest test
@@ -213,14 +289,17 @@ class GraphedSlidingWindow3d(GraphedEvaluation):
     precision ('fp32' default, 'bf16x3'): warm-up and capture run inside inference_precision(precision); a replay needs no setting and leaves none behind.
     The gather and score buffers hold all windows (test_single_case: about 0.93 GB each for a BraTS case) for the life of the object.
     tta: flip test-time augmentation as test_single_case(fused=True, tta=) runs it, inside the capture; the buffers then hold V times as much, and the case tail reads
-    the averaged map."""
+    the averaged map.
+    postprocess: None (default: exactly the capture without it) or a dict of postprocess_brats' keyword arguments: the rule runs inside the capture between the merge
+    and the case tail, so preds_hard, the counts and the label volume are the post-processed ones; preds_soft is the merged map unchanged."""
 
     _fold, _unfold = staticmethod(fold_batchnorm), staticmethod(unfold_batchnorm)
 
     def __init__(self, net, image_shape, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, num_classes=4, fold_bn=True, warmup=2,
-                 precision='fp32', with_labels=True, with_mask=False, tta=None):
+                 precision='fp32', with_labels=True, with_mask=False, tta=None, postprocess=None):
         self.with_labels, self.with_mask = bool(with_labels), bool(with_mask)
         views = None if tta is None else SF.check_views(tta, 3)                      # refused before the net is folded or anything is launched
+        self.post = check_postprocess(postprocess, num_classes)
         super().__init__(net, num_classes, fold_bn, warmup, precision, image_shape, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, views)
 
     def _build(self, device, *plan_args):
@@ -229,11 +308,16 @@ class GraphedSlidingWindow3d(GraphedEvaluation):
         self.mask = torch.zeros(spatial, dtype=torch.int32, device=device) if self.with_mask else None
         self.counts = torch.zeros(3, 3, dtype=torch.int32, device=device) if self.with_mask else None
         self.labels = torch.zeros(spatial, dtype=torch.uint8, device=device) if self.with_labels else None
+        self.flag = torch.zeros(2, dtype=torch.int32, device=device) if self.post is not None else None
 
     def _sequence(self):
         hard, soft = self.plan.run(self.net, self.image)
+        if self.post is not None:
+            hard, _ = SF.brats_postprocess(hard, flag=self.flag, **self.post)
         if self.with_labels or self.with_mask:
             SF.brats_case_tail(soft, hard, self.mask, want_labels=self.with_labels, counts=self.counts, labels=self.labels)
+        if self.post is not None and self.with_labels:
+            SF.brats_relabel(self.labels, hard, self.flag, out=self.labels)
         return hard, soft
 
     def _check_classes(self):
@@ -254,12 +338,12 @@ class GraphedSlidingWindow3d(GraphedEvaluation):
     def close(self):
         """GraphedEvaluation.close(), and drop the case's static buffers as well"""
         super().close()
-        self.labels = self.counts = self.image = self.mask = None
+        self.labels = self.counts = self.image = self.mask = self.flag = None
 
 
 def test_all_cases(net, db_test, task_name='brats', net_type='segtran', num_classes=4, batch_size=8, orig_patch_size=(128, 112, 80),
                    input_patch_size=(128, 112, 64), stride_xy=56, stride_z=40, has_mask=True, on_labels=None, fused=True, graph=False, surface=False, hd95=False,
-                   precision='fp32', fold_bn=False, tta=None):
+                   precision='fp32', fold_bn=False, tta=None, postprocess=None):
     """The reference's evaluation loop over the cases of a dataset (test_util3d.py:15-91) for the BraTS task, without its file I/O; returns avg_metric
     [num_classes - 1, 4] (columns dice, jc, hd, asd) = the sum of the cases' metrics over the number of cases in which each entry is valid, as the reference does
     (an entry valid in no case is 0 / 0 = NaN).
@@ -273,7 +357,10 @@ def test_all_cases(net, db_test, task_name='brats', net_type='segtran', num_clas
     surface=True (hd95=True implies it): columns 2 and 3 through surface_metrics on the float ground truth of SF.label_nhot(., 'brats') -- that builds the
     [4, S] maps and reads its histograms from the device once per case.
     fold_bn: ONE fold for all the cases; precision: as test_single_case.  The reference's test_interp is not built.
-    tta: flip test-time augmentation of every case's evaluation, as test_single_case takes it (fused, eager or graph)."""
+    tta: flip test-time augmentation of every case's evaluation, as test_single_case takes it (fused, eager or graph).
+    postprocess: None or a dict of postprocess_brats' keyword arguments: the rule runs on the device between every case's merge and its tail, so the Dice / Jaccard
+    counts, the surface columns and the on_labels volumes all see the post-processed prediction."""
+    post = check_postprocess(postprocess, num_classes)
     _check_task(net_type, task_name)
     views = None if tta is None else SF.check_views(tta, 3)
     if num_classes != 4:
@@ -296,7 +383,7 @@ def test_all_cases(net, db_test, task_name='brats', net_type='segtran', num_clas
                     if g is None:
                         g = graphs[tuple(image.shape)] = GraphedSlidingWindow3d(net, image.shape, orig_patch_size, input_patch_size, batch_size, stride_xy,
                                                                                 stride_z, num_classes, fold_bn=False, precision=precision,
-                                                                                with_labels=want_labels, with_mask=has_mask, tta=views)
+                                                                                with_labels=want_labels, with_mask=has_mask, tta=views, postprocess=post)
                     preds_hard, _, labels, counts = g(image, mask) if has_mask else g(image)
                     if has_mask:
                         counts_all[i].copy_(counts)
@@ -306,8 +393,12 @@ def test_all_cases(net, db_test, task_name='brats', net_type='segtran', num_clas
                     preds_hard, preds_soft = test_single_case(net, image, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, task_name,
                                                               net_type=net_type, num_classes=num_classes, fused=fused, tta=views)
                     labels = None
+                    if post is not None:
+                        preds_hard, flag = SF.brats_postprocess(preds_hard, **post)
                     if has_mask or want_labels:
                         _, labels = SF.brats_case_tail(preds_soft, preds_hard, mask, want_labels=want_labels, counts=counts_all[i] if has_mask else None)
+                    if post is not None and want_labels:
+                        labels = SF.brats_relabel(labels, preds_hard, flag, out=labels)
                 if surface and has_mask:
                     gt = SF.label_nhot((mask - (mask == 4).to(mask.dtype)).unsqueeze(0), 'brats')[0]
                     surf.append(surface_metrics(preds_hard[1:num_classes], gt[1:num_classes], hd95=hd95))

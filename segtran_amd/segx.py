@@ -716,6 +716,24 @@ class SegxLib:
     def nhot_to_values(self, nhot, values, out, B, C, S):
         self._call('segx_nhot_to_values', out, nhot, values, out, B, C, S)
 
+    # ---- 3-D components and the BraTS post-processing rule (components.hip) ------------------------------
+    CCL3_TILE = (8, 8, 32)                               # SEGX_CCL3_TILE_X / _Y / _Z of include/segx.h
+
+    def ccl3d(self, fg, bg_value, labels, sizes, volumes, X, Y, Z, connectivity):
+        self._call('segx_ccl3d', labels, fg, fg.element_size(), int(bg_value), labels, sizes, volumes, X, Y, Z, int(connectivity))
+
+    def cc3d_keep(self, labels, sizes, stats, keep, volumes, S, min_voxels, largest_only):
+        self._call('segx_cc3d_keep', keep, labels, sizes, stats, keep, volumes, S, int(min_voxels), int(bool(largest_only)))
+
+    def mask_apply(self, src, keep, out, n):
+        self._call('segx_mask_apply', out, src, src.element_size(), keep, out, n)
+
+    def brats_postprocess(self, hard, keep, out, flag, S, et_min_voxels):
+        self._call('segx_brats_postprocess', out, hard, keep, out, flag, S, int(et_min_voxels))
+
+    def brats_relabel(self, labels, wt, flag, out, S):
+        self._call('segx_brats_relabel', out, labels, wt, flag, out, S)
+
     def conv3d_splitk(self, B, Cout, geom, wgrad):
         return int(self.c.segx_conv3d_splitk(B, Cout, self._geom(geom), 1 if wgrad else 0))
 
@@ -915,6 +933,7 @@ _SIGS = {
     'segx_surface_border': 'ppliiiip', 'segx_edt_sq': 'ppliiip', 'segx_surface_hist': 'pppliiiip', 'segx_brats_case_tail': 'ppppplp',
     'segx_index_onehot': 'piplilp', 'segx_onehot_colormap': 'ppplilp', 'segx_onehot_case_tail': 'ppppppiilfp', 'segx_nhot_case_tail': 'ppiipppppiiiiiifp',
     'segx_ccl2d': 'pippliip', 'segx_frag_keep2': 'ppliip', 'segx_frag_apply': 'ppppliiip', 'segx_row_extent': 'ppliifp', 'segx_nhot_to_values': 'ppplilp',
+    'segx_ccl3d': 'piippliiiip', 'segx_cc3d_keep': 'pppplliip', 'segx_mask_apply': 'pipplp', 'segx_brats_postprocess': 'pppplip', 'segx_brats_relabel': 'pppplp',
     'segx_conv3d_fwd': 'pppiipipp', 'segx_conv3d_fwd_packed': 'pppiipipp', 'segx_conv3d_fwd_packed_bs': 'pppiipipllp', 'segx_conv3d_bwd_weight_packed_bs': 'pppiipipllp', 'segx_conv3d_pack_weights': 'ppiiiip', 'segx_conv3d_splitk': 'iipi', 'segx_conv3d_route': 'iipiiiip', 'segx_conv3d_fwd_terms': 'iipiii', 'segx_conv3d_flip_weights': 'ppiiip', 'segx_conv3d_bwd_weight': 'pppiipipp', 'segx_conv3d_bwd_weight_packed': 'pppiipipp', 'segx_conv3d_unpack_wgrad': 'ppiiip',
     'segx_conv3d_halo_ok': 'iip', 'segx_conv3d_halo_wq_floats': 'ii', 'segx_conv3d_halo_pack': 'ppiiip', 'segx_conv3d_halo_fwd': 'pppiipllip', 'segx_conv3d_halo_bias_act_fwd': 'ppppiiplliip', 'segx_conv3d_fwd_bias_act': 'ppppiipipillip', 'segx_bias_map_relu': 'ppilp', 'segx_conv3d_halo_wgrad_ok': 'iip', 'segx_conv3d_halo_wgrad_ws_floats': 'iip', 'segx_conv3d_halo_wgrad': 'ppppiipllp',
     'segx_conv3d_bwd_data_direct': 'ppppiipp', 'segx_nonzero_mask': 'ppiiiiiiiip', 'segx_label_nhot': 'ppiilip',
