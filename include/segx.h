@@ -855,6 +855,41 @@ int segx_brats_postprocess(const float* hard, const uint8_t* keep, float* out, i
  * set, else labels[s].  labels: as segx_brats_case_tail writes them; out may be labels. */
 int segx_brats_relabel(const uint8_t* labels, const float* wt, const int32_t* flag, uint8_t* out, int64_t S, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Lesion-wise evaluation (components.hip; the per-lesion scoring BraTS uses since 2023 -- the reference has no counterpart, DESIGN.md 5zb defines it).
+ * Stacks of region volumes [V][X][Y][Z], S = X * Y * Z < SEGX_CCL_MAX_PLANE.  A mask operand is named by (bytes, map): map SEGX_LESION_MAP_NONE with bytes 1 / 4 =
+ * uint8 / float32 [V][S], set = not 0 (a NaN is set, as segx_ccl3d reads it); map SEGX_LESION_MAP_BRATS with bytes 4 and V == 3 = ONE volume [S] of raw int32 BraTS
+ * labels shared by the regions 0, 1, 2 = ET, WT, TC and mapped in registers as segx_brats_case_tail maps it (a raw 4 counts as 3; any other value sets no region).
+ * Integer results, exact and independent of the order of execution.  No call copies to the host or synchronises the stream: every call can be captured.
+ * ------------------------------------------------------------------------------------------- */
+#define SEGX_LESION_MAX_GT 1024         /* lesions per region: the rows of the table */
+#define SEGX_LESION_MAX_PRED 16384      /* predicted components per region; the touch matrix is MAX_GT x MAX_PRED bytes = 16 MiB per region */
+#define SEGX_LESION_HEADER 8            /* int32 words per region: {n_lesions, n_pred_components, n_fp, fp_voxels, overflow, 0, 0, 0} */
+#define SEGX_LESION_MAP_NONE 0
+#define SEGX_LESION_MAP_BRATS 1
+/* out [V][S] (uint8, 0 / 1) = the mask src dilated iters >= 0 times by the 3 x 3 x 3 structuring element that holds the centre and its 6, 18 or 26 nearest neighbours
+ * (connectivity); voxels outside the volume are unset, nothing wraps around: scipy.ndimage.binary_dilation(src, generate_binary_structure(3, 1 | 2 | 3), iters).
+ * iters == 0 writes the mask itself as bytes.  One launch per iteration (iters == 0: one), a workgroup per SEGX_CCL3_TILE tile with its rim in LDS: volumes * tiles per
+ * volume < 2^24; tmp [V][S] is the second ping-pong buffer, needed (and not out) from
+ * two iterations on, else it may be NULL.  src is not modified and is neither out nor tmp. */
+int segx_dilate3d(const void* src, int src_bytes, int src_map, uint8_t* out, uint8_t* tmp, int64_t volumes, int X, int Y, int Z, int connectivity, int iters,
+                  void* stream);
+/* Bytes of the workspace of segx_lesion_match / segx_lesion_reduce for `volumes` regions (16-byte aligned; initialised by segx_lesion_match). */
+int64_t segx_lesion_ws_bytes(int64_t volumes);
+/* Matches predicted components to lesions.  gl, gsizes: segx_ccl3d's labels and sizes of the DILATED ground truth; pl, psizes: those of the prediction; gt: the
+ * ground truth itself.  Lesion g = the gt voxels with gl == g.  Every lesion root and every predicted root draws a compact id from an integer counter (arbitrary
+ * order); the cells of gsizes and psizes at the roots are OVERWRITTEN with 1 + that id (0 past a cap) -- both arrays are consumed.  Then one pass over the voxels
+ * accumulates per lesion gvol = |lesion| and tp = |lesion AND prediction| (integer atomic adds, folded per wave first) and marks in a byte matrix which (lesion,
+ * component) pairs share a voxel with gl == g and pl == p (plain idempotent stores).  More than SEGX_LESION_MAX_GT lesions or SEGX_LESION_MAX_PRED components in a
+ * region raise that region's overflow word; nothing is written out of bounds, the region's rows are then meaningless.  1 <= volumes <= 65535. */
+int segx_lesion_match(const void* gt, int gt_bytes, int gt_map, const int32_t* gl, int32_t* gsizes, const int32_t* pl, int32_t* psizes, void* ws, int64_t volumes,
+                      int64_t S, void* stream);
+/* Finishes ws as segx_lesion_match left it.  rows int32 [V][SEGX_LESION_MAX_GT][4]: for each of the region's first min(n_lesions, SEGX_LESION_MAX_GT) ids the row
+ * (root label of the dilated lesion, tp, gvol, pvol), pvol = the sum of the sizes of the distinct components that touch the lesion, in the arbitrary order of the ids;
+ * the rows behind them are zeros.  header int32 [V][SEGX_LESION_HEADER]: n_lesions and n_pred_components as counted (they may exceed the caps), n_fp = the number
+ * of components that touch no lesion and fp_voxels = the sum of their sizes, overflow = 1 iff a cap was exceeded. */
+int segx_lesion_reduce(void* ws, int32_t* rows, int32_t* header, int64_t volumes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

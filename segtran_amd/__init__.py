@@ -34,6 +34,12 @@ def postprocess_brats(preds_hard, labels=None, **kw):
     return f(preds_hard, labels, **kw)
 
 
+def lesionwise_metrics(pred, gt, **kw):
+    """Lesion-wise Dice, detections and false positives of binary device volumes [R, X, Y, Z] or [X, Y, Z] (infer3d.lesionwise_metrics): a list of R dicts."""
+    from .infer3d import lesionwise_metrics as f
+    return f(pred, gt, **kw)
+
+
 def __getattr__(name):
     # all three take tta= (flip test-time augmentation inside the captured gather and merge launches: DESIGN.md 5z)
     if name == 'GraphedSlidingWindow':          # infer2d.GraphedSlidingWindow: the whole sliding-window evaluation of one image shape as one replayable hipGraph

@@ -402,6 +402,202 @@ __global__ __launch_bounds__(256) void brats_pp_relabel_kernel(const uint8_t* la
     }
 }
 
+// ---- lesion-wise evaluation -------------------------------------------------------------------------------------------------------------------
+// Stacks of region volumes [V][S].  How a voxel of a mask operand is read: KIND 1 = uint8, 4 = float32 (set = not 0; a NaN is set, as segx_ccl3d reads it),
+// MASK_BRATS = ONE volume [S] of raw int32 BraTS labels shared by the three regions v = 0, 1, 2 = ET, WT, TC, mapped in registers as segx_brats_case_tail maps it
+// (a raw 4 counts as 3; ET = 3, WT = 1, 2, 3, TC = 1, 3; any other value sets no region).
+constexpr int MASK_BRATS = -4;
+template <int KIND>
+__device__ __forceinline__ bool mask_set(const void* p, int64_t S, int64_t v, int64_t i) {
+    if (KIND == 1) return ((const uint8_t*)p)[v * S + i] != 0;
+    if (KIND == 4) return ((const float*)p)[v * S + i] != 0.0f;
+    int l = ((const int*)p)[i];
+    if (l == 4) l = 3;
+    return v == 0 ? l == 3 : v == 1 ? (l >= 1 && l <= 3) : (l == 1 || l == 3);
+}
+
+// One application of the 3 x 3 x 3 structuring element that holds the centre and its neighbours at L1 distance <= maxd (1 / 2 / 3 = 6 / 18 / 26 neighbours); voxels
+// outside the volume are unset.  maxd = 0 copies the mask as bytes.  One workgroup per C3_TX x C3_TY x C3_TZ tile (the labelling's): the tile and its one-voxel rim
+// go to LDS as bytes, 0 beyond the volume, so no neighbour test remains; a thread owns the column (y, z) of the tile and walks x with a window of three layers.  Of a
+// layer it keeps three bits: the cell itself (distance 0 inside the layer), the OR of its 4 face neighbours inside the layer (1) and of the 4 diagonal ones (2); in the
+// layer before and behind, those distances are one more.
+constexpr int DL_PZ = C3_TZ + 2, DL_SX = (C3_TY + 2) * DL_PZ, DL_PN = (C3_TX + 2) * DL_SX;        // 10 x 10 x 34 bytes
+template <int KIND>
+__global__ __launch_bounds__(256) void dilate3_kernel(const void* __restrict__ src, uint8_t* __restrict__ out, int X, int Y, int Z, int tiles_y, int tiles_z,
+                                                      int per_volume, int maxd) {
+    __shared__ uint8_t m[DL_PN];
+    const int tid = threadIdx.x, lz = tid % C3_TZ, ly = tid / C3_TZ;
+    const int64_t blk = blockIdx.x, vol = blk / per_volume, S = (int64_t)X * Y * Z;
+    const int t = (int)(blk - vol * per_volume);
+    const int x0 = (t / (tiles_y * tiles_z)) * C3_TX, y0 = ((t / tiles_z) % tiles_y) * C3_TY, z0 = (t % tiles_z) * C3_TZ;
+    for (int i = tid; i < DL_PN; i += 256) {
+        const int px = i / DL_SX, r = i - px * DL_SX, py = r / DL_PZ, pz = r - py * DL_PZ;
+        const int gx = x0 + px - 1, gy = y0 + py - 1, gz = z0 + pz - 1;
+        bool s = false;
+        if ((unsigned)gx < (unsigned)X && (unsigned)gy < (unsigned)Y && (unsigned)gz < (unsigned)Z) s = mask_set<KIND>(src, S, vol, ((int64_t)gx * Y + gy) * Z + gz);
+        m[i] = s ? 1 : 0;
+    }
+    __syncthreads();
+    const int gy = y0 + ly, gz = z0 + lz;
+    if (gy >= Y || gz >= Z) return;                                                // behind the only barrier
+    const uint8_t* col = m + (ly + 1) * DL_PZ + lz + 1;
+    auto layer = [col](int px) -> int {
+        const uint8_t* p = col + px * DL_SX;
+        const int f = p[-1] | p[1] | p[-DL_PZ] | p[DL_PZ], e = p[-DL_PZ - 1] | p[-DL_PZ + 1] | p[DL_PZ - 1] | p[DL_PZ + 1];
+        return p[0] | (f << 1) | (e << 2);
+    };
+    const int same_mask = maxd == 0 ? 1 : maxd == 1 ? 3 : 7, next_mask = maxd == 0 ? 0 : maxd == 1 ? 1 : maxd == 2 ? 3 : 7;
+    int lo = layer(0), mid = layer(1);
+#pragma unroll
+    for (int k = 0; k < C3_TX; ++k) {
+        const int hi = layer(k + 2);
+        if (x0 + k < X) out[vol * S + ((int64_t)(x0 + k) * Y + gy) * Z + gz] = ((mid & same_mask) | ((lo | hi) & next_mask)) ? 1 : 0;
+        lo = mid; mid = hi;
+    }
+}
+
+// The workspace of segx_lesion_match / segx_lesion_reduce: per region LS_INTS words, then per region the touch matrix of LS_MAX_GT x LS_MAX_PRED bytes.
+constexpr int LS_MAX_GT = SEGX_LESION_MAX_GT, LS_MAX_PRED = SEGX_LESION_MAX_PRED, LS_HEADER = SEGX_LESION_HEADER;
+constexpr int LS_CNT = 4;                                                   // {lesion roots seen, predicted roots seen, overflow, unused}
+constexpr int LS_INTS = LS_CNT + 3 * LS_MAX_GT + 2 * LS_MAX_PRED;
+static_assert(LS_MAX_PRED % 4 == 0 && LS_INTS % 4 == 0, "touch rows are cleared as words");
+struct LesionWs { int *cnt, *groot, *gvol, *tp, *psize, *matched; uint8_t* touch; };
+__device__ __forceinline__ LesionWs lesion_ws(void* ws, int64_t volumes, int64_t v) {
+    int* w = (int*)ws + v * LS_INTS;
+    LesionWs r;
+    r.cnt = w; r.groot = w + LS_CNT; r.gvol = r.groot + LS_MAX_GT; r.tp = r.gvol + LS_MAX_GT; r.psize = r.tp + LS_MAX_GT; r.matched = r.psize + LS_MAX_PRED;
+    r.touch = (uint8_t*)((int*)ws + volumes * LS_INTS) + v * (int64_t)LS_MAX_GT * LS_MAX_PRED;
+    return r;
+}
+
+// Compact ids.  A root cell (sizes > 0) draws its id from the region's counter and leaves 1 + id in its own cell of sizes: the cell becomes the map root -> id that the
+// match pass reads through the labels, with no array of S words beside it.  The size of a predicted component moves to psize[id]; the size of a DILATED lesion is
+// not used by anything.  The order of the ids is arbitrary; rows carry the root label.  A root past a cap gets no id (cell 0) and raises the overflow word.
+// Roots are few (one atomic per component, not per voxel).
+__global__ __launch_bounds__(256) void lesion_ids_kernel(int* __restrict__ gsizes, int* __restrict__ psizes, void* ws, int64_t volumes, int S) {
+    const int64_t total = volumes * S;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        const int64_t v = idx / S;
+        const int gs = gsizes[idx], ps = psizes[idx];
+        if (gs <= 0 && ps <= 0) continue;
+        const LesionWs W = lesion_ws(ws, volumes, v);
+        if (gs > 0) {
+            const int id = atomicAdd(W.cnt, 1);
+            if (id < LS_MAX_GT) { W.groot[id] = (int)(idx - v * S) + 1; gsizes[idx] = id + 1; }
+            else { gsizes[idx] = 0; W.cnt[2] = 1; }
+        }
+        if (ps > 0) {
+            const int id = atomicAdd(W.cnt + 1, 1);
+            if (id < LS_MAX_PRED) { W.psize[id] = ps; psizes[idx] = id + 1; }
+            else { psizes[idx] = 0; W.cnt[2] = 1; }
+        }
+    }
+}
+
+// the ids are final (launch boundary): clear the part of the touch matrix that can be written, rows < lesions, columns < components.  One workgroup per row.
+__global__ __launch_bounds__(256) void lesion_clear_touch_kernel(void* ws, int64_t volumes) {
+    const int64_t v = blockIdx.x / LS_MAX_GT;
+    const int gid = blockIdx.x % LS_MAX_GT;
+    const LesionWs W = lesion_ws(ws, volumes, v);
+    if (gid >= min(W.cnt[0], LS_MAX_GT)) return;
+    int* row = (int*)(W.touch + (int64_t)gid * LS_MAX_PRED);
+    const int n = (min(W.cnt[1], LS_MAX_PRED) + 3) / 4;
+    for (int t = threadIdx.x; t < n; t += 256) row[t] = 0;
+}
+
+// One pass over the voxels.  A voxel with a lesion label g and a component label p marks touch[id(g)][id(p)] with a plain store of 1 (idempotent: every writer stores
+// the same byte).  A ground-truth voxel adds 1 to gvol[id(g)] and, where the prediction is set (p > 0), 1 to tp[id(g)].  Neighbouring voxels mostly belong to ONE
+// lesion, so a wave folds its 64 voxels first: the lowest lane that still holds a count names its lesion, the lanes of that lesion are summed by shuffles, that lane
+// issues the two atomics, and the round repeats while any lane is left -- one round for most waves, none for a wave without ground truth.  A wave walks whole groups of
+// 64 cells, so every lane takes part in every shuffle; cells past the end carry nothing.
+template <int KIND>
+__global__ __launch_bounds__(256) void lesion_match_kernel(const void* __restrict__ gt, const int* __restrict__ GL, const int* __restrict__ gid_of,
+                                                           const int* __restrict__ PL, const int* __restrict__ pid_of, void* ws, int64_t volumes, int S) {
+    const int lane = threadIdx.x & 63;
+    const int64_t total = volumes * S;
+    for (int64_t base = (int64_t)blockIdx.x * 256 + (threadIdx.x - lane); base < total; base += (int64_t)gridDim.x * 256) {
+        const int64_t idx = base + lane;
+        int slot = -1, both = 0;                                                   // slot = v * LS_MAX_GT + id of the lesion this lane counts for
+        if (idx < total) {
+            const int64_t v = idx / S, i = idx - v * S;
+            const int g = GL[idx];
+            if (g > 0 && g <= S) {                                                  // anything else is no label of this volume: no read through it
+                const int gid = gid_of[v * S + g - 1] - 1;
+                if ((unsigned)gid < (unsigned)LS_MAX_GT) {
+                    const int p = PL[idx];
+                    const bool hit = p > 0 && p <= S;
+                    if (hit) {
+                        const int pid = pid_of[v * S + p - 1] - 1;
+                        if ((unsigned)pid < (unsigned)LS_MAX_PRED) lesion_ws(ws, volumes, v).touch[(int64_t)gid * LS_MAX_PRED + pid] = 1;
+                    }
+                    if (mask_set<KIND>(gt, S, v, i)) { slot = (int)v * LS_MAX_GT + gid; both = hit ? 1 : 0; }
+                }
+            }
+        }
+        for (;;) {
+            int first = slot >= 0 ? lane : 64;
+            for (int m = 32; m > 0; m >>= 1) first = min(first, __shfl_xor(first, m));
+            if (first == 64) break;                                                 // wave-uniform
+            const int lead = __shfl(slot, first);
+            const bool mine = slot == lead;
+            int n = mine ? 1 + (both << 16) : 0;                                    // both counts stay below 2^16 in one word
+            for (int m = 32; m > 0; m >>= 1) n += __shfl_xor(n, m);
+            if (lane == first) {
+                const LesionWs W = lesion_ws(ws, volumes, lead / LS_MAX_GT);
+                atomicAdd(W.gvol + lead % LS_MAX_GT, n & 0xffff);
+                if (n >> 16) atomicAdd(W.tp + lead % LS_MAX_GT, n >> 16);
+            }
+            if (mine) slot = -1;
+        }
+    }
+}
+
+// One workgroup per (region, lesion id): pvol = the sizes of the components of its touch row; every such component is marked matched (plain stores of 1).  The row
+// (root label, tp, gvol, pvol) goes to the table; the rows past the last lesion are written as zeros.
+__global__ __launch_bounds__(256) void lesion_rows_kernel(void* ws, int* __restrict__ rows, int64_t volumes) {
+    __shared__ int total;
+    const int64_t v = blockIdx.x / LS_MAX_GT;
+    const int gid = blockIdx.x % LS_MAX_GT, tid = threadIdx.x;
+    const LesionWs W = lesion_ws(ws, volumes, v);
+    int* row = rows + ((int64_t)v * LS_MAX_GT + gid) * 4;
+    if (gid >= min(W.cnt[0], LS_MAX_GT)) {                                          // uniform over the workgroup
+        if (tid < 4) row[tid] = 0;
+        return;
+    }
+    if (tid == 0) total = 0;
+    __syncthreads();
+    const int np = min(W.cnt[1], LS_MAX_PRED);
+    const uint8_t* t = W.touch + (int64_t)gid * LS_MAX_PRED;
+    int s = 0;
+    for (int p = tid; p < np; p += 256)
+        if (t[p]) { s += W.psize[p]; W.matched[p] = 1; }
+    for (int m = 32; m > 0; m >>= 1) s += __shfl_xor(s, m);
+    if ((tid & 63) == 0 && s) atomicAdd(&total, s);
+    __syncthreads();
+    if (tid == 0) { row[0] = W.groot[gid]; row[1] = W.tp[gid]; row[2] = W.gvol[gid]; row[3] = total; }
+}
+
+// matched is final (launch boundary).  One workgroup per region counts the components no lesion touches and writes the header.
+__global__ __launch_bounds__(256) void lesion_header_kernel(void* ws, int* __restrict__ header, int64_t volumes) {
+    __shared__ int nfp, fpv;
+    const int64_t v = blockIdx.x;
+    const int tid = threadIdx.x;
+    const LesionWs W = lesion_ws(ws, volumes, v);
+    if (tid == 0) { nfp = 0; fpv = 0; }
+    __syncthreads();
+    const int np = min(W.cnt[1], LS_MAX_PRED);
+    int n = 0, s = 0;
+    for (int p = tid; p < np; p += 256)
+        if (!W.matched[p]) { ++n; s += W.psize[p]; }
+    for (int m = 32; m > 0; m >>= 1) { n += __shfl_xor(n, m); s += __shfl_xor(s, m); }
+    if ((tid & 63) == 0 && n) { atomicAdd(&nfp, n); atomicAdd(&fpv, s); }
+    __syncthreads();
+    if (tid < LS_HEADER) {
+        const int over = (W.cnt[2] != 0 || W.cnt[0] > LS_MAX_GT || W.cnt[1] > LS_MAX_PRED) ? 1 : 0;
+        header[v * LS_HEADER + tid] = tid == 0 ? W.cnt[0] : tid == 1 ? W.cnt[1] : tid == 2 ? nfp : tid == 3 ? fpv : tid == 4 ? over : 0;
+    }
+}
+
 // ---- which labels stay ---------------------------------------------------------------------------------------------------------------------------------------
 struct Top2 { int c1, l1, c2, l2; };                         // the best and the second candidate (count, label); count -1 = none
 __device__ __forceinline__ bool frag_better(int ca, int la, int cb, int lb) { return ca > cb || (ca == cb && la < lb); }     // ties: the lower label (background = 0) first
@@ -605,6 +801,76 @@ extern "C" int segx_brats_relabel(const uint8_t* labels, const float* wt, const 
     SEGX_REQUIRE(S > 0 && S < ((int64_t)1 << 31), "segx_brats_relabel: S = %lld is not in 1 .. 2^31 - 1", (long long)S);
     hipLaunchKernelGGL(brats_pp_relabel_kernel, dim3(grid_for(S)), dim3(256), 0, stream, labels, wt, flag, out, S);
     return check_launch("segx_brats_relabel");
+}
+
+// the KIND of a mask operand (mask_set) from the ABI's (bytes, map) pair; 0 = refused
+static int lesion_mask_kind(int bytes, int map, int64_t volumes) {
+    if (map == SEGX_LESION_MAP_NONE) return bytes == 1 || bytes == 4 ? bytes : 0;
+    return map == SEGX_LESION_MAP_BRATS && bytes == 4 && volumes == 3 ? MASK_BRATS : 0;
+}
+
+extern "C" int64_t segx_lesion_ws_bytes(int64_t volumes) {
+    return volumes < 1 ? 0 : volumes * ((int64_t)LS_INTS * 4 + (int64_t)LS_MAX_GT * LS_MAX_PRED);
+}
+
+extern "C" int segx_dilate3d(const void* src, int src_bytes, int src_map, uint8_t* out, uint8_t* tmp, int64_t volumes, int X, int Y, int Z, int connectivity,
+                             int iters, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(src && out, "segx_dilate3d: null pointer");
+    SEGX_REQUIRE(volumes > 0 && X > 0 && Y > 0 && Z > 0, "segx_dilate3d: volumes, X, Y and Z must be positive");
+    const int64_t S = (int64_t)X * Y * Z;
+    SEGX_REQUIRE(S < SEGX_CCL_MAX_PLANE, "segx_dilate3d: X * Y * Z = %lld is not below the limit of 2^30 voxels per volume", (long long)S);
+    const int kind = lesion_mask_kind(src_bytes, src_map, volumes);
+    SEGX_REQUIRE(kind != 0, "segx_dilate3d: src_bytes %d with src_map %d over %lld volumes is no mask operand (uint8 / float32, or the raw BraTS labels: int32, 3 regions)",
+                 src_bytes, src_map, (long long)volumes);
+    SEGX_REQUIRE(connectivity == 6 || connectivity == 18 || connectivity == 26, "segx_dilate3d: connectivity %d is not 6, 18 or 26", connectivity);
+    SEGX_REQUIRE(iters >= 0, "segx_dilate3d: iters %d is negative", iters);
+    SEGX_REQUIRE(iters < 2 || (tmp && tmp != out), "segx_dilate3d: two or more iterations need tmp, another buffer than out");
+    SEGX_REQUIRE((const void*)out != src && (const void*)tmp != src, "segx_dilate3d: out and tmp must not be src");
+    const int maxd = connectivity == 6 ? 1 : connectivity == 18 ? 2 : 3;
+    const int ty = (Y + C3_TY - 1) / C3_TY, tz = (Z + C3_TZ - 1) / C3_TZ;
+    const int64_t per = (int64_t)((X + C3_TX - 1) / C3_TX) * ty * tz, tiles = volumes * per;
+    SEGX_REQUIRE(tiles < ((int64_t)1 << 24), "segx_dilate3d: %lld tiles exceed one grid (2^24 workgroups of 256 threads)", (long long)tiles);
+    const dim3 grid((unsigned)tiles);
+    // pass k of n writes out when n - 1 - k is even, so the last one lands in out; pass 0 reads src in its own type, the others the bytes of the pass before
+    const int n = iters > 0 ? iters : 1;
+    uint8_t* first = (n - 1) % 2 == 0 ? out : tmp;
+    const int d0 = iters > 0 ? maxd : 0;
+    if (kind == 1) hipLaunchKernelGGL(dilate3_kernel<1>, grid, dim3(256), 0, stream, src, first, X, Y, Z, ty, tz, (int)per, d0);
+    else if (kind == 4) hipLaunchKernelGGL(dilate3_kernel<4>, grid, dim3(256), 0, stream, src, first, X, Y, Z, ty, tz, (int)per, d0);
+    else hipLaunchKernelGGL(dilate3_kernel<MASK_BRATS>, grid, dim3(256), 0, stream, src, first, X, Y, Z, ty, tz, (int)per, d0);
+    for (int k = 1; k < n; ++k) {
+        uint8_t* from = (n - k) % 2 == 0 ? out : tmp;
+        uint8_t* to = from == out ? tmp : out;
+        hipLaunchKernelGGL(dilate3_kernel<1>, grid, dim3(256), 0, stream, (const void*)from, to, X, Y, Z, ty, tz, (int)per, maxd);
+    }
+    return check_launch("segx_dilate3d");
+}
+
+extern "C" int segx_lesion_match(const void* gt, int gt_bytes, int gt_map, const int32_t* gl, int32_t* gsizes, const int32_t* pl, int32_t* psizes, void* ws,
+                                 int64_t volumes, int64_t S, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(gt && gl && gsizes && pl && psizes && ws, "segx_lesion_match: null pointer");
+    SEGX_REQUIRE(volumes > 0 && volumes <= 65535 && S > 0, "segx_lesion_match: 1 <= volumes <= 65535 and S > 0");
+    SEGX_REQUIRE(S < SEGX_CCL_MAX_PLANE, "segx_lesion_match: S = %lld is not below the limit of 2^30 voxels per volume", (long long)S);
+    SEGX_REQUIRE(((uintptr_t)ws & 15) == 0, "segx_lesion_match: ws must be 16-byte aligned");
+    const int kind = lesion_mask_kind(gt_bytes, gt_map, volumes);
+    SEGX_REQUIRE(kind != 0, "segx_lesion_match: gt_bytes %d with gt_map %d over %lld volumes is no mask operand (uint8 / float32, or the raw BraTS labels: int32, 3 regions)",
+                 gt_bytes, gt_map, (long long)volumes);
+    const dim3 grid(grid_for(volumes * S)), rows((unsigned)(volumes * LS_MAX_GT));
+    hipLaunchKernelGGL(cc3_zero_kernel, dim3(grid_for(volumes * LS_INTS)), dim3(256), 0, stream, (int*)ws, volumes * LS_INTS);
+    hipLaunchKernelGGL(lesion_ids_kernel, grid, dim3(256), 0, stream, gsizes, psizes, ws, volumes, (int)S);
+    hipLaunchKernelGGL(lesion_clear_touch_kernel, rows, dim3(256), 0, stream, ws, volumes);
+    if (kind == 1) hipLaunchKernelGGL(lesion_match_kernel<1>, grid, dim3(256), 0, stream, gt, gl, (const int*)gsizes, pl, (const int*)psizes, ws, volumes, (int)S);
+    else if (kind == 4) hipLaunchKernelGGL(lesion_match_kernel<4>, grid, dim3(256), 0, stream, gt, gl, (const int*)gsizes, pl, (const int*)psizes, ws, volumes, (int)S);
+    else hipLaunchKernelGGL(lesion_match_kernel<MASK_BRATS>, grid, dim3(256), 0, stream, gt, gl, (const int*)gsizes, pl, (const int*)psizes, ws, volumes, (int)S);
+    return check_launch("segx_lesion_match");
+}
+
+extern "C" int segx_lesion_reduce(void* ws, int32_t* rows, int32_t* header, int64_t volumes, void* stream_) {
+    SEGX_STREAM; SEGX_REQUIRE(ws && rows && header, "segx_lesion_reduce: null pointer");
+    SEGX_REQUIRE(volumes > 0 && volumes <= 65535, "segx_lesion_reduce: 1 <= volumes <= 65535");
+    hipLaunchKernelGGL(lesion_rows_kernel, dim3((unsigned)(volumes * LS_MAX_GT)), dim3(256), 0, stream, ws, rows, volumes);
+    hipLaunchKernelGGL(lesion_header_kernel, dim3((unsigned)volumes), dim3(256), 0, stream, ws, header, volumes);
+    return check_launch("segx_lesion_reduce");
 }
 
 extern "C" int segx_frag_keep2(const int32_t* sizes, int32_t* keep, int64_t planes, int H, int W, void* stream_) {

@@ -3100,6 +3100,92 @@ def brats_relabel(labels, hard_pp, flag, out=None):
     return out
 
 
+# -------------------------------------------------------------------------------------------------
+# Lesion-wise evaluation (components.hip): dilation of the ground truth, the matching of predicted components to lesions and the per-lesion integer
+# rows.  No copy to the host and no synchronisation, so the calls can be captured into a graph.  Forward only.
+# -------------------------------------------------------------------------------------------------
+DILATION_CONNECTIVITIES = (6, 18, 26)
+
+
+def check_dilation(what, iters, connectivity):
+    """(iters, connectivity) of a dilation: a non-negative iteration count and a structuring element of 6, 18 or 26 neighbours"""
+    if connectivity not in DILATION_CONNECTIVITIES or isinstance(connectivity, bool):
+        raise ValueError('%s: dilation connectivity %r is not 6, 18 or 26' % (what, connectivity))
+    try:
+        ok = not isinstance(iters, bool) and int(iters) == iters and 0 <= int(iters) < 1 << 15
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError('%s: dilation_iters = %r is not a non-negative iteration count' % (what, iters))
+    return int(iters), int(connectivity)
+
+
+def _gt_operand(what, gt, gt_map):
+    """(tensor the kernels read, map code, V, X, Y, Z) of a ground truth: a mask stack as _volumes_operand takes it, or with gt_map='brats' ONE raw label volume
+    [X, Y, Z] (any integer or float type, read as int32) that stands for the three regions ET, WT, TC"""
+    if gt_map not in segx.SegxLib.LESION_MAPS:
+        raise ValueError('%s: gt_map %r is not one of %s' % (what, gt_map, sorted(segx.SegxLib.LESION_MAPS, key=str)))
+    if gt_map is None:
+        m, V, X, Y, Z = _volumes_operand(what, gt)
+        return m, 0, V, X, Y, Z
+    if gt.dim() != 3 or gt.numel() < 1 or gt.dtype == torch.bool:
+        raise ValueError("%s: gt_map='brats' takes one raw label volume [X, Y, Z], not %s %s" % (what, gt.dtype, tuple(gt.shape)))
+    if gt.numel() >= segx.SegxLib.CCL_MAX_PLANE:
+        raise ValueError('%s: X * Y * Z = %d is not below the limit of 2^30 voxels per volume' % (what, gt.numel()))
+    g = _c(gt.detach())
+    return (g if g.dtype == torch.int32 else g.to(torch.int32), segx.SegxLib.LESION_MAPS[gt_map], 3) + tuple(gt.shape)
+
+
+def _dilate(what, g, gmap, V, X, Y, Z, iters, conn):
+    out = torch.empty((V, X, Y, Z), dtype=torch.uint8, device=g.device)
+    tmp = torch.empty_like(out) if iters >= 2 else None
+    segx.lib().dilate3d(g, gmap, out, tmp, V, X, Y, Z, conn, iters)
+    return out
+
+
+def dilate3d(mask, iters=1, connectivity=18, gt_map=None):
+    """uint8 0 / 1 of the mask's shape: a bool / uint8 / float mask [X, Y, Z] or [V, X, Y, Z] (set = not 0) dilated `iters` times by the 3 x 3 x 3 structuring element
+    of the centre and its 6, 18 or 26 nearest neighbours (segx_dilate3d) -- scipy.ndimage.binary_dilation(mask, generate_binary_structure(3, 1 | 2 | 3), iters);
+    outside the volume is unset.  iters = 0 gives the mask itself as bytes.  gt_map='brats': mask is one raw BraTS label volume, the result the [3, X, Y, Z] stack of
+    its dilated ET, WT and TC regions."""
+    iters, conn = check_dilation('dilate3d', iters, connectivity)
+    g, gmap, V, X, Y, Z = _gt_operand('dilate3d', mask, gt_map)
+    out = _dilate('dilate3d', g, gmap, V, X, Y, Z, iters, conn)
+    return out[0] if mask.dim() == 3 and gt_map is None else out
+
+
+def lesion_rows(pred, gt, *, gt_map=None, dilation_iters=3, dilation_connectivity=18, connectivity=26, out=None):
+    """The device tables of the lesion-wise evaluation of a stack of binary regions, without reading them: (rows, header) with rows int32
+    [V, LESION_MAX_GT, 4] = (root label, tp, gvol, pvol) per lesion in arbitrary order, zeros behind the last, and header int32 [V, LESION_HEADER] =
+    (n_lesions, n_pred_components, n_fp, fp_voxels, overflow, 0, 0, 0).  pred, gt: bool / uint8 / float [V, X, Y, Z] or [X, Y, Z] (set = not 0); with
+    gt_map='brats' gt is the raw label volume [X, Y, Z] and pred the [3, X, Y, Z] stack of ET, WT, TC (channels 1..3 of preds_hard).  The ground truth is dilated
+    (segx_dilate3d), both maps are labelled (segx_ccl3d at `connectivity`), then segx_lesion_match and segx_lesion_reduce.  out = (rows, header): contiguous
+    int32 tensors of those shapes to write into.  The inputs are not modified; infer3d.lesionwise_from_tables turns the tables into the metrics."""
+    what = 'lesion_rows'
+    iters, dconn = check_dilation(what, dilation_iters, dilation_connectivity)
+    conn = check_connectivity3d(what, connectivity)
+    p, V, X, Y, Z = _volumes_operand(what, pred)
+    g, gmap, Vg, Xg, Yg, Zg = _gt_operand(what, gt, gt_map)
+    if (V, X, Y, Z) != (Vg, Xg, Yg, Zg):
+        raise ValueError('%s: pred %s and gt %s (gt_map %r) are not the same stack of regions' % (what, tuple(pred.shape), tuple(gt.shape), gt_map))
+    L = segx.lib()
+    shape = ((V, L.LESION_MAX_GT, 4), (V, L.LESION_HEADER))
+    if out is None:
+        out = tuple(torch.empty(s, dtype=torch.int32, device=p.device) for s in shape)
+    elif len(out) != 2 or any(t.dtype != torch.int32 or tuple(t.shape) != s or not t.is_contiguous() for t, s in zip(out, shape)):
+        raise ValueError('%s: out is a pair of contiguous int32 tensors %s and %s' % ((what,) + shape))
+    rows, header = out
+    gd = g if iters == 0 and gmap == 0 else _dilate(what, g, gmap, V, X, Y, Z, iters, dconn)         # no dilation of a plain mask: it is labelled as it is
+    gl = torch.empty((V, X, Y, Z), dtype=torch.int32, device=p.device)
+    gsizes, pl, psizes = torch.empty_like(gl), torch.empty_like(gl), torch.empty_like(gl)
+    L.ccl3d(gd, 0, gl, gsizes, V, X, Y, Z, conn)
+    L.ccl3d(p, 0, pl, psizes, V, X, Y, Z, conn)
+    ws = torch.empty(L.lesion_ws_bytes(V), dtype=torch.uint8, device=p.device)
+    L.lesion_match(g, gmap, gl, gsizes, pl, psizes, ws, V, X * Y * Z)
+    L.lesion_reduce(ws, rows, header, V)
+    return rows, header
+
+
 def row_extent(mask, thres):
     """int32 [P, 2] (or [2] for one [H, W] plane): the lowest and the highest row index of each plane of the float mask that holds a value >= thres; (H, -1) where
     none does."""

@@ -12,7 +12,10 @@ eager loop's batches, one merge launch), GraphedSlidingWindow3d (that sequence w
 and test_all_cases (the reference's loop over the cases of a dataset, test_util3d.py:15-91, without its file I/O).
 
 And the step a BraTS user runs on the prediction: connected_components, remove_small_components and postprocess_brats on the device, and the
-`postprocess=` argument that places the rule between the merge and the case tail of test_single_case, GraphedSlidingWindow3d and test_all_cases."""
+`postprocess=` argument that places the rule between the merge and the case tail of test_single_case, GraphedSlidingWindow3d and test_all_cases.
+
+And the lesion-wise evaluation: lesionwise_metrics / lesionwise_from_tables (per-lesion Dice, detections and false positives from device tables) and the
+`lesionwise=` argument of GraphedSlidingWindow3d and test_all_cases."""
 import math
 import os
 
@@ -21,6 +24,7 @@ import torch
 
 from . import functional as SF
 from . import test_util3d as _T3
+from .segx import SegxLib
 from .infer_common import PRECISIONS, GraphedEvaluation, _precision, composed_tta, folded, inference_precision, run_chunks, view_chunks      # noqa: F401  (inference_precision: re-exported)
 
 
@@ -149,6 +153,82 @@ def postprocess_brats(preds_hard, labels=None, *, wt_min_voxels=0, wt_largest_on
     with torch.no_grad():
         hard, flag = SF.brats_postprocess(preds_hard, **p)
         return hard if labels is None else (hard, SF.brats_relabel(labels, hard, flag))
+
+
+# ---- lesion-wise evaluation -----------------------------------------------------------------------------------------------------------------
+LESIONWISE_KEYS = ('dilation_iters', 'dilation_connectivity', 'connectivity', 'min_lesion_voxels')
+
+
+def check_lesionwise(lesionwise, num_classes=4):
+    """the `lesionwise` argument of the evaluation entry points: None, or a dict of lesionwise_metrics' keyword arguments made complete and checked -- ValueError on an
+    unknown key, a negative dilation_iters, a dilation connectivity other than 6 / 18 / 26, a labelling connectivity other than 6 / 26, a negative
+    min_lesion_voxels or num_classes != 4, before anything is launched"""
+    if lesionwise is None:
+        return None
+    if not isinstance(lesionwise, dict):
+        raise ValueError('lesionwise: None or a dict of %s, not %r' % (LESIONWISE_KEYS, lesionwise))
+    unknown = sorted(set(lesionwise) - set(LESIONWISE_KEYS))
+    if unknown:
+        raise ValueError('lesionwise: unknown keys %s (known: %s)' % (unknown, LESIONWISE_KEYS))
+    if num_classes != 4:
+        raise ValueError('lesionwise: the BraTS regions need num_classes == 4, not %r' % (num_classes,))
+    p = dict(dilation_iters=3, dilation_connectivity=18, connectivity=26, min_lesion_voxels=0)
+    p.update(lesionwise)
+    p['dilation_iters'], p['dilation_connectivity'] = SF.check_dilation('lesionwise', p['dilation_iters'], p['dilation_connectivity'])
+    p['connectivity'] = SF.check_connectivity3d('lesionwise', p['connectivity'])
+    p['min_lesion_voxels'] = SF.check_voxel_count('lesionwise', 'min_lesion_voxels', p['min_lesion_voxels'])
+    return p
+
+
+def _kernel_args(lw):
+    return {k: v for k, v in lw.items() if k != 'min_lesion_voxels'}
+
+
+def lesionwise_from_tables(rows, header, min_lesion_voxels=0):
+    """The host half of lesionwise_metrics: rows [R, LESION_MAX_GT, 4] and header [R, LESION_HEADER] (SF.lesion_rows' tables, tensors or arrays, already read or
+    not) -> a list of R dicts.  'lesions': int64 [n, 4] rows (root label, tp, gvol, pvol) of ALL lesions sorted by root label; 'kept': bool [n], gvol >=
+    min_lesion_voxels; 'n_fp', 'fp_voxels': the predicted components that touch no lesion (an ignored lesion still counts as touched) and their voxels;
+    'n_detected', 'n_missed': kept lesions with and without tp > 0; 'lesion_dice': float64, the sum over the kept lesions (in the order of their root labels) of
+    2 tp / (gvol + pvol), divided by (kept lesions + n_fp), 1.0 when that is 0.  RuntimeError when a region exceeded a cap of the device tables (there is no slow
+    path)."""
+    nmin = SF.check_voxel_count('lesionwise_from_tables', 'min_lesion_voxels', min_lesion_voxels)
+    rows = (rows.cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)).astype(np.int64)
+    header = (header.cpu().numpy() if isinstance(header, torch.Tensor) else np.asarray(header)).astype(np.int64)
+    if rows.ndim != 3 or rows.shape[2] != 4 or header.ndim != 2 or header.shape[0] != rows.shape[0] or header.shape[1] < 5:
+        raise ValueError('lesionwise_from_tables: rows [R, MAX_GT, 4] and header [R, >= 5], not %r and %r' % (rows.shape, header.shape))
+    out = []
+    for r in range(rows.shape[0]):
+        n_all, n_pred, n_fp, fp_voxels, overflow = (int(v) for v in header[r, :5])
+        if overflow or n_all > rows.shape[1]:
+            raise RuntimeError('lesion-wise evaluation: region %d holds %d lesions and %d predicted components, more than the device tables take (%d and %d)'
+                               % (r, n_all, n_pred, rows.shape[1], SegxLib.LESION_MAX_PRED))
+        les = rows[r, :n_all]
+        les = les[np.argsort(les[:, 0], kind='stable')]
+        kept = les[:, 2] >= nmin
+        total = 0.0
+        for _, tp, gvol, pvol in les[kept].tolist():
+            total += 2.0 * tp / (gvol + pvol)
+        n = int(kept.sum())
+        detected = int((les[kept][:, 1] > 0).sum())
+        out.append(dict(lesions=les, kept=kept, n_fp=n_fp, fp_voxels=fp_voxels, n_detected=detected, n_missed=n - detected,
+                        lesion_dice=total / (n + n_fp) if n + n_fp > 0 else 1.0))
+    return out
+
+
+def lesionwise_metrics(pred, gt, *, dilation_iters=3, dilation_connectivity=18, connectivity=26, min_lesion_voxels=0):
+    """Lesion-wise Dice and detection counts (the per-lesion scoring BraTS uses since 2023; DESIGN.md 5zb defines it) of two stacks of binary device volumes
+    [R, X, Y, Z], or one volume [X, Y, Z] (bool, uint8 or float; set = not 0).  The ground truth is dilated dilation_iters times by the 3 x 3 x 3 element of
+    dilation_connectivity neighbours; a lesion is the ground truth inside one `connectivity`-connected component of the dilated map; a predicted component that
+    shares a voxel with that component touches the lesion.  Everything up to the integer rows runs on the device (SF.lesion_rows); ONE device-to-host copy brings them,
+    and lesionwise_from_tables forms the quotients in float64.  Returns its list of R dicts."""
+    lw = check_lesionwise(dict(dilation_iters=dilation_iters, dilation_connectivity=dilation_connectivity, connectivity=connectivity,
+                               min_lesion_voxels=min_lesion_voxels))
+    _device_operand('lesionwise_metrics', pred)
+    _device_operand('lesionwise_metrics', gt)
+    with torch.no_grad():
+        rows, header = SF.lesion_rows(pred, gt, **_kernel_args(lw))
+        both = torch.cat([rows.view(rows.shape[0], -1), header], 1).cpu().numpy()         # the one device-to-host copy
+    return lesionwise_from_tables(both[:, :rows.shape[1] * 4].reshape(rows.shape), both[:, rows.shape[1] * 4:], lw['min_lesion_voxels'])
 
 
 def _check_task(net_type, task_name):
@@ -291,15 +371,23 @@ class GraphedSlidingWindow3d(GraphedEvaluation):
     tta: flip test-time augmentation as test_single_case(fused=True, tta=) runs it, inside the capture; the buffers then hold V times as much, and the case tail reads
     the averaged map.
     postprocess: None (default: exactly the capture without it) or a dict of postprocess_brats' keyword arguments: the rule runs inside the capture between the merge
-    and the case tail, so preds_hard, the counts and the label volume are the post-processed ones; preds_soft is the merged map unchanged."""
+    and the case tail, so preds_hard, the counts and the label volume are the post-processed ones; preds_soft is the merged map unchanged.
+    lesionwise: None (default: exactly the capture without it) or a dict of lesionwise_metrics' keyword arguments; needs with_mask=True (ValueError otherwise).  The
+    dilation of the ground truth, the two labellings and the lesion kernels (SF.lesion_rows with gt_map='brats' on channels 1..3 of preds_hard) run inside the
+    capture after the rule and the case tail; __call__ keeps its 4-tuple, the STATIC tables are the attributes lesion_rows [3, LESION_MAX_GT, 4] and
+    lesion_header [3, LESION_HEADER] (lesionwise_from_tables reads them).  The capture then holds four more int32 and two more byte volumes per region."""
 
     _fold, _unfold = staticmethod(fold_batchnorm), staticmethod(unfold_batchnorm)
 
     def __init__(self, net, image_shape, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, num_classes=4, fold_bn=True, warmup=2,
-                 precision='fp32', with_labels=True, with_mask=False, tta=None, postprocess=None):
+                 precision='fp32', with_labels=True, with_mask=False, tta=None, postprocess=None, lesionwise=None):
         self.with_labels, self.with_mask = bool(with_labels), bool(with_mask)
         views = None if tta is None else SF.check_views(tta, 3)                      # refused before the net is folded or anything is launched
         self.post = check_postprocess(postprocess, num_classes)
+        self.lw = check_lesionwise(lesionwise, num_classes)
+        if self.lw is not None and not self.with_mask:
+            raise ValueError('GraphedSlidingWindow3d: lesionwise= needs the ground truth: build it with_mask=True')
+        self.lesion_rows = self.lesion_header = None
         super().__init__(net, num_classes, fold_bn, warmup, precision, image_shape, orig_patch_size, input_patch_size, batch_size, stride_xy, stride_z, views)
 
     def _build(self, device, *plan_args):
@@ -309,6 +397,9 @@ class GraphedSlidingWindow3d(GraphedEvaluation):
         self.counts = torch.zeros(3, 3, dtype=torch.int32, device=device) if self.with_mask else None
         self.labels = torch.zeros(spatial, dtype=torch.uint8, device=device) if self.with_labels else None
         self.flag = torch.zeros(2, dtype=torch.int32, device=device) if self.post is not None else None
+        if self.lw is not None:
+            self.lesion_rows = torch.zeros(3, SegxLib.LESION_MAX_GT, 4, dtype=torch.int32, device=device)
+            self.lesion_header = torch.zeros(3, SegxLib.LESION_HEADER, dtype=torch.int32, device=device)
 
     def _sequence(self):
         hard, soft = self.plan.run(self.net, self.image)
@@ -318,6 +409,8 @@ class GraphedSlidingWindow3d(GraphedEvaluation):
             SF.brats_case_tail(soft, hard, self.mask, want_labels=self.with_labels, counts=self.counts, labels=self.labels)
         if self.post is not None and self.with_labels:
             SF.brats_relabel(self.labels, hard, self.flag, out=self.labels)
+        if self.lw is not None:
+            SF.lesion_rows(hard[1:4], self.mask, gt_map='brats', out=(self.lesion_rows, self.lesion_header), **_kernel_args(self.lw))
         return hard, soft
 
     def _check_classes(self):
@@ -338,12 +431,12 @@ class GraphedSlidingWindow3d(GraphedEvaluation):
     def close(self):
         """GraphedEvaluation.close(), and drop the case's static buffers as well"""
         super().close()
-        self.labels = self.counts = self.image = self.mask = self.flag = None
+        self.labels = self.counts = self.image = self.mask = self.flag = self.lesion_rows = self.lesion_header = None
 
 
 def test_all_cases(net, db_test, task_name='brats', net_type='segtran', num_classes=4, batch_size=8, orig_patch_size=(128, 112, 80),
                    input_patch_size=(128, 112, 64), stride_xy=56, stride_z=40, has_mask=True, on_labels=None, fused=True, graph=False, surface=False, hd95=False,
-                   precision='fp32', fold_bn=False, tta=None, postprocess=None):
+                   precision='fp32', fold_bn=False, tta=None, postprocess=None, lesionwise=None):
     """The reference's evaluation loop over the cases of a dataset (test_util3d.py:15-91) for the BraTS task, without its file I/O; returns avg_metric
     [num_classes - 1, 4] (columns dice, jc, hd, asd) = the sum of the cases' metrics over the number of cases in which each entry is valid, as the reference does
     (an entry valid in no case is 0 / 0 = NaN).
@@ -359,8 +452,15 @@ def test_all_cases(net, db_test, task_name='brats', net_type='segtran', num_clas
     fold_bn: ONE fold for all the cases; precision: as test_single_case.  The reference's test_interp is not built.
     tta: flip test-time augmentation of every case's evaluation, as test_single_case takes it (fused, eager or graph).
     postprocess: None or a dict of postprocess_brats' keyword arguments: the rule runs on the device between every case's merge and its tail, so the Dice / Jaccard
-    counts, the surface columns and the on_labels volumes all see the post-processed prediction."""
+    counts, the surface columns and the on_labels volumes all see the post-processed prediction.
+    lesionwise: None (default: the return value is avg_metric alone, nothing more is launched or allocated) or a dict of lesionwise_metrics' keyword arguments: every
+    case's lesion tables (SF.lesion_rows on channels 1..3 of the -- post-processed -- preds_hard against the raw mask, gt_map='brats') stay on the device and are
+    read once after the loop, and the call returns (avg_metric, lw) with lw['cases'][i][r] = lesionwise_from_tables' dict of case i and region r (ET, WT, TC) and
+    lw['mean_lesion_dice'] [3] = the mean of lesion_dice over the cases.  Needs has_mask (ValueError otherwise)."""
     post = check_postprocess(postprocess, num_classes)
+    lw = check_lesionwise(lesionwise, num_classes)
+    if lw is not None and not has_mask:
+        raise ValueError('test_all_cases: lesionwise= needs the ground truth (has_mask=True)')
     _check_task(net_type, task_name)
     views = None if tta is None else SF.check_views(tta, 3)
     if num_classes != 4:
@@ -369,6 +469,10 @@ def test_all_cases(net, db_test, task_name='brats', net_type='segtran', num_clas
     ncases = len(db_test)
     device = next(net.parameters()).device
     counts_all = torch.zeros(ncases, 3, 3, dtype=torch.int32, device=device) if has_mask else None
+    lesion_tables = None
+    if lw is not None:
+        lesion_tables = (torch.zeros(ncases, 3, SegxLib.LESION_MAX_GT, 4, dtype=torch.int32, device=device),
+                         torch.zeros(ncases, 3, SegxLib.LESION_HEADER, dtype=torch.int32, device=device))
     surf = []
     graphs = {}
     try:
@@ -383,10 +487,14 @@ def test_all_cases(net, db_test, task_name='brats', net_type='segtran', num_clas
                     if g is None:
                         g = graphs[tuple(image.shape)] = GraphedSlidingWindow3d(net, image.shape, orig_patch_size, input_patch_size, batch_size, stride_xy,
                                                                                 stride_z, num_classes, fold_bn=False, precision=precision,
-                                                                                with_labels=want_labels, with_mask=has_mask, tta=views, postprocess=post)
+                                                                                with_labels=want_labels, with_mask=has_mask, tta=views, postprocess=post,
+                                                                                lesionwise=lw)
                     preds_hard, _, labels, counts = g(image, mask) if has_mask else g(image)
                     if has_mask:
                         counts_all[i].copy_(counts)
+                    if lw is not None:
+                        lesion_tables[0][i].copy_(g.lesion_rows)
+                        lesion_tables[1][i].copy_(g.lesion_header)
                     if want_labels:
                         labels = labels.clone()                 # the graph's static volume: the next replay overwrites it
                 else:
@@ -399,6 +507,8 @@ def test_all_cases(net, db_test, task_name='brats', net_type='segtran', num_clas
                         _, labels = SF.brats_case_tail(preds_soft, preds_hard, mask, want_labels=want_labels, counts=counts_all[i] if has_mask else None)
                     if post is not None and want_labels:
                         labels = SF.brats_relabel(labels, preds_hard, flag, out=labels)
+                    if lw is not None:
+                        SF.lesion_rows(preds_hard[1:4], mask, gt_map='brats', out=(lesion_tables[0][i], lesion_tables[1][i]), **_kernel_args(lw))
                 if surface and has_mask:
                     gt = SF.label_nhot((mask - (mask == 4).to(mask.dtype)).unsqueeze(0), 'brats')[0]
                     surf.append(surface_metrics(preds_hard[1:num_classes], gt[1:num_classes], hd95=hd95))
@@ -420,7 +530,12 @@ def test_all_cases(net, db_test, task_name='brats', net_type='segtran', num_clas
     else:
         valid_counts += ncases
     with np.errstate(divide='ignore', invalid='ignore'):
-        return total / valid_counts
+        avg_metric = total / valid_counts
+    if lw is None:
+        return avg_metric
+    cases = [lesionwise_from_tables(r, h, lw['min_lesion_voxels']) for r, h in zip(lesion_tables[0].cpu().numpy(), lesion_tables[1].cpu().numpy())]
+    mean = np.array([[c[r]['lesion_dice'] for r in range(3)] for c in cases], dtype=np.float64).reshape(ncases, 3).mean(0) if ncases else np.full(3, np.nan)
+    return avg_metric, dict(cases=cases, mean_lesion_dice=mean)
 
 
 test_all_cases.__test__ = False

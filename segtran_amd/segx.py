@@ -102,7 +102,7 @@ class SegxLib:
         for name, sig in _SIGS.items():
             fn = getattr(self.c, name)
             fn.argtypes = [kinds[k] for k in sig]
-            fn.restype = c_l if name.endswith(('_floats', '_rows', '_splitk', '_elems', '_chunks', '_nparts')) else c_i
+            fn.restype = c_l if name.endswith(('_floats', '_rows', '_splitk', '_elems', '_chunks', '_nparts', '_bytes')) else c_i
 
     # ---- tile engine -------------------------------------------------------------------------
     ENGINES = {'f32': 0, 'x6': 1}
@@ -734,6 +734,22 @@ class SegxLib:
     def brats_relabel(self, labels, wt, flag, out, S):
         self._call('segx_brats_relabel', out, labels, wt, flag, out, S)
 
+    # ---- lesion-wise evaluation (components.hip) -----------------------------------------------------------
+    LESION_MAX_GT, LESION_MAX_PRED, LESION_HEADER = 1024, 16384, 8       # SEGX_LESION_MAX_GT / _MAX_PRED / _HEADER of include/segx.h
+    LESION_MAPS = {None: 0, 'brats': 1}                                  # SEGX_LESION_MAP_NONE / _BRATS
+
+    def dilate3d(self, src, src_map, out, tmp, volumes, X, Y, Z, connectivity, iters):
+        self._call('segx_dilate3d', out, src, src.element_size(), int(src_map), out, tmp, volumes, X, Y, Z, int(connectivity), int(iters))
+
+    def lesion_ws_bytes(self, volumes):
+        return int(self.c.segx_lesion_ws_bytes(volumes))
+
+    def lesion_match(self, gt, gt_map, gl, gsizes, pl, psizes, ws, volumes, S):
+        self._call('segx_lesion_match', ws, gt, gt.element_size(), int(gt_map), gl, gsizes, pl, psizes, ws, volumes, S)
+
+    def lesion_reduce(self, ws, rows, header, volumes):
+        self._call('segx_lesion_reduce', rows, ws, rows, header, volumes)
+
     def conv3d_splitk(self, B, Cout, geom, wgrad):
         return int(self.c.segx_conv3d_splitk(B, Cout, self._geom(geom), 1 if wgrad else 0))
 
@@ -934,6 +950,7 @@ _SIGS = {
     'segx_index_onehot': 'piplilp', 'segx_onehot_colormap': 'ppplilp', 'segx_onehot_case_tail': 'ppppppiilfp', 'segx_nhot_case_tail': 'ppiipppppiiiiiifp',
     'segx_ccl2d': 'pippliip', 'segx_frag_keep2': 'ppliip', 'segx_frag_apply': 'ppppliiip', 'segx_row_extent': 'ppliifp', 'segx_nhot_to_values': 'ppplilp',
     'segx_ccl3d': 'piippliiiip', 'segx_cc3d_keep': 'pppplliip', 'segx_mask_apply': 'pipplp', 'segx_brats_postprocess': 'pppplip', 'segx_brats_relabel': 'pppplp',
+    'segx_dilate3d': 'piippliiiiip', 'segx_lesion_ws_bytes': 'l', 'segx_lesion_match': 'piipppppllp', 'segx_lesion_reduce': 'ppplp',
     'segx_conv3d_fwd': 'pppiipipp', 'segx_conv3d_fwd_packed': 'pppiipipp', 'segx_conv3d_fwd_packed_bs': 'pppiipipllp', 'segx_conv3d_bwd_weight_packed_bs': 'pppiipipllp', 'segx_conv3d_pack_weights': 'ppiiiip', 'segx_conv3d_splitk': 'iipi', 'segx_conv3d_route': 'iipiiiip', 'segx_conv3d_fwd_terms': 'iipiii', 'segx_conv3d_flip_weights': 'ppiiip', 'segx_conv3d_bwd_weight': 'pppiipipp', 'segx_conv3d_bwd_weight_packed': 'pppiipipp', 'segx_conv3d_unpack_wgrad': 'ppiiip',
     'segx_conv3d_halo_ok': 'iip', 'segx_conv3d_halo_wq_floats': 'ii', 'segx_conv3d_halo_pack': 'ppiiip', 'segx_conv3d_halo_fwd': 'pppiipllip', 'segx_conv3d_halo_bias_act_fwd': 'ppppiiplliip', 'segx_conv3d_fwd_bias_act': 'ppppiipipillip', 'segx_bias_map_relu': 'ppilp', 'segx_conv3d_halo_wgrad_ok': 'iip', 'segx_conv3d_halo_wgrad_ws_floats': 'iip', 'segx_conv3d_halo_wgrad': 'ppppiipllp',
     'segx_conv3d_bwd_data_direct': 'ppppiipp', 'segx_nonzero_mask': 'ppiiiiiiiip', 'segx_label_nhot': 'ppiilip',
